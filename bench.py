@@ -73,6 +73,8 @@ RELEASE_TEXT = {
 FP32_MFMA_PEAK_TFLOPS = 157.3     # MI355X_MICROARCH.md chip table
 HBM_PEAK_GBS = 8000.0
 PMC_TRAFFIC_JSON = os.path.join(ROOT, 'profiles', 'pmc_traffic.json')
+DUMP_LIMIT_BYTES = 64 << 20       # --dump-outputs: all arrays together
+DUMP_ARENA_ENTRIES = 1 << 21      # parameter / gradient entries kept (a seeded sample above that)
 
 
 def dtype_label(model):
@@ -342,14 +344,54 @@ def pmc_traffic(workload, which, launch_steps):
                             'profiles/pmc_traffic.json'.format(workload, which, launch_steps)}
 
 
+def arena_sample_index(numel, limit=DUMP_ARENA_ENTRIES, seed=0):
+    """Entries of a parameter arena that `dump_outputs` keeps: all of them up to ``limit``, else
+    one seeded random entry from each of ``limit`` equal strata (covers every tensor of the
+    arena; the same entries for the same arena size in every run)."""
+    if numel <= limit:
+        return np.arange(numel, dtype=np.int64)
+    starts = np.arange(limit, dtype=np.int64) * numel // limit
+    widths = np.diff(np.append(starts, numel))
+    return starts + np.random.default_rng(seed).integers(0, widths)
+
+
+def dump_outputs(directory, model, loss):
+    """``--dump-outputs DIR``: what the last timed training step computed, as DIR/<name>.npy -
+    the mean loss `train_step` returned, the per-utterance losses, the logits [T', B, C] and
+    their lengths, and the arena's parameters after that step's Adam update with the gradients
+    that went into it (a fixed sample of arena entries above DUMP_ARENA_ENTRIES, their indices in
+    ``arena_index``).  Everything float32 / float64, at most DUMP_LIMIT_BYTES."""
+    torch.cuda.synchronize()
+    arena = model.arena
+    index = arena_sample_index(arena.param.numel())
+    index_d = torch.from_numpy(index).to(arena.param.device)
+    arrays = {
+        'loss': np.asarray(float(loss), dtype=np.float64),
+        'per_utterance_loss': model.last_per_utterance_loss.double().cpu().numpy(),
+        'logits': model.last_logits.float().cpu().numpy(),
+        'logit_lengths': model.last_seq_length.double().cpu().numpy(),
+        'arena_index': index.astype(np.float64),
+        'param': arena.param.index_select(0, index_d).cpu().numpy(),
+        'grad': arena.grad.index_select(0, index_d).cpu().numpy(),
+    }
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise RuntimeError('--dump-outputs: {} bytes exceed the {} byte limit'.format(
+            total, DUMP_LIMIT_BYTES))
+    os.makedirs(directory, exist_ok=True)
+    for key, value in arrays.items():
+        assert value.dtype in (np.float32, np.float64), (key, value.dtype)
+        np.save(os.path.join(directory, key + '.npy'), value)
+
+
 def measure(name, args, rank, local_rank, world, allreduce_early=None, reduce=True,
-            model_attrs=None, stand_in=None):
+            model_attrs=None, stand_in=None, dump=None):
     """Build the workload ``name`` on this rank's GPU, run warm-up + timed steps under the
     contract's protocol and return the result dict (rank 0) or None.  ``allreduce_early``
     selects the release mode of the gradient buckets (None: the environment / default),
     ``reduce=False`` runs the same step without any collective (to price the all-reduce),
     ``model_attrs`` overrides attributes of the CTCModel (which arithmetic the GEMMs run in:
-    PROBE_VARIANTS)."""
+    PROBE_VARIANTS), ``dump``: directory for `dump_outputs` of the last timed step (rank 0)."""
     from ctc_asr_amd import hip
     from ctc_asr_amd.engine import Trainer
     from ctc_asr_amd.model import CTCModel, GATES, ModelConfig
@@ -453,6 +495,8 @@ def measure(name, args, rank, local_rank, world, allreduce_early=None, reduce=Tr
                        .format(rank, skipped))
         if world == 1:
             raise hip.CtcAsrError(failure[-1])
+    if dump and rank == 0:
+        dump_outputs(dump, model, loss)          # (after the clock stopped)
     failed_ranks = 0
     if world > 1:
         flag = torch.tensor([1.0 if failure else 0.0], device=device)
@@ -683,11 +727,12 @@ def c5_bucket_sequence(batch, count, seed=1234, pool=4096, num_buckets=96):
     return out
 
 
-def measure_c5(args, rank, local_rank, world):
+def measure_c5(args, rank, local_rank, world, dump=None):
     """BASELINE.json configs[4] on this rank's GPU: training over a fixed seeded sequence of
     ``args.steps`` bucketed mixed-length batches (one untimed pass to warm the allocator over the
     sequence's shapes, one timed pass), then evaluation-style decoding of the same batches with
-    the beam search at width 64 (logits of all batches decoded in grouped launches)."""
+    the beam search at width 64 (logits of all batches decoded in grouped launches).  ``dump``:
+    directory for `dump_outputs` of the timed pass's last training step (rank 0)."""
     from ctc_asr_amd import hip
     from ctc_asr_amd.engine import Trainer
     from ctc_asr_amd.labels import encode
@@ -753,6 +798,8 @@ def measure_c5(args, rank, local_rank, world):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     trainer.drain_checks()
+    if dump and rank == 0:
+        dump_outputs(dump, model, loss)          # (before the decode passes replace the logits)
     # (the arithmetic of the TRAINING passes: `arithmetic()` reports the last forward pass, and the
     # decode passes below run in eval mode - no backward recurrence in theirs)
     train_arith = model.arithmetic()
@@ -1157,9 +1204,14 @@ def main():
                          'cost; reported under `collective_stand_in`')
     ap.add_argument('--c5-batches', type=int, default=24,
                     help='bucketed batches in the C5 sequence of the default N = 1 run')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step of the headline workload computed as '
+                         'DIR/<name>.npy (bench.dump_outputs; N > 1: rank 0, first release mode)')
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit('--gpus must be >= 1')
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit('--steps must be >= 1 and --warmup >= 0')
 
     if 'WORLD_SIZE' not in os.environ and args.gpus > 1:
         sys.exit(spawn_ranks(args))
@@ -1206,7 +1258,7 @@ def main():
 
     other, exit_code = {}, 0
     if args.workload == 'c5':
-        result = measure_c5(args, rank, local_rank, world)
+        result = measure_c5(args, rank, local_rank, world, dump=args.dump_outputs)
         cfg = frames = batch = seconds = None
         if world == 1:
             try:
@@ -1215,7 +1267,7 @@ def main():
                 other['c5_from_disk'] = {'error': '{}: {}'.format(type(err).__name__, err)}
     elif world == 1:
         result, (cfg, frames, batch, seconds) = measure(args.workload, args, rank, local_rank,
-                                                        world)
+                                                        world, dump=args.dump_outputs)
     else:
         # N > 1: the driver runs this once per N, so the run itself is the experiment - both
         # release modes of the gradient buckets back to back (each: warm-up + K timed steps under
@@ -1234,7 +1286,8 @@ def main():
                 skipped.append(mode)
                 continue
             legs[mode], shape = measure(args.workload, args, rank, local_rank, world,
-                                        allreduce_early=(mode == 'early'))
+                                        allreduce_early=(mode == 'early'),
+                                        dump=None if legs else args.dump_outputs)
         stub, _ = measure(args.workload, args, rank, local_rank, world, reduce=False)
         cfg, frames, batch, seconds = shape
         result = merge_release_modes(legs, stub) if rank == 0 else None

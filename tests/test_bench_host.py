@@ -147,3 +147,22 @@ def test_predicted_input_bounds_and_dtype_label():
     assert 'recurrence' not in bench.dtype_label(model(rnn_fwd_f16=False, rnn_bwd_f16=False))
     assert 'fp16x3' not in bench.dtype_label(model(fwd_f16=False, rnn_fwd_f16=False,
                                                    rnn_bwd_f16=False))
+
+
+def test_dump_sample_of_the_arena_is_fixed_and_covers_it():
+    """--dump-outputs keeps a seeded sample of a large parameter arena: the same entries every
+    run, one from each stratum (every tensor is represented), all of a small arena."""
+    import numpy as np
+    import bench
+    assert (bench.arena_sample_index(1000, limit=4096) == np.arange(1000)).all()
+    first = bench.arena_sample_index(10 ** 7 + 3, limit=1 << 16)
+    assert (first == bench.arena_sample_index(10 ** 7 + 3, limit=1 << 16)).all()
+    assert first.shape == (1 << 16,) and (np.diff(first) > 0).all()
+    assert first[0] >= 0 and first[-1] < 10 ** 7 + 3
+    assert np.diff(first).max() < 2 * (10 ** 7 + 3) // (1 << 16) + 2
+
+
+def test_steps_below_one_are_refused():
+    out = _run(['--gpus', '1', '--steps', '0', '--warmup', '0'])
+    assert out.returncode != 0 and '--steps' in out.stderr
+    assert out.stdout.strip() == ''

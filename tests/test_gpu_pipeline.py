@@ -327,3 +327,41 @@ def test_out_of_range_weights_take_the_bf16_form(monkeypatch):
     pieces = hip.split_f16(x, split_gemm.W_SCALE, split_gemm.H_B)
     assert torch.isfinite(pieces.float()).all()
     assert float(pieces[0, 0, 0]) == 65504.0 and float(pieces[0, 0, 1]) == -65504.0
+
+
+def test_bench_dump_outputs_are_reproducible_and_follow_steps(tmp_path):
+    """bench.py --dump-outputs: the last timed step's loss, logits and (sampled) parameters and
+    gradients as float .npy files; two runs with the same arguments compute the same outputs
+    from the same inputs, and one more timed step (--steps) moves the parameters."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+    def run(steps, name):
+        out = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1',
+                              '--steps', str(steps), '--warmup', '1', '--workload', 'tiny',
+                              '--no-cpu-baseline', '--no-parity-probe',
+                              '--dump-outputs', str(tmp_path / name)],
+                             capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        assert json.loads(out.stdout.strip().splitlines()[-1])['steps'] == steps
+        return {f[:-4]: np.load(str(tmp_path / name / f))
+                for f in os.listdir(str(tmp_path / name))}
+
+    first, again, longer = run(2, 'a'), run(2, 'b'), run(3, 'c')
+    assert set(first) == {'loss', 'per_utterance_loss', 'logits', 'logit_lengths', 'arena_index',
+                          'param', 'grad'}
+    assert all(a.dtype in (np.float32, np.float64) for a in first.values())
+    assert sum(a.nbytes for a in first.values()) <= 64 << 20
+    assert first['logits'].ndim == 3 and first['logits'].shape[1] == 4        # T', B, C
+    assert first['param'].shape == first['grad'].shape == first['arena_index'].shape
+    assert np.isfinite(first['loss']) and \
+        abs(float(first['loss']) - first['per_utterance_loss'].mean()) < 1e-3 * abs(first['loss'])
+    assert (first['arena_index'] == again['arena_index']).all()
+    assert (first['logit_lengths'] == again['logit_lengths']).all()
+    assert abs(float(first['loss']) - float(again['loss'])) < 1e-4 * abs(float(first['loss']))
+    assert np.abs(first['logits'] - again['logits']).max() < 1e-3
+    same = np.median(np.abs(first['param'] - again['param']))
+    moved = np.median(np.abs(first['param'] - longer['param']))
+    assert same < 1e-7 and moved > 1e-6, (same, moved)
