@@ -357,9 +357,10 @@ __global__ void __launch_bounds__(256) dgrad16_pack_kernel(const float *w, int64
 
 // (rnn_persistent.hip) where the fp16 backward recurrence keeps its exchange blocks and inverse
 // scales inside a recurrence workspace
-int prnn_b16_published(void *sync, int T, int B, int H, const char **xchg, const float **scales);
-// (rnn_step.hip) the barrier words of row block 0 of a recurrence workspace
-void *rnn_workspace_sync_block0(void *workspace, int B, int H);
+int prnn_b16_published(const void *exchange, int T, int B, int H, const char **xchg,
+                       const float **scales);
+// (rnn_step.hip) the exchange region of row block 0 of a recurrence workspace
+const void *rnn_workspace_xchg_block0(const void *workspace, int cell, int B, int H);
 
 // this file's share of ctcasr_build_flags() (rnn_persistent.hip)
 unsigned dgrad16_build_flags() {
@@ -392,8 +393,8 @@ extern "C" int ctcasr_dgrad16_published_offsets(int T, int B, int hidden, size_t
     const char *x;
     const float *sc;
     if (T < 1 || B < 1 || hidden < 1 ||
-        prnn_b16_published(rnn_workspace_sync_block0(base, B, hidden), T, B, hidden, &x, &sc) !=
-            CTCASR_OK)
+        prnn_b16_published(rnn_workspace_xchg_block0(base, CTCASR_CELL_LSTM, B, hidden), T, B,
+                           hidden, &x, &sc) != CTCASR_OK)
         return CTCASR_ERR_BAD_ARGUMENT;
     *exchange = (size_t)(x - base);
     *inverse_scales = (size_t)(reinterpret_cast<const char *>(sc) - base);
@@ -424,8 +425,8 @@ extern "C" int ctcasr_dgrad16_blockscaled(void *workspace, int T, int B, int hid
         attr_set = true;
     }
     DgArgs a = {};
-    if (prnn_b16_published(rnn_workspace_sync_block0(workspace, B, hidden), T, B, hidden, &a.xchg,
-                           &a.scales) != CTCASR_OK)
+    if (prnn_b16_published(rnn_workspace_xchg_block0(workspace, CTCASR_CELL_LSTM, B, hidden), T, B,
+                           hidden, &a.xchg, &a.scales) != CTCASR_OK)
         return CTCASR_ERR_BAD_ARGUMENT;
     a.wpk = reinterpret_cast<const char *>(packed);
     a.out = dx; a.ldc = ld_dx;

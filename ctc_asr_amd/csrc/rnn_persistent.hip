@@ -4077,7 +4077,11 @@ int launch_persistent(K kernel, const PArgs &p, size_t lds, hipStream_t s, int c
     // No memsets: the arrival counters are zeroed again by the launch that used them
     // (counters_done), the all-zero block of the exchange buffer is never written, and the
     // time-out word is sticky (ctcasr_rnn_poll_error reads and clears it).  All three rely on the
-    // workspace having been zero-filled ONCE before its first use with this (B, H).
+    // workspace having been zero-filled ONCE before its first use with this (B, H), and on the
+    // words that last from launch to launch (barrier words, K-pair hand-off words) sitting at
+    // offsets that do not move with T: the workspace's control header (rnn_step.hip).  The
+    // all-zero block of row blocks >= 1 does move with T; the library clears it at the start of
+    // each pass (ctcasr_rnn_fwd_steps / _bwd_steps).
     TimedLaunch timed = {};
     const bool record = g_kernel_events && g_timed.size() < 65536 &&
                         hipEventCreate(&timed.start) == hipSuccess &&
@@ -4159,26 +4163,27 @@ static size_t prnn_step_exchange_bytes(int T, int B, int H, int G) {
     return ctcasr_align_up((size_t)(T + 1) * 2 * B * G * H * sizeof(float), 256);
 }
 // the per-step blocks, then (LSTM, H = 1024) the ring of the reduce-scatter backward kernel
-// ... and the inverse scales of the fp16 backward kernel
+// ... and the inverse scales of the fp16 backward kernel.  Everything here is written by a pass
+// before that pass reads it - except the all-zero block in front of the steps (rnn_step.hip) - so
+// it may sit at offsets that move with T; the K-pair hand-off words, which last from launch to
+// launch, are not part of it (prnn_kp_region_bytes).
 size_t prnn_exchange_bytes(int T, int B, int H, int G) {
     return prnn_step_exchange_bytes(T, B, H, G) +
            (G == 4 && H == PRNN_RS_H
-                ? prnn_rs_ring_bytes() + ctcasr_align_up(prnn_b16_scale_bytes(T), 256) + prnn_kp_bytes()
-                : 0) +
-           (G == 4 && H == PRNN_W16_H
-                ? ctcasr_align_up(prnn_w16_scale_bytes(T), 256) + prnn_w16_kp_bytes() : 0) +
+                ? prnn_rs_ring_bytes() + ctcasr_align_up(prnn_b16_scale_bytes(T), 256) : 0) +
+           (G == 4 && H == PRNN_W16_H ? ctcasr_align_up(prnn_w16_scale_bytes(T), 256) : 0) +
            (G == 1 && H == PRNN_R16_H ? prnn_r16_scale_bytes(T) : 0);
 }
 
 int prnn_fwd(int cell, const float *xw, const float *xw_bias, const float *w_hh,
              const float *b_hh_n, const int32_t *seq_len, int T, int B, int BS, int H, float *y,
-             void *y16, float *gates, float *cells, void *sync, float *carry, int step_begin,
-             int step_end, int flags, hipStream_t s) {
+             void *y16, float *gates, float *cells, void *sync, void *xchg, float *carry,
+             int step_begin, int step_end, int flags, hipStream_t s) {
     // forward default: the whole chip (nothing of the same layer can overlap it)
     const bool fwd_half_chip = (flags & CTCASR_RNN_HALF_CHIP) != 0;
     PArgs p = {};
     p.carry = carry;
-    p.xchg = reinterpret_cast<float *>(reinterpret_cast<char *>(sync) + sizeof(SyncWords));
+    p.xchg = reinterpret_cast<float *>(xchg);
     p.xw = xw; p.w = w_hh; p.seq_len = seq_len; p.y = y; p.gates = gates; p.cells = cells;
     p.y16 = reinterpret_cast<unsigned short *>(y16);
     p.bias = xw_bias; p.b_hh = b_hh_n;
@@ -4298,11 +4303,12 @@ int prnn_fwd(int cell, const float *xw, const float *xw_bias, const float *w_hh,
 int prnn_bwd(int cell, const float *dy, const float *y, const float *w_hh_t,
              const int32_t *seq_len, int T, int B, int BS, int H, const float *gates,
              const float *cells, float *dxw, float *drec, float *dbias, unsigned *colmax,
-             void *sync, float *carry, int step_begin, int step_end, int flags, hipStream_t s) {
+             void *sync, void *kp, void *xchg, float *carry, int step_begin, int step_end,
+             int flags, hipStream_t s) {
     PArgs p = {};
     p.dbias = dbias;
     p.s_lo = step_begin; p.s_hi = step_end; p.carry = carry;
-    p.xchg = reinterpret_cast<float *>(reinterpret_cast<char *>(sync) + sizeof(SyncWords));
+    p.xchg = reinterpret_cast<float *>(xchg);
     p.w = w_hh_t; p.seq_len = seq_len; p.y = const_cast<float *>(y); p.dy = dy; p.dxw = dxw;
     p.drec = drec;
     p.gates = const_cast<float *>(gates); p.cells = const_cast<float *>(cells);
@@ -4377,8 +4383,7 @@ int prnn_bwd(int cell, const float *dy, const float *y, const float *w_hh_t,
         const size_t lds = (size_t)4 * 64 * 32 * 16 + (size_t)4 * 16 * 17 * 4 +
                            (size_t)4 * 256 * 16 + 64;
         const bool pairs = (flags & CTCASR_RNN_KPAIR) != 0;
-        p.kp = reinterpret_cast<unsigned *>(reinterpret_cast<char *>(p.rs) +
-                                            ctcasr_align_up(prnn_w16_scale_bytes(T), 256));
+        p.kp = reinterpret_cast<unsigned *>(kp);
         for (int tile = 0; tile < mt; ++tile)
             for (int dir = 0; dir < 2; ++dir) {
                 p.chain0 = tile; p.dir0 = dir;
@@ -4430,8 +4435,7 @@ int prnn_bwd(int cell, const float *dy, const float *y, const float *w_hh_t,
         if (mt == 2 && half_chip && (flags & CTCASR_RNN_KPAIR) && !seq_len && tiles_apart) {
             // K-pair form of the staggered kernel: weights 128 KB, partial tiles [2 tiles][2 n],
             // inverse scales [2 tiles][4 waves][32] float4
-            p.kp = reinterpret_cast<unsigned *>(reinterpret_cast<char *>(p.rs) +
-                                                ctcasr_align_up(prnn_b16_scale_bytes(T), 256));
+            p.kp = reinterpret_cast<unsigned *>(kp);
             const size_t kp_lds = (size_t)128 * 1024 + (size_t)4 * 4 * 16 * 17 * 4 +
                                   (size_t)2 * 4 * 32 * 16 + 64;
             if (p.prof)
@@ -4509,11 +4513,13 @@ int prnn_bwd(int cell, const float *dy, const float *y, const float *w_hh_t,
 // Where prnn_bwd16_kernel keeps what it publishes, for the block-scaled data-gradient kernel that
 // reads it after the pass (csrc/dgrad16.hip): the exchange blocks (the all-zero block first, then
 // one per step) and the inverse scales, of a pass over T steps of B <= 32 rows.
-// (``sync``: the barrier words of the pass's row block, rnn_step.hip: rnn_workspace_sync_block0)
-int prnn_b16_published(void *sync, int T, int B, int H, const char **xchg, const float **scales) {
-    if (!sync || H != PRNN_RS_H || B < 1 || B > PRNN_BLOCK_ROWS || T < 1)
+// (``exchange``: the exchange region of the pass's row block, rnn_step.hip:
+// rnn_workspace_xchg_block0)
+int prnn_b16_published(const void *exchange, int T, int B, int H, const char **xchg,
+                       const float **scales) {
+    if (!exchange || H != PRNN_RS_H || B < 1 || B > PRNN_BLOCK_ROWS || T < 1)
         return CTCASR_ERR_BAD_ARGUMENT;
-    const char *x = reinterpret_cast<const char *>(sync) + sizeof(SyncWords);
+    const char *x = reinterpret_cast<const char *>(exchange);
     *xchg = x;
     *scales = reinterpret_cast<const float *>(x + prnn_step_exchange_bytes(T, B, H, 4) +
                                               prnn_rs_ring_bytes());
@@ -4522,21 +4528,15 @@ int prnn_b16_published(void *sync, int T, int B, int H, const char **xchg, const
 
 size_t prnn_error_offset() { return offsetof(SyncWords, error); }
 
-// The K-pair hand-off words of a block's region (byte offset from its barrier words, size): after
-// a time-out their write counts are undefined - ctcasr_rnn_poll_error zero-fills them with the
-// barrier words.  0 bytes for shapes without them.
-void prnn_kp_region(int T, int B, int H, int G, size_t *offset, size_t *bytes) {
-    *offset = *bytes = 0;
-    if (G == 4 && H == PRNN_W16_H) {
-        *offset = sizeof(SyncWords) + prnn_step_exchange_bytes(T, B, H, 4) +
-                  ctcasr_align_up(prnn_w16_scale_bytes(T), 256);
-        *bytes = prnn_w16_kp_bytes();
-        return;
-    }
-    if (G != 4 || H != PRNN_RS_H) return;
-    *offset = sizeof(SyncWords) + prnn_step_exchange_bytes(T, B, H, 4) +
-              prnn_rs_ring_bytes() + ctcasr_align_up(prnn_b16_scale_bytes(T), 256);
-    *bytes = prnn_kp_bytes();
+// Bytes of a row block's K-pair hand-off words (KPairWords + the tagged slots; 0 for shapes
+// without them).  `total` must last from launch to launch - its parity is the tag base - so they
+// sit in the workspace's control header, at an offset that does not move with T (rnn_step.hip);
+// after a time-out their write counts are undefined and ctcasr_rnn_poll_error zero-fills them
+// with the barrier words.
+size_t prnn_kp_region_bytes(int H, int G) {
+    if (G == 4 && H == PRNN_W16_H) return prnn_w16_kp_bytes();
+    if (G == 4 && H == PRNN_RS_H) return prnn_kp_bytes();
+    return 0;
 }
 
 int prnn_resident_gate(void *sync, unsigned ticket, int max_wait_us, hipStream_t s) {

@@ -282,17 +282,18 @@ int cell_gates(int cell) {
 extern "C" int ctcasr_rnn_persistent_supported(int cell, int T, int B, int H);
 size_t prnn_sync_bytes();
 size_t prnn_error_offset();
-void prnn_kp_region(int T, int B, int H, int G, size_t *offset, size_t *bytes);
+size_t prnn_kp_region_bytes(int H, int G);
 int prnn_resident_gate(void *sync, unsigned ticket, int max_wait_us, hipStream_t s);
 size_t prnn_exchange_bytes(int T, int B, int H, int G);
 int prnn_fwd(int cell, const float *xw, const float *xw_bias, const float *w_hh,
              const float *b_hh_n, const int32_t *seq_len, int T, int B, int BS, int H, float *y,
-             void *y16, float *gates, float *cells, void *sync, float *carry, int step_begin,
-             int step_end, int flags, hipStream_t s);
+             void *y16, float *gates, float *cells, void *sync, void *xchg, float *carry,
+             int step_begin, int step_end, int flags, hipStream_t s);
 int prnn_bwd(int cell, const float *dy, const float *y, const float *w_hh_t,
              const int32_t *seq_len, int T, int B, int BS, int H, const float *gates,
              const float *cells, float *dxw, float *drec, float *dbias, unsigned *colmax,
-             void *sync, float *carry, int step_begin, int step_end, int flags, hipStream_t s);
+             void *sync, void *kp, void *xchg, float *carry, int step_begin, int step_end,
+             int flags, hipStream_t s);
 
 // The persistent kernels cover at most 32 rows (two 16-row tiles) per launch: a bigger batch
 // (33..64) runs as consecutive launches over blocks of rows, each block with its own barrier
@@ -304,20 +305,61 @@ static int prnn_block_rows(int B, int block) {
     const int left = B - block * PRNN_BLOCK_ROWS;
     return left < PRNN_BLOCK_ROWS ? left : PRNN_BLOCK_ROWS;
 }
-// bytes of one block's region: barrier words, then its exchange buffer
-static size_t prnn_block_bytes(int T, int B, int H, int G) {
-    const int rows = B < PRNN_BLOCK_ROWS ? B : PRNN_BLOCK_ROWS;
-    return ctcasr_align_up(prnn_sync_bytes(), 256) + prnn_exchange_bytes(T, rows, H, G);
-}
 
 static size_t rnn_state_bytes(int B, int H) {
     return ctcasr_align_up((size_t)6 * B * H * sizeof(float), 256);
 }
 
-// (dgrad16.hip) the barrier words of row block 0 inside a recurrence workspace: the exchange
-// buffer of a pass over B <= 32 rows follows them
-void *rnn_workspace_sync_block0(void *workspace, int B, int H) {
-    return reinterpret_cast<char *>(workspace) + rnn_state_bytes(B, H);
+// Layout of a workspace of the persistent kernels:
+//   [state ping-pong + carry]                                   rnn_state_bytes(B, H)
+//   [control header: per row block, its barrier words (SyncWords: arrival counters, the sticky
+//    time-out word, the residency words), then its K-pair hand-off words]
+//                                                               prnn_blocks(B) * prnn_ctl_bytes
+//   [exchange regions: per row block, the all-zero block, the per-step blocks, the reduce-scatter
+//    ring, the inverse scales]                                  prnn_blocks(B) * prnn_exchange_bytes
+// What must last from launch to launch, or be zero at a launch, sits in the header at offsets
+// that depend on (cell, B, H) only - one workspace serves every T up to the one it was sized for.
+// The exchange regions follow and move with T: a pass writes them before it reads them, except
+// the all-zero block at the head of each region.  Block 0's zero block is at a fixed place; that
+// of a block >= 1 lands on what an earlier, longer pass left there, so the library clears it at
+// the start of each pass (prnn_clear_zero_block).
+static size_t prnn_ctl_bytes(int H, int G) {
+    return ctcasr_align_up(prnn_sync_bytes(), 256) +
+           ctcasr_align_up(prnn_kp_region_bytes(H, G), 256);
+}
+// bytes of one block's exchange region (every block is sized for 32 rows once B > 32)
+static size_t prnn_block_xchg_bytes(int T, int B, int H, int G) {
+    const int rows = B < PRNN_BLOCK_ROWS ? B : PRNN_BLOCK_ROWS;
+    return prnn_exchange_bytes(T, rows, H, G);
+}
+struct PrnnBlock {
+    char *sync;     // SyncWords
+    char *kp;       // K-pair hand-off words (prnn_kp_region_bytes)
+    char *xchg;     // exchange region
+};
+static PrnnBlock prnn_block(void *workspace, int T, int B, int H, int G, int block) {
+    char *ctl = reinterpret_cast<char *>(workspace) + rnn_state_bytes(B, H);
+    PrnnBlock r;
+    r.sync = ctl + (size_t)block * prnn_ctl_bytes(H, G);
+    r.kp = r.sync + ctcasr_align_up(prnn_sync_bytes(), 256);
+    r.xchg = ctl + (size_t)prnn_blocks(B) * prnn_ctl_bytes(H, G) +
+             (size_t)block * prnn_block_xchg_bytes(T, B, H, G);
+    return r;
+}
+// The all-zero block in front of a row block's steps (2 x rows x G x H floats, the largest any
+// kernel reads): block 0's never moves; a block >= 1 starts a pass with it cleared.
+static int prnn_clear_zero_block(const PrnnBlock &b, int block, int rows, int H, int G,
+                                 hipStream_t s) {
+    if (block == 0) return CTCASR_OK;
+    return hipMemsetAsync(b.xchg, 0, (size_t)2 * rows * G * H * sizeof(float), s) == hipSuccess
+               ? CTCASR_OK : CTCASR_ERR_LAUNCH;
+}
+
+// (dgrad16.hip) the exchange region of row block 0 inside a recurrence workspace (the pass over
+// B <= 32 rows publishes there)
+const void *rnn_workspace_xchg_block0(const void *workspace, int cell, int B, int H) {
+    // (block 0's region starts right behind the header: any T gives the same address)
+    return prnn_block(const_cast<void *>(workspace), 1, B, H, cell_gates(cell), 0).xchg;
 }
 
 extern "C" size_t ctcasr_rnn_reserve_bytes(int cell, int T, int B, int H) {
@@ -331,10 +373,12 @@ extern "C" size_t ctcasr_rnn_reserve_bytes(int cell, int T, int B, int H) {
 extern "C" size_t ctcasr_rnn_workspace_bytes(int cell, int T, int B, int H) {
     if (T <= 0 || B <= 0 || H <= 0 || cell_gates(cell) == 0) return 0;
     // state ping-pong [2,2,B,H] + cell / dc carry [2,B,H]
-    // persistent variant: + the per-step exchange buffer (h forward, dgates backward)
+    // persistent variant: + the control header and the exchange regions (h forward, dgates
+    // backward; see prnn_block)
+    const int G = cell_gates(cell);
     return rnn_state_bytes(B, H) +
            (ctcasr_rnn_persistent_supported(cell, T, B, H)
-                ? prnn_blocks(B) * prnn_block_bytes(T, B, H, cell_gates(cell))
+                ? prnn_blocks(B) * (prnn_ctl_bytes(H, G) + prnn_block_xchg_bytes(T, B, H, G))
                 : ctcasr_align_up(prnn_sync_bytes(), 256));
 }
 
@@ -395,14 +439,16 @@ extern "C" int ctcasr_rnn_fwd_steps(int cell, const float *xw, const float *xw_b
         const int G = cell_gates(cell);
         for (int blk = 0; blk < prnn_blocks(B); ++blk) {
             const size_t b0 = (size_t)blk * PRNN_BLOCK_ROWS;
+            const PrnnBlock wb = prnn_block(workspace, T, B, H, G, blk);
+            if (step_begin == 0 &&
+                (rc = prnn_clear_zero_block(wb, blk, prnn_block_rows(B, blk), H, G, s)) != CTCASR_OK)
+                return rc;
             rc = prnn_fwd(cell, xw + b0 * 2 * G * H, xw_bias, w_hh, b_hh_n,
                           seq_len ? seq_len + b0 : nullptr, T, prnn_block_rows(B, blk), B, H,
                           y + b0 * 2 * H,
                           y_pieces ? reinterpret_cast<char *>(y_pieces) + b0 * 3 * 2 * H * 2
                                    : nullptr,
-                          p.gates + b0 * 2 * 4 * H, p.cells + b0 * 2 * H,
-                          reinterpret_cast<char *>(workspace) + rnn_state_bytes(B, H) +
-                              blk * prnn_block_bytes(T, B, H, G),
+                          p.gates + b0 * 2 * 4 * H, p.cells + b0 * 2 * H, wb.sync, wb.xchg,
                           p.cbuf + b0 * 2 * H, step_begin, step_end, flags, s);
             if (rc != CTCASR_OK) return rc;
         }
@@ -499,12 +545,14 @@ extern "C" int ctcasr_rnn_bwd_steps(int cell, const float *dy, const float *y,
     if (ctcasr_rnn_persistent_supported(cell, T, B, H)) {
         for (int blk = 0; blk < prnn_blocks(B); ++blk) {
             const size_t b0 = (size_t)blk * PRNN_BLOCK_ROWS;
+            const PrnnBlock wb = prnn_block(workspace, T, B, H, G, blk);
+            if (step_end == T &&
+                (rc = prnn_clear_zero_block(wb, blk, prnn_block_rows(B, blk), H, G, s)) != CTCASR_OK)
+                return rc;
             rc = prnn_bwd(cell, dy + b0 * 2 * H, y + b0 * 2 * H, w_hh_t,
                           seq_len ? seq_len + b0 : nullptr, T, prnn_block_rows(B, blk), B, H,
                           p.gates + b0 * 2 * 4 * H, p.cells + b0 * 2 * H, dxw + b0 * 2 * G * H,
-                          p.drec + b0 * 2 * G * H, dbias, colmax,
-                          reinterpret_cast<char *>(workspace) + rnn_state_bytes(B, H) +
-                              blk * prnn_block_bytes(T, B, H, G),
+                          p.drec + b0 * 2 * G * H, dbias, colmax, wb.sync, wb.kp, wb.xchg,
                           p.cbuf + b0 * 2 * H, step_begin, step_end, flags, s);
             if (rc != CTCASR_OK) return rc;
         }
@@ -548,7 +596,8 @@ extern "C" size_t ctcasr_rnn_timeout_word_offset(int cell, int T, int B, int H, 
     if (rnn_check(cell, T, B, H) != CTCASR_OK || !ctcasr_rnn_persistent_supported(cell, T, B, H) ||
         block < 0 || block >= prnn_blocks(B))
         return (size_t)-1;
-    return rnn_state_bytes(B, H) + (size_t)block * prnn_block_bytes(T, B, H, cell_gates(cell)) +
+    // (the control header does not move with T: every T of one workspace reads the same word)
+    return rnn_state_bytes(B, H) + (size_t)block * prnn_ctl_bytes(H, cell_gates(cell)) +
            prnn_error_offset();
 }
 
@@ -564,18 +613,18 @@ extern "C" int ctcasr_rnn_poll_error(void *workspace, size_t workspace_bytes, in
     bool timed_out = false;
     for (int blk = 0; blk < prnn_blocks(B); ++blk) {
         unsigned err = 0;
-        char *sync = reinterpret_cast<char *>(workspace) + rnn_state_bytes(B, H) +
-                     blk * prnn_block_bytes(T, B, H, cell_gates(cell));
-        if (hipMemcpy(&err, sync + prnn_error_offset(), sizeof(err), hipMemcpyDeviceToHost) !=
+        // (the header: the same words whatever T the caller passes, up to the workspace's own)
+        const PrnnBlock wb = prnn_block(workspace, T, B, H, cell_gates(cell), blk);
+        if (hipMemcpy(&err, wb.sync + prnn_error_offset(), sizeof(err), hipMemcpyDeviceToHost) !=
             hipSuccess)
             return CTCASR_ERR_LAUNCH;
         // after a time-out the arrival counters are in an undefined state: start over with
         // clean barrier words (this also clears the time-out word)
-        if (err && hipMemset(sync, 0, prnn_sync_bytes()) != hipSuccess) return CTCASR_ERR_LAUNCH;
-        // ... and so are the write counts of the K-pair hand-off slots (prnn_bwd16k_kernel)
-        size_t kp_off = 0, kp_bytes = 0;
-        prnn_kp_region(T, prnn_block_rows(B, blk), H, cell_gates(cell), &kp_off, &kp_bytes);
-        if (err && kp_bytes && hipMemset(sync + kp_off, 0, kp_bytes) != hipSuccess)
+        if (err && hipMemset(wb.sync, 0, prnn_sync_bytes()) != hipSuccess) return CTCASR_ERR_LAUNCH;
+        // ... and so are the write counts of the K-pair hand-off slots (prnn_bwd16k_kernel,
+        // prnn_bwd16w_kernel)
+        const size_t kp_bytes = prnn_kp_region_bytes(H, cell_gates(cell));
+        if (err && kp_bytes && hipMemset(wb.kp, 0, kp_bytes) != hipSuccess)
             return CTCASR_ERR_LAUNCH;
         timed_out = timed_out || err != 0;
     }
@@ -596,7 +645,7 @@ extern "C" int ctcasr_rnn_resident_gate(void *workspace, size_t workspace_bytes,
     // (B = 33 .. 64: a pass runs as one launch per block of <= 32 rows, all carrying the ticket;
     // the gate watches the FIRST block's words - work behind it overlaps every block, and may take
     // CUs the later blocks need at their start: a late start, never a wrong result)
-    return prnn_resident_gate(reinterpret_cast<char *>(workspace) + rnn_state_bytes(B, H), ticket,
+    return prnn_resident_gate(prnn_block(workspace, T, B, H, cell_gates(cell), 0).sync, ticket,
                               max_wait_us, (hipStream_t)stream);
 }
 

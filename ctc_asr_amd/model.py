@@ -1006,7 +1006,10 @@ class CTCModel:
         """The recurrence workspace shared by every layer and pass of this model: zero-filled
         when created (the persistent kernels' time-out word is sticky - a launch never clears
         it, `check_rnn_error` reads and clears it), kept across steps and re-created only when
-        the batch changes or a longer sequence needs a bigger exchange buffer."""
+        the batch changes or a longer sequence needs a bigger exchange buffer.  Every T' up to
+        the one it was created for runs on it: the words that last from launch to launch
+        (barrier words, time-out words, K-pair hand-off words) sit in a header at offsets that
+        depend on (cell, batch, hidden) only; the exchange buffers behind it move with T'."""
         need = hip.rnn_workspace_bytes(cell, t_out, batch, hidden)
         key = (cell, batch, hidden)
         have = self._rnn_ws.get(key)
@@ -1020,7 +1023,9 @@ class CTCModel:
     def check_rnn_error(self):
         """Raise `hip.CtcAsrError` (CTCASR_ERR_TIMEOUT) if a persistent recurrence kernel of
         any layer, pass or step since the last check gave up at a grid barrier: its output -
-        and every gradient computed from it - is invalid.  Synchronises the stream."""
+        and every gradient computed from it - is invalid.  Synchronises the stream.  (Polls with
+        the T' each workspace was created with: the time-out words do not move with T', so this
+        reads the words `step_guard` reads at the current T'.)"""
         for (cell, batch, hidden), (workspace, t_out) in self._rnn_ws.items():
             hip.rnn_poll_error(cell, workspace, t_out, batch, hidden)
         # ... or a part of a weight-gradient tile stopped waiting for its turn (its sum was not

@@ -132,7 +132,10 @@ int ctcasr_ctc_beam_decode(const float *logits, const int32_t *seq_len, int T, i
  *            buffer).  ZERO-FILL IT ONCE before its first use with a given (B, H): the launches
  *            themselves issue no memset - the arrival counters are reset by the kernel that used
  *            them, the all-zero block of the exchange buffer is never written, and the time-out
- *            word is sticky until ctcasr_rnn_poll_error reads it.
+ *            word is sticky until ctcasr_rnn_poll_error reads it.  A workspace sized for T serves
+ *            every T' <= T: the words that last from launch to launch sit at offsets that do not
+ *            depend on T (B = 33 .. 64: the all-zero block of the second row block does move, and
+ *            the first launch of a pass clears it).
  * bwd: dy [T,B,2H] -> dxw [T,B,2,G*H] (gradient w.r.t. xw, which is also what the weight
  * gradients are GEMMs of), w_hh_t = w_hh transposed to [2, H, G*H] (caller keeps it current;
  * ctcasr_transpose_batched does it).  GRU: the recurrent path differs from dxw in the candidate

@@ -269,6 +269,8 @@ def _recurrence_float64(cell, xw, w_hh, b_hh, seq_len):
             rec = h @ w64[d].t()
             if cell == 'rnn_relu':
                 h_new = torch.relu(x + rec)
+            elif cell == 'rnn_tanh':
+                h_new = torch.tanh(x + rec)
             elif cell == 'lstm':
                 i, f, g, o = (x + rec).split(hidden, dim=1)
                 c_new = torch.sigmoid(f) * c + torch.sigmoid(i) * torch.tanh(g)
@@ -763,6 +765,262 @@ def test_staggered_launch_leaves_at_once_when_the_time_out_word_is_set(hip):
     again = hip.rnn_bwd('lstm', dy, y, w_hh_t, reserve, workspace=ws, flags=flags)
     hip.rnn_poll_error('lstm', ws, num_steps, batch, hidden)
     assert torch.equal(again, want)
+
+
+# (cell, hidden) of every persistent kernel family, the batches of one and two row blocks, the
+# sequence lengths one workspace sized for T_MAX serves (the model's `_rnn_workspace`)
+_PERSISTENT = [('lstm', 1024), ('gru', 1024), ('lstm', 2048), ('gru', 2048), ('rnn_relu', 2048),
+               ('rnn_tanh', 2048)]
+_T_MAX = 24
+
+
+@pytest.mark.parametrize('cell,hidden', _PERSISTENT)
+def test_control_words_do_not_move_with_the_sequence_length(hip, cell, hidden):
+    """One workspace serves every T up to the one it was created for, so the words that last from
+    launch to launch - barrier words, the sticky time-out word - must sit where every T finds them.
+    `check_rnn_error` polls with the T of the workspace's creation, `step_guard` reads the words at
+    the current T: both must name the same addresses, for each row block.  Block 0's exchange
+    region (its all-zero block; what the data-gradient kernel reads) does not move either.  No
+    kernel is launched."""
+    for batch in (9, 16, 32, 40, 64):
+        assert hip.rnn_persistent_supported(cell, _T_MAX, batch, hidden), batch
+        ws = hip.rnn_workspace(cell, _T_MAX, batch, hidden, DEV)
+        want = hip.rnn_timeout_words(cell, ws, _T_MAX, batch, hidden)
+        assert want[0] != 0 and (want[1] != 0) == (batch > 32), (batch, want)
+        for num_steps in (1, 2, 9, 17, _T_MAX - 1, _T_MAX):
+            assert hip.rnn_workspace_bytes(cell, num_steps, batch, hidden) <= ws.numel()
+            got = hip.rnn_timeout_words(cell, ws, num_steps, batch, hidden)
+            assert got == want, (batch, num_steps, [g - ws.data_ptr() for g in got],
+                                 [w - ws.data_ptr() for w in want])
+        if cell == 'lstm' and hidden == 1024 and batch <= 32:
+            x0 = hip.dgrad16_published_offsets(_T_MAX, batch, hidden)[0]
+            for num_steps in (1, 2, 9, 17, _T_MAX - 1):
+                assert hip.dgrad16_published_offsets(num_steps, batch, hidden)[0] == x0
+
+
+def _changing_t_variants(h, cell, hidden):
+    """(name, forward flags, backward flags, per-row lengths allowed) of every persistent
+    variant of (cell, hidden)."""
+    f16 = h.RNN_F16 | h.RNN_XCD_SPLIT
+    if (cell, hidden) == ('lstm', 1024):
+        return [('fp32', 0, 0, True), ('whole chip', 0, h.RNN_WHOLE_CHIP, True),
+                ('one barrier', h.RNN_ONE_BARRIER, h.RNN_ONE_BARRIER, True),
+                ('reduce-scatter', 0, h.RNN_REDUCE_SCATTER, True), ('f16', f16, f16, True),
+                ('f16 stagger', f16, f16 | h.RNN_STAGGER, True),
+                ('f16 k-pair', f16, f16 | h.RNN_KPAIR, True),
+                ('f16 half-chip forward', h.RNN_F16 | h.RNN_HALF_CHIP, h.RNN_F16, True)]
+    if (cell, hidden) == ('lstm', 2048):
+        return [('f16', h.RNN_F16, h.RNN_F16, True),
+                ('f16 k-pair', h.RNN_F16, h.RNN_F16 | h.RNN_KPAIR, True), ('fp32', 0, 0, True)]
+    if cell == 'gru':
+        return [('fp32', 0, 0, True), ('f16 forward', h.RNN_F16, 0, True)]
+    if cell == 'rnn_relu':
+        return [('fp32', 0, 0, True), ('f16', h.RNN_F16, h.RNN_F16, False)]
+    return [('fp32', 0, 0, True)]
+
+
+def _variant_applies(hip, cell, hidden, batch, fwd_flags, bwd_flags):
+    """Whether this batch runs the kernels the variant names (else the dispatch would quietly
+    take another one)."""
+    if not hip.rnn_persistent_supported(cell, _T_MAX, batch, hidden):
+        return False
+    if cell in ('lstm', 'gru') and fwd_flags & hip.RNN_F16 and \
+            not hip.rnn_fwd_f16_supported(cell, _T_MAX, batch, hidden, fwd_flags):
+        return False
+    if bwd_flags & hip.RNN_F16 and not hip.rnn_bwd_f16_supported(cell, _T_MAX, batch, hidden,
+                                                                  bwd_flags):
+        return False
+    if bwd_flags & (hip.RNN_KPAIR | hip.RNN_STAGGER) and batch % 8:
+        return False        # (prnn_bwd keeps those to multiples of 8 rows)
+    return True
+
+
+class _Pass:
+    """One forward + backward pass of a recurrence over new data (``seed``) at ``num_steps``."""
+
+    def __init__(self, hip, cell, hidden, batch, num_steps, seed, w, wt, b_hh, lengths):
+        self.hip, self.cell, self.hidden, self.batch = hip, cell, hidden, batch
+        self.num_steps, self.w, self.wt, self.b_hh = num_steps, w, wt, b_hh
+        gh = hip.CELL_GATES[cell] * hidden
+        g = torch.Generator(device=DEV).manual_seed(seed)
+        self.xw = torch.randn(num_steps, batch, 2, gh, device=DEV, generator=g) * 0.5
+        self.dy = torch.randn(num_steps, batch, 2 * hidden, device=DEV, generator=g)
+        self.sl = None
+        if lengths:
+            self.sl = torch.randint(1, num_steps + 1, (batch,), device=DEV, generator=g).int()
+            self.sl[0] = num_steps
+
+    def run(self, ws, fwd_flags, bwd_flags, fwd_cuts=None, bwd_cuts=None):
+        """-> y, dxw, dbias, colmax (None where the variant fills none)."""
+        hip, cell, n = self.hip, self.cell, self.num_steps
+        gh = hip.CELL_GATES[cell] * self.hidden
+        y = torch.full((n, self.batch, 2 * self.hidden), float('nan'), device=DEV)
+        reserve = torch.zeros(hip.rnn_reserve_bytes(cell, n, self.batch, self.hidden),
+                              dtype=torch.uint8, device=DEV)
+        fwd_cuts = fwd_cuts or [0, n]
+        for lo, hi in zip(fwd_cuts[:-1], fwd_cuts[1:]):
+            hip.rnn_fwd(cell, self.xw, self.w, self.sl, b_hh_n=self.b_hh, y=y, reserve=reserve,
+                        workspace=ws, steps=(lo, hi), flags=fwd_flags)
+        colmax = None
+        if hip.rnn_bwd_f16_supported(cell, n, self.batch, self.hidden, bwd_flags) and \
+                not (cell == 'rnn_relu' and self.sl is not None):
+            colmax = torch.zeros(2 * gh, dtype=torch.int32, device=DEV)
+        dbias = torch.zeros(2 * gh * (2 if cell == 'gru' else 1), device=DEV)
+        dxw = torch.full((n, self.batch, 2, gh), float('nan'), device=DEV)
+        bwd_cuts = bwd_cuts or [n, 0]
+        for hi, lo in zip(bwd_cuts[:-1], bwd_cuts[1:]):
+            hip.rnn_bwd(cell, self.dy, y, self.wt, reserve, self.sl, b_hh_n=self.b_hh, dxw=dxw,
+                        dbias=dbias, workspace=ws, steps=(lo, hi), flags=bwd_flags, colmax=colmax)
+        self.reserve = reserve
+        return y, dxw, dbias, colmax
+
+
+def _assert_same_pass(got, want, what):
+    """y, dxw and the column maxima bit for bit; the bias gradients to rounding (their atomics
+    have no fixed order: include/ctcasr.h)."""
+    for name, a, b in zip(('y', 'dxw'), got[:2], want[:2]):
+        assert torch.equal(a, b), (what, name, int((a != b).sum()))
+    assert float((got[2] - want[2]).abs().max()) <= 1e-6 * max(1.0, float(want[2].abs().max())), \
+        (what, 'dbias')
+    assert (got[3] is None) == (want[3] is None), what
+    if got[3] is not None:
+        assert torch.equal(got[3], want[3]), (what, 'colmax')
+
+
+@pytest.mark.parametrize('cell,hidden', _PERSISTENT)
+def test_one_workspace_serves_every_shorter_pass(hip, cell, hidden):
+    """The model keeps one recurrence workspace per (cell, batch, hidden) and runs every T' up to
+    the longest seen on it (bucketed training changes T' almost every batch).  Per variant and
+    batch: passes at T = 24, 17, 24, 9, 13, 24 on ONE workspace created for 24 - new data each
+    pass, an odd T after an even one (the K-pair kernels' tag parity flips), the 17-step pass cut
+    into three launches each way, the 13-step pass with per-row lengths - each equal to the same
+    pass on a fresh workspace of exactly its T.  A barrier word, time-out word, K-pair hand-off word
+    or all-zero block that moved with T would sit on what the longer pass left there.  After each
+    pass the time-out words read clear at the workspace's T and at the pass's own.  The last pass
+    of each variant, at its largest batch, against the float64 recurrence / autograd."""
+    gates = hip.CELL_GATES[cell]
+    g = torch.Generator(device=DEV).manual_seed(61)
+    w = torch.randn(2, gates * hidden, hidden, device=DEV, generator=g) / np.sqrt(hidden)
+    wt = hip.transpose_batched(w)
+    b_hh = torch.randn(2, gates * hidden, device=DEV, generator=g) * 0.3 if cell == 'gru' else None
+    lengths_at, cut_at = 4, 1
+    ran = set()
+    for name, fwd_flags, bwd_flags, lengths_ok in _changing_t_variants(hip, cell, hidden):
+        last = None
+        for batch in (9, 16, 24, 32, 40, 64):
+            if not _variant_applies(hip, cell, hidden, batch, fwd_flags, bwd_flags):
+                continue
+            ran.add((name, batch))
+            ws = hip.rnn_workspace(cell, _T_MAX, batch, hidden, DEV)
+            for k, num_steps in enumerate((24, 17, 24, 9, 13, 24)):
+                what = (name, batch, num_steps)
+                p = _Pass(hip, cell, hidden, batch, num_steps, 1000 * k + batch, w, wt, b_hh,
+                          lengths_ok and k == lengths_at)
+                cuts = {}
+                if k == cut_at:
+                    cuts = dict(fwd_cuts=[0, 1, 8, num_steps], bwd_cuts=[num_steps, 16, 9, 0])
+                got = p.run(ws, fwd_flags, bwd_flags, **cuts)
+                hip.rnn_poll_error(cell, ws, _T_MAX, batch, hidden)
+                hip.rnn_poll_error(cell, ws, num_steps, batch, hidden)
+                fresh = hip.rnn_workspace(cell, num_steps, batch, hidden, DEV)
+                want = p.run(fresh, fwd_flags, bwd_flags)
+                hip.rnn_poll_error(cell, fresh, num_steps, batch, hidden)
+                _assert_same_pass(got, want, what)
+            last = (p, got, bwd_flags)
+        assert last is not None, name
+        _anchor_float64(hip, *last)
+    # the paths this test exists for run, rather than being skipped
+    if (cell, hidden) == ('lstm', 2048):
+        assert {('f16 k-pair', 16), ('f16 k-pair', 40)} <= ran, ran
+    if (cell, hidden) == ('lstm', 1024):
+        assert {('f16 k-pair', 24), ('f16 k-pair', 32), ('f16 stagger', 40)} <= ran, ran
+    assert {('fp32', 40), ('fp32', 64)} <= ran, ran
+
+
+def _relu_backward_float64(y, dy, w_hh):
+    """dxw f64[T, B, 2, H] of the ReLU recurrence (all rows all T steps) given its output y:
+    dpre_t = (dy_t + dpre_next W) * (y_t > 0), walked against each direction's order."""
+    num_steps, batch, _ = y.shape
+    hidden = w_hh.shape[2]
+    y64 = y.double().view(num_steps, batch, 2, hidden)
+    dy64 = dy.double().view(num_steps, batch, 2, hidden)
+    dxw = torch.zeros(num_steps, batch, 2, hidden, dtype=torch.float64, device=y.device)
+    for d in (0, 1):
+        w64 = w_hh[d].double()
+        carry = torch.zeros(batch, hidden, dtype=torch.float64, device=y.device)
+        for t in (range(num_steps - 1, -1, -1) if d == 0 else range(num_steps)):
+            dpre = (dy64[t, :, d] + carry) * (y64[t, :, d] > 0)
+            dxw[t, :, d] = dpre
+            carry = dpre @ w64
+    return dxw
+
+
+def _anchor_float64(hip, p, got, bwd_flags):
+    """"Equal to a fresh workspace" must not mean "equal and wrong": y and dxw of a pass against
+    the float64 recurrence and autograd, inside the bars of the kernels' own tests (fp32: 2e-5 on
+    y, 1e-4 on dxw; fp16 backward: each row's error within 3x the fp32 kernel's + 1e-6)."""
+    xw64 = p.xw.double().requires_grad_(True)
+    ref_y = _recurrence_float64(p.cell, xw64, p.w, p.b_hh, p.sl)
+    (ref_y * p.dy.double()).sum().backward()
+    ref = xw64.grad
+    y, dxw = got[0], got[1]
+    scale_y = max(1.0, float(ref_y.detach().abs().max()))
+    assert float((y.double() - ref_y.detach()).abs().max()) < 2e-5 * scale_y
+    if p.cell == 'rnn_relu':
+        # the backward kernels take the mask y > 0 from the y they are given; where a
+        # pre-activation is ~1e-7 the float64 recurrence may have the other sign, and the
+        # flipped entry's gradient is O(1) - backpropagate float64 through the kernel's mask
+        ref = _relu_backward_float64(y, p.dy, p.w)
+    if not bwd_flags & hip.RNN_F16:
+        assert float((dxw.double() - ref).abs().max()) < 1e-4 * max(1.0, float(ref.abs().max()))
+        return
+
+    def row_err(d):
+        err = (d.double() - ref).abs().amax(dim=(0, 2, 3))
+        return float((err / ref.abs().amax(dim=(0, 2, 3)).clamp_min(1e-30)).max())
+    dxw32 = hip.rnn_bwd(p.cell, p.dy, y, p.wt, p.reserve, p.sl, b_hh_n=p.b_hh)
+    e16, e32 = row_err(dxw), row_err(dxw32)
+    assert e16 < 3 * e32 + 1e-6, (e16, e32)
+
+
+@pytest.mark.parametrize('cell,hidden,batch,flag_names', [
+    ('lstm', 1024, 40, ()), ('lstm', 1024, 40, ('RNN_F16', 'RNN_XCD_SPLIT', 'RNN_KPAIR')),
+    ('lstm', 2048, 40, ('RNN_F16', 'RNN_KPAIR')), ('lstm', 2048, 16, ('RNN_F16', 'RNN_KPAIR'))])
+def test_time_out_word_of_a_shorter_pass_is_the_one_the_poll_reads(hip, cell, hidden, batch,
+                                                                   flag_names):
+    """A pass at a shorter T than the workspace's sets its time-out word (by hand, like
+    test_staggered_launch_leaves_at_once_when_the_time_out_word_is_set - a real time-out needs a
+    starved GPU): `step_guard`, which reads the words at the current T, sees it, and the poll at
+    the workspace's T - `check_rnn_error`'s - raises and resets the barrier and K-pair words, so
+    that the next pass, at a third T, equals a fresh workspace."""
+    flags = sum(getattr(hip, f) for f in flag_names)
+    gates = hip.CELL_GATES[cell]
+    g = torch.Generator(device=DEV).manual_seed(67)
+    w = torch.randn(2, gates * hidden, hidden, device=DEV, generator=g) / np.sqrt(hidden)
+    wt = hip.transpose_batched(w)
+    ws = hip.rnn_workspace(cell, _T_MAX, batch, hidden, DEV)
+    first = _Pass(hip, cell, hidden, batch, 17, 5, w, wt, None, False)
+    first.run(ws, flags, flags)
+    hip.rnn_poll_error(cell, ws, _T_MAX, batch, hidden)
+    words = hip.rnn_timeout_words(cell, ws, 17, batch, hidden)
+    block = 1 if batch > 32 else 0
+    offset = words[block] - ws.data_ptr()
+    ws[offset:offset + 4].view(torch.int32).fill_(1)
+    guard = hip.step_guard(torch.zeros(batch, dtype=torch.int32, device=DEV),
+                           torch.zeros(batch, device=DEV), words, wgrad_word=False)
+    assert int(guard[0]) != 0 and int(guard[1]) != 0
+    with pytest.raises(hip.CtcAsrError, match='time'):
+        hip.rnn_poll_error(cell, ws, _T_MAX, batch, hidden)
+    guard = hip.step_guard(torch.zeros(batch, dtype=torch.int32, device=DEV),
+                           torch.zeros(batch, device=DEV), words, wgrad_word=False)
+    assert int(guard[0]) == 0 and int(guard[1]) == 0
+    third = _Pass(hip, cell, hidden, batch, 9, 7, w, wt, None, False)
+    got = third.run(ws, flags, flags)
+    hip.rnn_poll_error(cell, ws, _T_MAX, batch, hidden)
+    fresh = hip.rnn_workspace(cell, 9, batch, hidden, DEV)
+    want = third.run(fresh, flags, flags)
+    hip.rnn_poll_error(cell, fresh, 9, batch, hidden)
+    _assert_same_pass(got, want, (cell, hidden, batch))
 
 
 @pytest.mark.parametrize('magnitude', [1e-6, 3.0, 40.0, 3000.0])

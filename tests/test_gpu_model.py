@@ -510,6 +510,50 @@ def test_a_pass_reads_nothing_of_the_pass_before(cell, hidden, batch):
         assert rel < 1e-5, (name, rel)
 
 
+@pytest.mark.parametrize('cell,hidden,batch', [('lstm', 1024, 16), ('lstm', 1024, 40),
+                                               ('lstm', 2048, 16), ('rnn_relu', 2048, 16)])
+def test_a_shorter_pass_reads_nothing_of_a_longer_one(cell, hidden, batch):
+    """Bucketed training changes T' almost every batch, and the model keeps ONE recurrence
+    workspace per (cell, batch, hidden) for every T' up to the longest seen.  One model over
+    199 -> 149 -> 199 -> 97 frames (T' = 100, 75, 100, 49: the longest first, so the workspace is
+    reused and never re-created), new data each pass; each pass against a fresh model with the
+    same parameters, to the bars of test_a_pass_reads_nothing_of_the_pass_before.  After each pass
+    the time-out words - as `check_rnn_error` polls them and as `step_guard` reads them - are
+    clear."""
+    cfg = ModelConfig(used_model='ds2', conv_filters=(32, 32), num_units_dense=2048,
+                      num_layers_rnn=2, num_units_rnn=hidden, rnn_cell=cell, cudnn=True,
+                      dense_dropout_rate=0.0, conv_dropout_rate=0.0)
+    rng = np.random.default_rng(43)
+    flat = init_params(cfg, 43)
+
+    def sample(frames):
+        feats = torch.tensor(rng.normal(size=(batch, frames, 80)).astype(np.float32), device='cuda')
+        labels = [list(rng.integers(1, 28, size=25)) for _ in range(batch)]
+        return feats, torch.full((batch,), frames, dtype=torch.int32), labels
+
+    model = CTCModel(cfg, 'cuda', params=flat)
+    workspace = None
+    for frames in (199, 149, 199, 97):
+        data = sample(frames)
+        loss1 = float(model.forward_backward(*data))
+        guard = model.step_guard().cpu()
+        model.check_rnn_error()
+        assert int(guard[0]) == 0 and int(guard[1]) == 0, (frames, guard)
+        (ws, t_out), = model._rnn_ws.values()
+        workspace = workspace if workspace is not None else ws
+        assert ws is workspace and t_out == 100, frames     # one workspace, never re-created
+        grad1 = model.arena.grad.clone()
+        fresh = CTCModel(cfg, 'cuda', params=flat)
+        loss2 = float(fresh.forward_backward(*data))
+        fresh.check_rnn_error()
+        assert abs(loss1 - loss2) <= 1e-6 * abs(loss2), (frames, loss1, loss2)
+        for name, lo, hi in fresh.arena.layer_slices:
+            want = fresh.arena.grad[lo:hi].double()
+            rel = float((grad1[lo:hi].double() - want).norm() / want.norm().clamp_min(1e-30))
+            assert rel < 1e-5, (frames, name, rel)
+        del fresh
+
+
 def test_decode_many_equals_batch_by_batch_decoding():
     """`CTCModel.decode_many` (several batches in one beam-search launch, what
     `evaluate_dataset` uses) returns exactly what `decode_fn` returns batch by batch: different
