@@ -209,3 +209,55 @@ def test_the_model_takes_the_kernel_and_its_schedules_agree(hip, batch, frames):
             ref = grad_own[a:b].double()
             rel = float((ref - grad_e[a:b].double()).norm() / ref.norm().clamp_min(1e-30))
             assert rel < 2e-6, (early, name, rel)    # the same products, summed in another order
+
+
+@pytest.mark.parametrize('steps', [1, 2, 3])
+@pytest.mark.parametrize('batch', [1, 2, 8, 15, 17, 24, 31, 32])
+def test_behind_the_recurrence_kernel_at_the_edges(hip, steps, batch):
+    """The operands the fp16-pipe backward recurrence publishes at one to three steps and batches
+    of one row, of a tile and one row, and of tiles a row short of full - behind the one-barrier
+    kernel and behind the staggered / K-pair kernels (which take 24 and 32 rows) - for column
+    counts of 640, 2048 and 200 (not a multiple of 16): dx against float64 `dxw @ W_ih` within the
+    bars of test_against_float64_next_to_the_fp32_gemm, whole, one step at a time (the other rows
+    untouched) and one direction at a time."""
+    gen = torch.Generator(device=DEV).manual_seed(13 + 7 * steps + batch)
+    xw = torch.randn(steps, batch, 2, 4 * H, device=DEV, generator=gen) * 0.5
+    w_hh = torch.randn(2, 4 * H, H, device=DEV, generator=gen) / np.sqrt(H)
+    dy = torch.randn(steps, batch, 2 * H, device=DEV, generator=gen) * \
+        torch.logspace(-5, 0, batch, device=DEV).view(1, batch, 1)
+    assert hip.dgrad16_supported('lstm', steps, batch, H)
+    y, reserve, ws = hip.rnn_fwd('lstm', xw, w_hh, flags=hip.RNN_F16)
+    w_hh_t = hip.transpose_batched(w_hh)
+    weights = {n: torch.randn(8 * H, n, device=DEV, generator=gen) / np.sqrt(n)
+               for n in (640, 2048, 200)}
+    base = hip.RNN_F16 | hip.RNN_XCD_SPLIT
+    for flags in (hip.RNN_F16, base | hip.RNN_STAGGER, base | hip.RNN_KPAIR):
+        dxw = hip.rnn_bwd('lstm', dy, y, w_hh_t, reserve, workspace=ws, flags=flags)
+        hip.rnn_poll_error('lstm', ws, steps, batch, H)
+        d2 = dxw.view(steps * batch, 8 * H)
+        for n, w_ih in weights.items():
+            what = (flags, n)
+            packed = hip.dgrad16_pack_weights(w_ih, H, 2048.0)
+            got = hip.dgrad16_blockscaled(ws, steps, batch, H, packed, 2048.0, n)
+            assert torch.isfinite(got).all(), what
+            rms, row = rel_errors(got, d2.double() @ w_ih.double())
+            rms32, row32 = rel_errors(torch.mm(d2, w_ih), d2.double() @ w_ih.double())
+            assert rms < 2.0 * rms32 + 1e-7 and row < 3.0 * row32 + 1e-7, \
+                (what, rms, rms32, row, row32)
+            for t in range(steps):
+                part = torch.full((steps * batch, n), 7.0, device=DEV)
+                hip.dgrad16_blockscaled(ws, steps, batch, H, packed, 2048.0, n, out=part,
+                                        steps=(t, t + 1))
+                rows = slice(t * batch, (t + 1) * batch)
+                assert torch.equal(part[rows], got[rows]), (what, t)
+                part[rows] = 7.0
+                assert bool((part == 7.0).all()), (what, t)
+            for d in (0, 1):
+                half = hip.dgrad16_blockscaled(ws, steps, batch, H, packed, 2048.0, n,
+                                               dirs=(d, d + 1))
+                a = dxw[:, :, d].reshape(steps * batch, 4 * H)
+                b = w_ih[4 * H * d:4 * H * (d + 1)]
+                rms, row = rel_errors(half, a.double() @ b.double())
+                rms32, row32 = rel_errors(torch.mm(a, b), a.double() @ b.double())
+                assert rms < 2.0 * rms32 + 1e-7 and row < 3.0 * row32 + 1e-7, \
+                    (what, d, rms, rms32, row, row32)

@@ -7,6 +7,7 @@ import torch
 from oracle import ctc as octc
 from oracle import cref
 from oracle import nn as onn
+from tests import rnn_reference
 from tests.helpers import pack_labels
 
 pytestmark = pytest.mark.gpu
@@ -143,45 +144,13 @@ def test_rnn_fwd_bwd(hip, cell, use_len, dims):
         seq_len[0] = num_steps
     dy = rng.normal(size=(num_steps, batch, 2 * hidden)).astype(np.float32)
 
-    # reference: torch CPU autograd over the same recurrence written with plain ops (float64)
+    # reference: torch CPU autograd through the float64 recurrence (tests/rnn_reference.py)
     b_hh = (rng.normal(size=(2, gates * hidden)) * 0.3).astype(np.float32) if cell == 'gru' \
         else None
     xw_t = torch.tensor(xw, dtype=torch.float64, requires_grad=True)
     w_t = torch.tensor(w_hh, dtype=torch.float64, requires_grad=True)
-    ys = torch.zeros(num_steps, batch, 2 * hidden, dtype=torch.float64)
-    out_rows = []
-    for d in (0, 1):
-        for b in range(batch):
-            steps = int(seq_len[b]) if use_len else num_steps
-            h = torch.zeros(hidden, dtype=torch.float64)
-            c = torch.zeros(hidden, dtype=torch.float64)
-            for s in range(steps):
-                t = s if d == 0 else steps - 1 - s
-                pre = xw_t[t, b, d] + w_t[d] @ h
-                if cell == 'gru':
-                    rec = w_t[d] @ h
-                    xr, xz, xn = xw_t[t, b, d].split(hidden)
-                    rr, rz, rn = rec.split(hidden)
-                    r = torch.sigmoid(xr + rr)
-                    z = torch.sigmoid(xz + rz)
-                    n = torch.tanh(xn + r * (rn + torch.tensor(b_hh[d, 2 * hidden:],
-                                                               dtype=torch.float64)))
-                    h = (1 - z) * n + z * h
-                elif cell == 'lstm':
-                    i, f, g, o = pre.split(hidden)
-                    c = torch.sigmoid(f) * c + torch.sigmoid(i) * torch.tanh(g)
-                    h = torch.sigmoid(o) * torch.tanh(c)
-                elif cell == 'rnn_tanh':
-                    h = torch.tanh(pre)
-                else:
-                    h = torch.relu(pre)
-                out_rows.append((t, b, d, h))
-    ys = torch.zeros(num_steps, batch, 2, hidden, dtype=torch.float64)
-    idx_t = torch.tensor([r[0] for r in out_rows])
-    idx_b = torch.tensor([r[1] for r in out_rows])
-    idx_d = torch.tensor([r[2] for r in out_rows])
-    ys = ys.index_put((idx_t, idx_b, idx_d), torch.stack([r[3] for r in out_rows]))
-    ys = ys.reshape(num_steps, batch, 2 * hidden)
+    ys = rnn_reference.recurrence(cell, xw_t, w_t, None if b_hh is None else torch.tensor(b_hh),
+                                  seq_len)
     (ys * torch.tensor(dy, dtype=torch.float64)).sum().backward()
 
     sl = _t(seq_len, torch.int32) if use_len else None
@@ -250,41 +219,8 @@ def test_rnn_fwd_bwd(hip, cell, use_len, dims):
 
 
 def _recurrence_float64(cell, xw, w_hh, b_hh, seq_len):
-    """Forward recurrence in float64 with batched torch ops on the GPU: y [T, B, 2H]."""
-    num_steps, batch, _, _ = xw.shape
-    hidden = w_hh.shape[2]
-    x64, w64 = xw.double(), w_hh.double()
-    steps = torch.full((batch,), num_steps, device=xw.device, dtype=torch.long) \
-        if seq_len is None else seq_len.long()
-    rows = torch.arange(batch, device=xw.device)
-    y = torch.zeros(num_steps, batch, 2 * hidden, dtype=torch.float64, device=xw.device)
-    for d in (0, 1):
-        h = torch.zeros(batch, hidden, dtype=torch.float64, device=xw.device)
-        c = torch.zeros_like(h)
-        for s in range(num_steps):
-            active = s < steps
-            t = torch.where(active, torch.full_like(steps, s) if d == 0 else steps - 1 - s,
-                            torch.zeros_like(steps))
-            x = x64[t, rows, d]
-            rec = h @ w64[d].t()
-            if cell == 'rnn_relu':
-                h_new = torch.relu(x + rec)
-            elif cell == 'rnn_tanh':
-                h_new = torch.tanh(x + rec)
-            elif cell == 'lstm':
-                i, f, g, o = (x + rec).split(hidden, dim=1)
-                c_new = torch.sigmoid(f) * c + torch.sigmoid(i) * torch.tanh(g)
-                h_new = torch.sigmoid(o) * torch.tanh(c_new)
-                c = torch.where(active[:, None], c_new, c)
-            else:
-                xr, xz, xn = x.split(hidden, dim=1)
-                rr, rz, rn = rec.split(hidden, dim=1)
-                r, z = torch.sigmoid(xr + rr), torch.sigmoid(xz + rz)
-                n = torch.tanh(xn + r * (rn + b_hh[d, 2 * hidden:].double()))
-                h_new = (1 - z) * n + z * h
-            h = torch.where(active[:, None], h_new, h)
-            y[t[active], rows[active], d * hidden:(d + 1) * hidden] = h[active]
-    return y
+    """Forward recurrence in float64 with batched torch ops (on xw's device): y [T, B, 2H]."""
+    return rnn_reference.recurrence(cell, xw, w_hh, b_hh, seq_len)
 
 
 @pytest.mark.parametrize('cell', ['lstm', 'gru'])

@@ -31,19 +31,34 @@ CASES = {
 }
 
 
-def _setup(case, seed=0, batch=3, frames=61, hidden=64, dense=32, layers=2):
+_PARAMS = {}
+
+
+def _setup(case, seed=0, batch=3, frames=61, hidden=64, dense=32, layers=2, label_len=None):
+    """``label_len``: every label row that long (default: random lengths 1..8, which the
+    shortest sequences cannot align)."""
     cfg = ModelConfig(num_units_dense=dense, num_layers_rnn=layers, num_units_rnn=hidden,
                       dense_dropout_rate=0.0, **CASES[case])
+    key = (case, seed, hidden, dense, layers)
+    if key not in _PARAMS:
+        # (the weights of the last configuration are kept: the H = 2048 ones take seconds)
+        _PARAMS.clear()
+        rng = np.random.default_rng(seed)
+        flat = init_params(cfg, seed)
+        for name in flat:   # non-zero biases and livelier weights than the tiny-σ initialiser
+            flat[name] = (flat[name] + rng.normal(size=flat[name].shape) * 0.05).astype(np.float32)
+        _PARAMS[key] = (flat, rng.bit_generator.state)
+    flat, state = _PARAMS[key]
+    flat = dict(flat)
     rng = np.random.default_rng(seed)
-    flat = init_params(cfg, seed)
-    for name in flat:   # non-zero biases and livelier weights than the tiny-σ initialiser
-        flat[name] = (flat[name] + rng.normal(size=flat[name].shape) * 0.05).astype(np.float32)
+    rng.bit_generator.state = state
     feats = rng.normal(size=(batch, frames, 80)).astype(np.float32)
     flen = np.array([frames] + list(rng.integers(frames // 2, frames, size=batch - 1)),
                     dtype=np.int32)
     for b in range(batch):
         feats[b, flen[b]:] = 0.0
-    labels = [list(rng.integers(1, 28, size=rng.integers(1, 9))) for _ in range(batch)]
+    labels = [list(rng.integers(1, 28, size=rng.integers(1, 9) if label_len is None else label_len))
+              for _ in range(batch)]
     return cfg, flat, feats, flen, labels
 
 
@@ -83,6 +98,51 @@ def test_gradients_through_the_other_persistent_kernels(case, hidden, batch):
     assert hip.rnn_persistent_supported(cell, (frames + 1) // 2, batch, hidden)
     model = _check_logits_loss_and_gradients(case, hidden=hidden, frames=frames, batch=batch)
     model.check_rnn_error()
+
+
+def _check_guards(model, t_out):
+    """T' as the model derived it, the device guard words clear, no time-out anywhere."""
+    assert model._acts['t_out'] == t_out
+    assert model.step_guard().tolist() == [0, 0]
+    model.check_rnn_error()
+
+
+@pytest.mark.parametrize('case,hidden', [('ds2_lstm_2conv', 1024), ('ds2_gru', 1024),
+                                         ('ds2_lstm_2conv', 2048), ('ds2_relu', 2048)])
+@pytest.mark.parametrize('batch', [1, 2])
+def test_the_smallest_inputs(case, hidden, batch):
+    """One and two utterances whose front end leaves T' = 1, 2, 3 frames (2 x T' feature frames:
+    the first convolution strides 2 in time, the 2-conv and 3-conv front ends alike) - the
+    recurrence kernels' one-step and few-step passes inside the model, one-label transcripts so
+    that the CTC alignment is feasible.  Same bars as the other cases; at T' = 1 the greedy
+    decode of the model's logits equals the oracle decoder on the same logits."""
+    for t_out in (1, 2, 3):
+        model = _check_logits_loss_and_gradients(case, hidden=hidden, frames=2 * t_out,
+                                                 batch=batch, label_len=1)
+        _check_guards(model, t_out)
+        if t_out == 1:
+            cfg, flat, feats, flen, _ = _setup(case, hidden=hidden, frames=2, batch=batch,
+                                               label_len=1)
+            logits, seq_len = model.inference_fn(torch.tensor(feats), torch.tensor(flen),
+                                                 training=False)
+            decoded, _, _ = model.decode_fn(logits, seq_len, None, greedy=True)
+            assert decoded == octc.greedy_decode(logits.cpu().numpy(), seq_len.cpu().numpy())
+
+
+@pytest.mark.parametrize('hidden,batch', [(1024, 33), (1024, 56), (2048, 33)])
+def test_two_row_blocks_at_two_frames(hidden, batch):
+    """T' = 2 with two blocks of rows under the default flags: at LSTM-1024 block 0 (32 rows)
+    takes the staggered backward kernel, and at B = 56 block 1 (24 rows, row stride 56) does too;
+    at LSTM-2048 every 16-row tile the K-pair kernel."""
+    from ctc_asr_amd import hip
+    assert hip.rnn_f16_recurrence('lstm', 2, batch, hidden, hip.RNN_F16, backward=True)
+    model = _check_logits_loss_and_gradients('ds2_lstm_2conv', hidden=hidden, frames=4,
+                                             batch=batch, label_len=1)
+    _check_guards(model, 2)
+    if hidden == 1024:
+        assert model.rnn_stagger_flag & hip.RNN_STAGGER
+    else:
+        assert model.rnn_kpair_wide
 
 
 @pytest.mark.parametrize('frames,pipelined', [(131, 4), (129, 4), (97, 2), (141, 3)])

@@ -210,3 +210,46 @@ def test_a_part_that_gives_up_adds_nothing_and_the_step_is_dropped(hip):
     finally:
         hip.set_option('wgrad16_spin_limit', 0)
         _WGRAD16_SYNC[torch.cuda.current_device()].zero_()
+
+
+@pytest.mark.parametrize('rows', [1, 2, 15, 31, 33])
+@pytest.mark.parametrize('shift', [-2, -1, 1, 2])
+def test_row_ranges_shorter_than_a_stage(hip, rows, shift):
+    """Step ranges of one or two frames of a batch of one or two utterances: fewer rows than one
+    32-row stage (the rest of the stage zero-filled), or one more; the second operand shifted by
+    one batch (y_shift = +-B, B = 1, 2) so that whole ranges of it fall outside the rows; parts
+    = 1, 2, 8 - more parts than stages.  Against float64 within the bars of
+    test_against_float64_next_to_the_fp32_gemm, exactly zero where the shifted operand has no
+    rows; the sync words back at zero and no part gave up waiting.  (Below one stage the library's
+    fp32 error is one or a few roundings of single products, finer than the 2^-21 that two fp16
+    pieces of each operand resolve: there the row bar keeps that resolution as its floor.)"""
+    from ctc_asr_amd.hip import _WGRAD16_SYNC
+    g = torch.Generator(device=DEV).manual_seed(100 * rows + shift)
+    m, nx, ny = 300, 48, 272
+    d = torch.randn(rows, m, device=DEV, generator=g)
+    d *= torch.logspace(-9, -3, m, device=DEV)[torch.randperm(m, device=DEV, generator=g)]
+    x = torch.rand(rows, nx, device=DEV, generator=g) * 2 - 1
+    y = torch.rand(rows, ny, device=DEV, generator=g) * 2 - 1
+    y_sh = torch.zeros_like(y)
+    if shift < 0 and rows > -shift:
+        y_sh[-shift:] = y[:shift]
+    elif shift > 0 and rows > shift:
+        y_sh[:rows - shift] = y[shift:]
+    ref_x = d.double().t() @ x.double()
+    ref_y = d.double().t() @ y_sh.double()
+    for parts in (1, 2, 8):
+        dw_x, dw_y = own_wgrad(hip, d, x, 32768.0, y, shift, 32768.0, parts=parts)
+        for got, ref, lib in ((dw_x, ref_x, torch.mm(d.t(), x)),
+                              (dw_y, ref_y, torch.mm(d.t(), y_sh))):
+            assert torch.isfinite(got).all()
+            if float(ref.abs().max()) == 0.0:
+                assert float(got.abs().max()) == 0.0, parts
+                continue
+            rms, row = errors(got, ref)
+            rms32, row32 = errors(lib, ref)
+            floor = 1e-7 if rows >= 32 else 2.0 ** -21
+            assert rms < 2.0 * rms32 + 1e-7 and row < 3.0 * row32 + floor, \
+                (parts, rms, rms32, row, row32)
+    assert not hip.wgrad16_gave_up_waiting(DEV)
+    sync = _WGRAD16_SYNC.get(torch.cuda.current_device())
+    assert sync is None or int(sync.abs().sum()) == 0
