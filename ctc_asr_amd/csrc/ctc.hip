@@ -101,6 +101,9 @@ ctc_sweep_kernel(const float *__restrict__ logits, const int *__restrict__ label
     const int S = 2 * L + 1;
     const int len = seq_len[b];
     const int *lab = labels + label_offsets[b];
+    // a row longer than max_label_len (or with decreasing offsets) does not fit the lattices and
+    // the lattice slab sized from s_pad: refuse it before anything is written
+    const bool unfit = L < 0 || S > s_pad;
 
     double *lat0 = reinterpret_cast<double *>(smem);
     double *lat1 = lat0 + s_pad;
@@ -111,7 +114,7 @@ ctc_sweep_kernel(const float *__restrict__ logits, const int *__restrict__ label
 
     if (tid < 4) flags[tid] = 0;
     __syncthreads();
-    for (int u = tid; u < S; u += CTC_THREADS) {
+    for (int u = tid; u < (unfit ? 0 : S); u += CTC_THREADS) {
         int sym = blank;
         if (u & 1) {
             sym = lab[u >> 1];
@@ -122,7 +125,7 @@ ctc_sweep_kernel(const float *__restrict__ logits, const int *__restrict__ label
     }
     __syncthreads();
     int st = 0;
-    if (flags[0] || len > T || len < 0) st = 2;
+    if (unfit || flags[0] || len > T || len < 0) st = 2;
     else if (len < L + flags[1]) st = 1;
     const int live = st == 0 ? len : 0;
 

@@ -84,7 +84,8 @@ int ctcasr_log_softmax_bwd(const float *y, const float *dy, float *dx, int rows,
  *   loss          [B]   -ln p(label_b | x_b); +inf when status[b] != 0
  *   grad_logits   [T, B, C] d(sum_b grad_scale * loss_b) / d logits; rows t >= seq_len[b] are 0
  *   status        int32 [B]: 0 ok; 1 "not enough time for target transition sequence"
- *                 (TensorFlow raises here); 2 label id out of range / seq_len > T
+ *                 (TensorFlow raises here); 2 label id out of range / seq_len > T, or the row
+ *                 is longer than max_label_len / has a negative length
  * Workspace: ctcasr_ctc_loss_workspace_bytes(T, B, C, max_label_len). */
 size_t ctcasr_ctc_loss_workspace_bytes(int T, int B, int C, int max_label_len);
 int ctcasr_ctc_loss_fwd_bwd(const float *logits, const int32_t *labels,

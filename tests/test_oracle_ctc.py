@@ -108,3 +108,87 @@ def test_c_beam_search_equals_numpy_beam_search():
 def test_dense_to_label_lists_drops_padding_zeros():
     assert octc.dense_to_label_lists(np.array([[3, 4, 0, 0], [0, 0, 0, 0], [1, 0, 2, 0]])) == \
         [[3, 4], [], [1, 2]]
+
+
+def _torch_ctc(logits, labels, seq_len, blank):
+    """torch.nn.functional.ctc_loss in float64 on the same (float32) logits: loss per row and the
+    gradient w.r.t. the logits through autograd."""
+    x = torch.tensor(np.asarray(logits, dtype=np.float64), requires_grad=True)
+    ref = torch.nn.functional.ctc_loss(
+        torch.log_softmax(x, -1), torch.tensor([v for r in labels for v in r], dtype=torch.long),
+        torch.tensor(seq_len), torch.tensor([len(r) for r in labels]), blank=blank,
+        reduction='none')
+    ref.sum().backward()
+    return ref.detach().numpy(), x.grad.numpy()
+
+
+def _edge_case(name):
+    """(logits f32[T, B, C], labels, seq_len, blank) of the edge shapes test_gpu_ctc_edges.py
+    runs the kernel at."""
+    rng = np.random.default_rng(sum(map(ord, name)))
+
+    def labels_of(lengths, classes, blank):
+        ids = np.array([c for c in range(classes) if c != blank])
+        return [rng.choice(ids, size=n).tolist() for n in lengths]
+
+    if name == 'T=1':
+        classes, blank, labels, seq_len = 5, 4, [[], [2], [0]], [1, 1, 1]
+    elif name == 'T=1 blank=0':
+        classes, blank, labels, seq_len = 5, 0, [[], [3]], [1, 1]
+    elif name == 'T=3 len=0':
+        classes, blank, labels, seq_len = 6, 5, [[], [1, 1], [], [2]], [0, 3, 2, 1]
+    elif name == 'C=64 blank=0':
+        classes, blank = 64, 0
+        labels, seq_len = labels_of([63, 20, 0], classes, blank), [140, 90, 70]
+    elif name == 'C=64 blank=32':
+        classes, blank = 64, 32
+        labels, seq_len = labels_of([63, 20, 1], classes, blank), [140, 140, 3]
+    elif name == 'L=575 blank=0':
+        classes, blank = 64, 0
+        labels, seq_len = labels_of([575, 300], classes, blank), [1200, 1100]
+    elif name == 'L=575 blank=32':
+        classes, blank = 64, 32
+        labels, seq_len = labels_of([575, 575], classes, blank), [1200, 1200]
+    num_steps = max(seq_len + [1])
+    logits = (rng.normal(size=(num_steps, len(labels), classes)) * 2).astype(np.float32)
+    return logits, labels, seq_len, blank
+
+
+@pytest.mark.parametrize('name', ['T=1', 'T=1 blank=0', 'T=3 len=0', 'C=64 blank=0',
+                                  'C=64 blank=32', 'L=575 blank=0', 'L=575 blank=32'])
+def test_c_oracle_matches_torch_at_the_edge_shapes(name):
+    """The C oracle that test_gpu_ctc_edges.py measures the kernel against, pinned at the same
+    edges: T = 1, len = 0 with L = 0 (loss exactly 0, no gradient), L = 575 (the kernel's label
+    ceiling), C = 64 and a blank of 0 or C // 2."""
+    logits, labels, seq_len, blank = _edge_case(name)
+    loss, grad, status = cref.ctc_loss(logits, labels, seq_len, blank)
+    ref_loss, ref_grad = _torch_ctc(logits, labels, seq_len, blank)
+    assert (status == 0).all()
+    assert (np.abs(loss - ref_loss) <= 1e-9 * np.maximum(1.0, np.abs(ref_loss))).all()
+    assert np.abs(grad - ref_grad).max() < 1e-9
+    for b, length in enumerate(seq_len):
+        assert (grad[length:, b] == 0).all()
+        if length == 0:
+            assert loss[b] == 0.0
+
+
+@pytest.mark.parametrize('classes', [2, 3, 4])
+@pytest.mark.parametrize('num_steps', [1, 2, 3, 4])
+def test_c_oracle_equals_path_enumeration(num_steps, classes):
+    """Every labelling that has probability at T <= 4, C <= 4, with the blank at C - 1, 0 and
+    C // 2: the C oracle's loss is minus the log of the summed probability of its paths, and a
+    labelling that needs more frames than there are is refused with status 1."""
+    rng = np.random.default_rng(10 * num_steps + classes)
+    logits = (rng.normal(size=(num_steps, classes)) * 2).astype(np.float32)
+    for blank in sorted({classes - 1, 0, classes // 2}):
+        post = octc.brute_force_posteriors(logits.astype(np.float64), blank)
+        labels = [list(label) for label in post]
+        batch = np.repeat(logits[:, None, :], len(labels), axis=1)
+        loss, _, status = cref.ctc_loss(batch, labels, [num_steps] * len(labels), blank)
+        assert (status == 0).all()
+        want = -np.log([post[tuple(label)] for label in labels])
+        assert np.abs(loss - want).max() < 1e-9
+        symbol = 0 if blank else 1
+        _, _, status = cref.ctc_loss(logits[:, None, :], [[symbol] * num_steps + [symbol]],
+                                     [num_steps], blank)
+        assert status[0] == 1
