@@ -33,6 +33,17 @@ struct FeatTables {
 
 __device__ __forceinline__ unsigned bitrev10(unsigned v) { return __brev(v) >> 22; }
 
+__host__ __device__ __forceinline__ int frames_of(int n) {
+    return n <= FEAT_FRAME ? 1 : 1 + (n - FEAT_FRAME + FEAT_STEP - 1) / FEAT_STEP;
+}
+
+// Frame count of row b as all three kernels see it: 0 for a row whose num_samples lies outside
+// [1, n_max].  Such a row reads none of its PCM, gets out_len 0 and all-zero output rows.
+__device__ __forceinline__ int row_frames(const int *num_samples, int b, int n_max) {
+    const int n = num_samples[b];
+    return n < 1 || n > n_max ? 0 : frames_of(n);
+}
+
 // grid (Tmax, B).  raw32: [B, Tmax, 80] float (mel: final pre-normalisation values; mfcc: unused)
 // cep64: [B, Tmax, 40] double (mfcc only)
 __global__ void __launch_bounds__(FEAT_THREADS)
@@ -48,9 +59,9 @@ frame_features_kernel(const int16_t *__restrict__ pcm, const int *__restrict__ n
     __shared__ double logmel[FEAT_NFILT];
     __shared__ double wsum[FEAT_THREADS / 64];
     const int t = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
-    const int n = num_samples[b];
-    const int frames = n <= FEAT_FRAME ? 1 : 1 + (n - FEAT_FRAME + FEAT_STEP - 1) / FEAT_STEP;
+    const int frames = row_frames(num_samples, b, n_max);
     if (t >= frames) return;
+    const int n = num_samples[b];
     const int16_t *x = pcm + (size_t)b * n_max;
     auto sample = [&](int i) -> double {          // pre-emphasised sample i of the frame
         const int g = t * FEAT_STEP + i;
@@ -124,10 +135,9 @@ frame_features_kernel(const int16_t *__restrict__ pcm, const int *__restrict__ n
 // mfcc: [cepstra || delta] -> raw32.  grid (Tmax, B), 64 threads.
 __global__ void __launch_bounds__(64)
 mfcc_delta_kernel(const double *__restrict__ cep64, const int *__restrict__ num_samples,
-                  int t_max, float *__restrict__ raw32) {
+                  int n_max, int t_max, float *__restrict__ raw32) {
     const int t = blockIdx.x, b = blockIdx.y, c = threadIdx.x;
-    const int n = num_samples[b];
-    const int frames = n <= FEAT_FRAME ? 1 : 1 + (n - FEAT_FRAME + FEAT_STEP - 1) / FEAT_STEP;
+    const int frames = row_frames(num_samples, b, n_max);
     if (t >= frames || c >= FEAT_NCEP) return;
     const double *base = cep64 + (size_t)b * t_max * FEAT_NCEP + c;
     double d = 0.0;
@@ -148,8 +158,9 @@ mfcc_delta_kernel(const double *__restrict__ cep64, const int *__restrict__ num_
 // norm: 0 none, 1 local (per feature column over time), 2 local_scalar (whole matrix).
 #define NORM_SPLIT 16
 __global__ void __launch_bounds__(FEAT_THREADS)
-normalize_kernel(const float *__restrict__ raw32, const int *__restrict__ num_samples, int t_max,
-                 int out_t, int drop, int norm, float *__restrict__ out, int *__restrict__ out_len) {
+normalize_kernel(const float *__restrict__ raw32, const int *__restrict__ num_samples, int n_max,
+                 int t_max, int out_t, int drop, int norm, float *__restrict__ out,
+                 int *__restrict__ out_len) {
     // statistics: thread = (4 feature columns, one of 12 row groups): 16-byte loads, every lane
     // busy, eight rows in flight per thread (one column per lane and one accumulator took 100 us
     // for a 5 MB matrix: the loop only waits for its loads)
@@ -157,15 +168,19 @@ normalize_kernel(const float *__restrict__ raw32, const int *__restrict__ num_sa
     __shared__ double s1[RG][FEAT_NFILT], s2[RG][FEAT_NFILT];
     __shared__ float mean_s[FEAT_NFILT], inv_s[FEAT_NFILT];
     const int b = blockIdx.x, tid = threadIdx.x;
-    const int n = num_samples[b];
-    const int frames = n <= FEAT_FRAME ? 1 : 1 + (n - FEAT_FRAME + FEAT_STEP - 1) / FEAT_STEP;
+    const int frames = row_frames(num_samples, b, n_max);
     const int step = drop ? 2 : 1;
     const int kept = (frames + step - 1) / step;
     const float *src = raw32 + (size_t)b * t_max * FEAT_NFILT;
     if (tid == 0 && blockIdx.y == 0) out_len[b] = kept;
-    if (norm != 0) {
+    // The sums are of v - v0, v0 = the column's first kept value ('local') or the matrix's first
+    // value ('local_scalar'): a constant column then has variance exactly 0 and comes out NaN, as
+    // in the reference, instead of NaN or 0 depending on how q / n - mean^2 rounds.
+    if (norm != 0 && kept > 0) {
         if (tid < RG * C4) {
             const int c4 = tid % C4, rg = tid / C4;
+            const float4 v0 = norm == 2 ? make_float4(src[0], src[0], src[0], src[0])
+                                        : *reinterpret_cast<const float4 *>(src + 4 * c4);
             double a[4] = {0.0, 0.0, 0.0, 0.0}, q[4] = {0.0, 0.0, 0.0, 0.0};
             for (int i = rg; i < kept; i += 8 * RG) {
                 float4 v[8];
@@ -175,14 +190,18 @@ normalize_kernel(const float *__restrict__ raw32, const int *__restrict__ num_sa
                     v[j] = row < kept
                                ? *reinterpret_cast<const float4 *>(
                                      src + (size_t)row * step * FEAT_NFILT + 4 * c4)
-                               : make_float4(0.f, 0.f, 0.f, 0.f);
+                               : v0;
                 }
 #pragma unroll
                 for (int j = 0; j < 8; ++j) {
-                    a[0] += (double)v[j].x; q[0] += (double)v[j].x * (double)v[j].x;
-                    a[1] += (double)v[j].y; q[1] += (double)v[j].y * (double)v[j].y;
-                    a[2] += (double)v[j].z; q[2] += (double)v[j].z * (double)v[j].z;
-                    a[3] += (double)v[j].w; q[3] += (double)v[j].w * (double)v[j].w;
+                    const double dx = (double)v[j].x - (double)v0.x;
+                    const double dy = (double)v[j].y - (double)v0.y;
+                    const double dz = (double)v[j].z - (double)v0.z;
+                    const double dw = (double)v[j].w - (double)v0.w;
+                    a[0] += dx; q[0] += dx * dx;
+                    a[1] += dy; q[1] += dy * dy;
+                    a[2] += dz; q[2] += dz * dz;
+                    a[3] += dw; q[3] += dw * dw;
                 }
             }
 #pragma unroll
@@ -197,14 +216,16 @@ normalize_kernel(const float *__restrict__ raw32, const int *__restrict__ num_sa
         __syncthreads();
         if (tid < FEAT_NFILT) {
             double a = s1[0][tid], q = s2[0][tid], cnt = (double)kept;
+            double v0 = (double)src[tid];
             if (norm == 2) {
                 a = 0.0; q = 0.0;
                 for (int c = 0; c < FEAT_NFILT; ++c) { a += s1[0][c]; q += s2[0][c]; }
                 cnt *= FEAT_NFILT;
+                v0 = (double)src[0];
             }
-            const double mean = a / cnt;
-            const double var = fmax(q / cnt - mean * mean, 0.0);
-            mean_s[tid] = (float)mean;
+            const double shift = a / cnt;                 // mean - v0
+            const double var = fmax(q / cnt - shift * shift, 0.0);
+            mean_s[tid] = (float)(v0 + shift);
             inv_s[tid] = (float)(1.0 / sqrt(var));   // no epsilon, like the reference
         }
         __syncthreads();
@@ -258,8 +279,6 @@ void build_tables(FeatTables *t, int sampling_rate) {
     }
 }
 
-int frames_of(int n) { return n <= FEAT_FRAME ? 1 : 1 + (n - FEAT_FRAME + FEAT_STEP - 1) / FEAT_STEP; }
-
 size_t tables_bytes() { return ctcasr_align_up(sizeof(FeatTables), 256); }
 
 }  // namespace
@@ -271,9 +290,11 @@ extern "C" int ctcasr_features_num_frames(int num_samples) {
 extern "C" size_t ctcasr_features_tables_bytes(void) { return tables_bytes(); }
 
 // Fills `tables` (device, ctcasr_features_tables_bytes()) for the given sampling rate: FFT
-// twiddles, the psf mel filterbank in sparse form, the liftered DCT matrix.  Call once.
+// twiddles, the psf mel filterbank in sparse form, the liftered DCT matrix.  Call once.  Only
+// 16000 is served; any other rate is refused before the device is touched.
 extern "C" int ctcasr_features_init_tables(void *tables, int sampling_rate, ctcasr_stream_t stream) {
-    if (!tables || sampling_rate <= 128) return CTCASR_ERR_BAD_ARGUMENT;
+    // frame length and step are compile-time constants (25 ms / 10 ms at 16 kHz): no other rate
+    if (!tables || sampling_rate != 16000) return CTCASR_ERR_BAD_ARGUMENT;
     static FeatTables host;     // pageable staging buffer; the copy below is synchronous
     build_tables(&host, sampling_rate);
     if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) return CTCASR_ERR_LAUNCH;
@@ -313,9 +334,9 @@ extern "C" int ctcasr_features(const int16_t *pcm, const int32_t *num_samples, i
     frame_features_kernel<<<grid, FEAT_THREADS, 0, s>>>(pcm, num_samples, max_samples, t_max,
                                                         feature_type, tab, raw32, cep64);
     if (feature_type == 1)
-        mfcc_delta_kernel<<<grid, 64, 0, s>>>(cep64, num_samples, t_max, raw32);
-    normalize_kernel<<<dim3(B, NORM_SPLIT), FEAT_THREADS, 0, s>>>(raw32, num_samples, t_max, out_frames,
-                                                drop_every_second_frame, normalization, out,
-                                                out_len);
+        mfcc_delta_kernel<<<grid, 64, 0, s>>>(cep64, num_samples, max_samples, t_max, raw32);
+    normalize_kernel<<<dim3(B, NORM_SPLIT), FEAT_THREADS, 0, s>>>(
+        raw32, num_samples, max_samples, t_max, out_frames, drop_every_second_frame,
+        normalization, out, out_len);
     return ctcasr_launch_status();
 }

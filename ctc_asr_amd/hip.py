@@ -1227,7 +1227,9 @@ def features_num_frames(num_samples):
 @_on_tensor_device
 def features(pcm, num_samples, feature_type='mel', normalization='local',
              drop_every_second_frame=False, sampling_rate=16000, out=None, out_len=None):
-    """pcm int16[B, N] (device), num_samples int32[B] (device) -> (f32[B, T, 80], i32[B])."""
+    """pcm int16[B, N] (device), num_samples int32[B] (device) -> (f32[B, T, 80], i32[B]).
+    Only sampling_rate 16000 is served (CtcAsrError otherwise); a row whose num_samples lies
+    outside [1, N] gets length 0 and all-zero frames."""
     if pcm.dtype != torch.int16:
         raise CtcAsrError('pcm must be int16 (raw WAV samples, not rescaled).')
     batch, max_samples = pcm.shape

@@ -588,13 +588,20 @@ int ctcasr_absmax(const float *x, int64_t n, uint32_t *max_bits, ctcasr_stream_t
  * Replaces python_speech_features.logfbank / mfcc / delta + the post-processing of load_sample
  * (asr/input_functions.py:156-335) for a batch of utterances.
  *   pcm            int16 [B, max_samples] raw PCM (NOT rescaled), rows zero padded
- *   num_samples    int32 [B] valid samples per row (>= 401 like the reference's check)
+ *   num_samples    int32 [B] valid samples per row.  The reference refuses fewer than 401; the
+ *                  kernels serve 1..max_samples (n <= 400 is psf's one zero-padded frame).  A row
+ *                  outside [1, max_samples] reads none of its PCM and gets out_len 0 and all-zero
+ *                  output rows, like ctcasr_features_num_frames(n < 1) = 0.
  *   feature_type   0 = 'mel' (80 log-mel), 1 = 'mfcc' (40 cepstra + 40 deltas)
  *   normalization  0 = 'none', 1 = 'local', 2 = 'local_scalar'
  *   tables         device block of ctcasr_features_tables_bytes(), filled once by
- *                  ctcasr_features_init_tables(tables, sampling_rate, stream) (synchronous)
+ *                  ctcasr_features_init_tables(tables, sampling_rate, stream) (synchronous).
+ *                  The frame length 400 and step 160 are 25 ms / 10 ms at 16 kHz only, so any
+ *                  sampling_rate other than 16000 is CTCASR_ERR_BAD_ARGUMENT.
  *   out            float32 [B, out_frames, 80], rows beyond an utterance's length are 0
  *   out_len        int32 [B] frames per utterance (after the optional every-2nd-frame drop)
+ * 'local' / 'local_scalar' divide by the population std with no epsilon, like the reference: a
+ * column (matrix) that is constant over the kept frames comes out all NaN.
  * ctcasr_features_num_frames(n) = 1 + ceil((n - 400) / 160) is the frame count of n samples. */
 int ctcasr_features_num_frames(int num_samples);
 size_t ctcasr_features_tables_bytes(void);

@@ -132,3 +132,28 @@ def test_missing_library_fails_loudly(tmp_path):
     from ctc_asr_amd import hip
     with pytest.raises(hip.CtcAsrError):
         hip.load(str(tmp_path / 'libctcasr.so'))
+
+
+def test_feature_tables_refuse_every_rate_but_16k(lib):
+    """Frame length 400 and step 160 are compile-time constants, 25 ms / 10 ms at 16 kHz only:
+    any other rate is an argument error, found before the device is touched."""
+    import ctypes
+    import torch
+    nbytes = lib.ctcasr_features_tables_bytes()
+    host = ctypes.create_string_buffer(nbytes)
+    for rate in (8000, 22050, 16001, 15999, 44100, 129, 0, -16000):
+        assert lib.ctcasr_features_init_tables(ctypes.addressof(host), rate, None) == -1, rate
+    assert lib.ctcasr_features_init_tables(None, 16000, None) == -1
+    if torch.cuda.is_available():
+        tables = torch.empty(nbytes, dtype=torch.uint8, device='cuda')
+        assert lib.ctcasr_features_init_tables(tables.data_ptr(), 16000, None) == 0
+    else:
+        # no device: 16000 passes the argument check and fails at the first runtime call
+        assert lib.ctcasr_features_init_tables(ctypes.addressof(host), 16000, None) not in (0, -1)
+
+
+def test_feature_frame_count_matches_the_oracle(lib):
+    from oracle import features as ofeat
+    for n in list(range(-1, 3001)) + [16000, 272000, 272001]:
+        expect = 0 if n < 1 else ofeat.num_frames(n)
+        assert lib.ctcasr_features_num_frames(n) == expect, n

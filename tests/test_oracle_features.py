@@ -100,3 +100,63 @@ def test_int16_pcm_is_not_rescaled():
     raw_f, _ = ofeat.load_sample_from_pcm(pcm.astype(np.float64) / 32768.0, 16000, 'mel', 'none')
     # scaling the signal by 1/32768 shifts every log-energy by -2*ln(32768)
     assert np.allclose(raw_i16 - raw_f, 2 * np.log(32768.0), atol=1e-3)
+
+
+# lengths around the frame-count seams: 1 frame up to 400 samples, then one more every 160
+SEAM_LENGTHS = [1, 2, 159, 160, 399, 400, 401, 402, 559, 560, 561, 720, 721, 880, 881, 1040, 1041]
+
+
+def _direct_power_spectrum(signal, num_samples):
+    """psf framing and |DFT|^2 / 1024 written out: pre-emphasis by hand, frame t = samples
+    160 t .. 160 t + 399 (zero past the signal's end), an O(N^2) float64 DFT of 1024 points."""
+    x = np.asarray(signal, dtype=np.float64)
+    y = np.concatenate([x[:1], x[1:] - 0.97 * x[:-1]])
+    count = 1 if num_samples <= 400 else 1 + -(-(num_samples - 400) // 160)
+    m = np.arange(400)
+    basis = np.exp(-2j * np.pi * np.outer(np.arange(513), m) / 1024.0)
+    out = np.empty((count, 513))
+    for t in range(count):
+        frame = np.zeros(400)
+        seg = y[160 * t: min(160 * t + 400, num_samples)]
+        frame[:len(seg)] = seg
+        out[t] = np.abs(basis @ frame) ** 2 / 1024.0
+    return out
+
+
+@pytest.mark.parametrize('num_samples', SEAM_LENGTHS)
+def test_power_spectrum_at_the_frame_seams_against_a_direct_dft(num_samples):
+    pcm = _pcm(num_samples / 16000.0 + 1e-9, seed=num_samples)[:num_samples]
+    pcm[0] = 32767 if num_samples % 2 else -32768          # full scale on the first sample
+    assert len(pcm) == num_samples
+    frames = ofeat.frame_signal(ofeat.preemphasis(pcm))
+    assert frames.shape == (ofeat.num_frames(num_samples), 400)
+    got = ofeat.power_spectrum(frames)
+    ref = _direct_power_spectrum(pcm, num_samples)
+    assert got.shape == ref.shape
+    assert np.abs(got - ref).max() <= 1e-9 * ref.max()
+    # the energy psf puts in c0 is the sum over the one-sided spectrum
+    _, energy = ofeat.filterbank_energies(pcm)
+    assert np.allclose(energy, ref.sum(axis=1), rtol=1e-12)
+
+
+def test_one_frame_up_to_400_samples_and_silence_takes_eps():
+    for n in (1, 2, 160, 399, 400):
+        feat, energy = ofeat.filterbank_energies(np.zeros(n, dtype=np.int16))
+        assert feat.shape == (1, 80) and (feat == ofeat.EPS).all() and (energy == ofeat.EPS).all()
+    assert ofeat.num_frames(1) == 1 and ofeat.num_frames(400) == 1
+
+
+@pytest.mark.parametrize('count', [1, 2, 3, 4, 5])
+def test_delta_at_a_few_frames_is_the_edge_padded_closed_form(count):
+    rng = np.random.default_rng(40 + count)
+    c = rng.normal(size=(count, 40)) * 10
+    at = lambda t: c[min(max(t, 0), count - 1)]           # noqa: E731  edge padding
+    ref = np.stack([(1 * (at(t + 1) - at(t - 1)) + 2 * (at(t + 2) - at(t - 2))) / 10.0
+                    for t in range(count)])
+    got = ofeat.delta(c, 2)
+    assert got.shape == (count, 40)
+    assert np.abs(got - ref).max() <= 1e-12
+    if count == 1:      # -2c - c + 0 + c + 2c: zero up to the rounding of the running sum
+        assert np.abs(got).max() <= 1e-15 * np.abs(c).max()
+    if count == 2:
+        assert np.allclose(got, [0.3 * (c[1] - c[0])] * 2, rtol=0, atol=1e-12)
