@@ -43,6 +43,8 @@ SIGNATURES = {
     'ctcasr_ctc_greedy_decode': (_c_int, [_c_p, _c_p] + [_c_int] * 4 + [_c_p, _c_p, _c_p]),
     'ctcasr_ctc_beam_workspace_bytes': (_c_sz, [_c_int] * 4),
     'ctcasr_ctc_beam_decode': (_c_int, [_c_p, _c_p] + [_c_int] * 6 + [_c_p] * 4 + [_c_sz, _c_p]),
+    'ctcasr_ctc_align_workspace_bytes': (_c_sz, [_c_int] * 4),
+    'ctcasr_ctc_align': (_c_int, [_c_p] * 4 + [_c_int] * 5 + [_c_p] * 5 + [_c_sz, _c_p]),
     'ctcasr_rnn_reserve_bytes': (_c_sz, [_c_int] * 4),
     'ctcasr_rnn_workspace_bytes': (_c_sz, [_c_int] * 4),
     'ctcasr_rnn_persistent_supported': (_c_int, [_c_int] * 4),
@@ -333,6 +335,41 @@ def ctc_beam_decode(logits, seq_len, beam_width, blank=None, normalization='max'
     if bool((out_len < 0).any()):
         raise CtcAsrError('ctc_beam_decode: prefix-tree pool exhausted')
     return out, out_len, logp
+
+
+def ctc_align_workspace_bytes(num_steps, batch, classes, max_label_len):
+    return load().ctcasr_ctc_align_workspace_bytes(num_steps, batch, classes, max_label_len)
+
+
+@_on_tensor_device
+def ctc_align(logits, labels, label_offsets, seq_len, max_label_len, blank=None, path=None,
+              score=None, frame_logp=None, status=None, workspace=None):
+    """CTC forced alignment (Viterbi).  logits f32[T,B,C]; labels/label_offsets/seq_len int32
+    device tensors, as `ctc_loss_fwd_bwd` takes them.  Returns (path i32[B,T], score f32[B],
+    frame_logp f32[B,T], status i32[B]); ``frame_logp=False`` skips that output (returns None).
+    A non-zero status is data, not an error: the caller reads it."""
+    num_steps, batch, classes = logits.shape
+    blank = classes - 1 if blank is None else blank
+    dev = logits.device
+    if path is None:
+        path = torch.empty((batch, num_steps), dtype=torch.int32, device=dev)
+    score = torch.empty(batch, dtype=torch.float32, device=dev) if score is None else score
+    if frame_logp is None:
+        frame_logp = torch.empty((batch, num_steps), dtype=torch.float32, device=dev)
+    elif frame_logp is False:
+        frame_logp = None
+    status = torch.empty(batch, dtype=torch.int32, device=dev) if status is None else status
+    if workspace is None:
+        workspace = _workspace(ctc_align_workspace_bytes(num_steps, batch, classes,
+                                                         max_label_len), dev)
+    _check(load().ctcasr_ctc_align(
+        _dev(logits, name='logits'), _dev(labels, torch.int32, 'labels'),
+        _dev(label_offsets, torch.int32, 'label_offsets'), _dev(seq_len, torch.int32, 'seq_len'),
+        num_steps, batch, classes, blank, int(max_label_len), _dev(path, torch.int32, 'path'),
+        _dev(score, name='score'), _dev(frame_logp, name='frame_logp'),
+        _dev(status, torch.int32, 'status'), _dev(workspace, torch.uint8, 'workspace'),
+        workspace.numel(), _stream()), 'ctc_align')
+    return path, score, frame_logp, status
 
 
 def rnn_reserve_bytes(cell, num_steps, batch, hidden):

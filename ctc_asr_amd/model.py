@@ -1175,6 +1175,16 @@ class CTCModel:
             self.check_status(status)
         return per_utt.mean()
 
+    def align_fn(self, logits, seq_len, labels):
+        """CTC forced alignment of ``labels`` (the forms `loss_fn` takes) to ``logits``: returns
+        (path i32[B, T], score f32[B], frame_logp f32[B, T], status i32[B]) as device tensors
+        (``hip.ctc_align``).  Raises nothing for a non-zero status: the caller reads it."""
+        if isinstance(labels, tuple) and len(labels) == 4 and torch.is_tensor(labels[0]):
+            flat, offsets, max_len, _ = labels
+        else:
+            flat, offsets, max_len, _ = self.pack_labels(labels, self.device)
+        return hip.ctc_align(logits, flat, offsets, seq_len, max_len)
+
     @staticmethod
     def check_status(status):
         bad = status.cpu().numpy()

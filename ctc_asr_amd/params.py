@@ -210,6 +210,14 @@ FLAGS.define('bool', 'allow_vram_growth', True, 'Accepted for compatibility (no 
 FLAGS.define('bool', 'dev', False, 'evaluate.py: score dev.csv instead of test.csv.')
 FLAGS.define('string', 'input', '', 'predict.py: WAV file to decode.')
 
+# Forced alignment (no counterpart in the reference): word timestamps in predict.py, and the
+# corpus aligner `python -m ctc_asr_amd.align`.
+FLAGS.define('bool', 'timestamps', False, "predict.py: add 'words' (start / end / confidence) "
+             'by aligning the decoded text to the logits.')
+FLAGS.define('string', 'align_csv', '', 'align.py: path;label;length manifest to align, in file '
+             'order.')
+FLAGS.define('string', 'align_output', '', 'align.py: JSON-lines output, one line per manifest row.')
+
 # ####### Constants (asr/params.py:138-155). #########
 NP_FLOAT = np.float32
 

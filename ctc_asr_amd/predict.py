@@ -1,5 +1,7 @@
 """Transcribe one WAV file: ``python -m ctc_asr_amd.predict --input file.wav``
-(counterpart of ``asr/predict.py:44-67``; returns / prints {'decoded', 'plaintext'})."""
+(counterpart of ``asr/predict.py:44-67``; returns / prints {'decoded', 'plaintext'}).
+``--timestamps`` adds ``'words'``: the decoded text aligned to the same logits
+(`CTCModel.align_fn`), one ``{'word', 'start', 'end', 'confidence'}`` per word."""
 
 import os
 import sys
@@ -7,18 +9,27 @@ import sys
 import numpy as np
 import torch
 
-from ctc_asr_amd import storage
+from ctc_asr_amd import alignment, storage
 from ctc_asr_amd.input_functions import features_from_pcm, read_wav
 from ctc_asr_amd.model import CTCModel, ModelConfig
 from ctc_asr_amd.params import FLAGS
 
 
-def predict(model, wav_path):
+def predict(model, wav_path, timestamps=False):
     feats, lengths = features_from_pcm([read_wav(wav_path)], model.device)
     logits, seq_len = model.inference_fn(feats, lengths, training=False)
     model.check_rnn_error()
     decoded, plaintext, _ = model.decode_fn(logits, seq_len, None)
-    return {'decoded': np.array(decoded[0], dtype=np.int32), 'plaintext': plaintext[0]}
+    result = {'decoded': np.array(decoded[0], dtype=np.int32), 'plaintext': plaintext[0]}
+    if timestamps:
+        ids = [v for v in decoded[0] if v != 0]     # (id 0 renders as '' and is no label)
+        path, _, frame_logp, _ = model.align_fn(logits, seq_len, [ids])
+        # a decode the alignment cannot place (status != 0) leaves a path of -1: no words
+        result['words'] = alignment.segments(
+            path[0].cpu().numpy(), ids,
+            alignment.frame_seconds(model.cfg, FLAGS.features_drop_every_second_frame),
+            frame_logp[0].cpu().numpy())
+    return result
 
 
 def main(argv=None):
@@ -33,7 +44,7 @@ def main(argv=None):
         raise SystemExit('No checkpoint found in {}.'.format(FLAGS.train_dir))
     storage.restore_checkpoint(latest, model)
     print('Inputs: {}'.format(FLAGS.input))
-    print(predict(model, FLAGS.input))
+    print(predict(model, FLAGS.input, FLAGS.timestamps))
     return 0
 
 

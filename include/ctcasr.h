@@ -112,6 +112,31 @@ int ctcasr_ctc_beam_decode(const float *logits, const int32_t *seq_len, int T, i
                            int32_t *out_len, float *logp, void *workspace,
                            size_t workspace_bytes, ctcasr_stream_t stream);
 
+/* ---- K11: CTC forced alignment ----------------------------------------------------------------
+ * The Viterbi (max-sum) form of K9's alpha recursion: the single best alignment of each
+ * utterance's label to its frames (no counterpart in the reference).  Inputs and status codes
+ * are those of ctcasr_ctc_loss_fwd_bwd; blank is any id in [0, C).  Per utterance, with L labels
+ * and S = 2L + 1 extended states, the lattice runs in fp64 and ends in S - 1 or (L > 0) S - 2.
+ * Tie rule: predecessors are compared with strict > in the order s, s - 1, s - 2, and S - 1 wins
+ * over S - 2 at the end, so equal scores keep the smaller move; results are bit-reproducible.
+ *   path       int32 [B, T]: the state s in [0, S) of the best path at frame t < seq_len[b]
+ *              (even s: blank, odd s: label position (s - 1) / 2); -1 for t >= seq_len[b]
+ *   score      [B]   log-probability of the best path (0 for seq_len 0 and L = 0)
+ *   frame_logp [B, T] log-softmax of the class the path emits at frame t, 0 for t >= seq_len[b];
+ *              may be NULL
+ *   status     int32 [B]: 0 ok; 1 seq_len < L + adjacent repeats (no alignment exists); 2 label
+ *              id out of range / the blank, seq_len > T or < 0, or the row is longer than
+ *              max_label_len; 3 a non-finite logit in the first seq_len frames.  Non-zero: score
+ *              -inf (NaN for 3), path -1 and frame_logp 0 for the whole row.
+ * Every output is fully written.  2 * max_label_len + 1 <= 1152, C <= 64 (else
+ * CTCASR_ERR_UNSUPPORTED).  Workspace: ctcasr_ctc_align_workspace_bytes(T, B, C,
+ * max_label_len). */
+size_t ctcasr_ctc_align_workspace_bytes(int T, int B, int C, int max_label_len);
+int ctcasr_ctc_align(const float *logits, const int32_t *labels, const int32_t *label_offsets,
+                     const int32_t *seq_len, int T, int B, int C, int blank, int max_label_len,
+                     int32_t *path, float *score, float *frame_logp, int32_t *status,
+                     void *workspace, size_t workspace_bytes, ctcasr_stream_t stream);
+
 /* ---- K4/K5: recurrence of one bidirectional RNN layer ----------------------------------------
  * Replaces the time loop of tfc.cudnn_rnn.Cudnn{LSTM,GRU,RNNRelu,RNNTanh}(direction=
  * 'bidirectional') (asr/model.py:194-215) and of stack_bidirectional_dynamic_rnn over
