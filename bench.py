@@ -14,17 +14,26 @@ Workload (``--workload``, default ``c3``): BASELINE.json configs[2] - DS2, 2 con
 5 x BiLSTM-1024, batch 32 per GPU, 10 s utterances (999 feature frames -> T' = 500), fp32.  It is
 the per-GPU unit of configs[3] (global batch 256 on 8 GPUs), so the N = 1/2/4/8 curve is weak
 scaling of exactly this workload.  ``--workload c2`` is configs[1] (2 x BiLSTM-1024, batch 16);
-at N = 1 the default run measures it too and reports it under ``other_workloads``.
+at N = 1 a ``--full`` run measures it too and reports it under ``other_workloads``.
 
 One process per GPU.  Started without a torchrun environment and with ``--gpus N`` > 1, this
 script re-executes itself under ``torch.distributed.run`` with N ranks (backend nccl = RCCL) and
 exits non-zero if fewer than N GPUs are visible - it never silently falls back to one GPU.
 
+A plain run does what the headline figure needs and nothing else: set up, warm up, time the K
+steps, write ``--dump-outputs`` if asked, print the line.  ``--full`` adds everything else the
+benchmark measures or checks, after the headline measurement: at N = 1 the other workloads and
+GEMM arithmetics (C2, C3 without the split / fp16 forms, C5, C5 from disk, the reference's own
+models), the parity probe against the float64 oracle and the CPU baseline; with ``--workload c5``
+the beam-search decode and the from-disk epoch; at N > 1 the stubbed step that prices the
+all-reduce.  A plain run's line has the same headline fields as a full run's.
+
 Rank 0 prints ONE JSON line (schema in the task contract) that also carries
   "roofline":     the dominant kernel (the recurrent time-step kernel) against its roof, from
                   HIP events recorded by the library around every launch in the timed region;
                   ``traffic`` comes from the committed rocprofv3 PMC summary
-                  (profiles/pmc_traffic.json, written by tools/make_profile_md.py), and
+                  (profiles/pmc_traffic.json, written by tools/make_profile_md.py), and, with
+                  ``--full``,
   "cpu_baseline": the same graph in stock torch CPU operators (oracle/torch_ref.py, kind
                   "port" - the reference's TensorFlow cannot run offline) on the host cores,
                   rank 0, N = 1 only, SAME batch as the GPU line, bounded sample.
@@ -727,12 +736,13 @@ def c5_bucket_sequence(batch, count, seed=1234, pool=4096, num_buckets=96):
     return out
 
 
-def measure_c5(args, rank, local_rank, world, dump=None):
+def measure_c5(args, rank, local_rank, world, dump=None, decode=True):
     """BASELINE.json configs[4] on this rank's GPU: training over a fixed seeded sequence of
     ``args.steps`` bucketed mixed-length batches (one untimed pass to warm the allocator over the
-    sequence's shapes, one timed pass), then evaluation-style decoding of the same batches with
-    the beam search at width 64 (logits of all batches decoded in grouped launches).  ``dump``:
-    directory for `dump_outputs` of the timed pass's last training step (rank 0)."""
+    sequence's shapes, one timed pass), then - ``decode`` - evaluation-style decoding of the same
+    batches with the beam search at width 64 (logits of all batches decoded in grouped launches,
+    reported under ``decode``).  ``dump``: directory for `dump_outputs` of the timed pass's last
+    training step (rank 0)."""
     from ctc_asr_amd import hip
     from ctc_asr_amd.engine import Trainer
     from ctc_asr_amd.labels import encode
@@ -825,8 +835,9 @@ def measure_c5(args, rank, local_rank, world, dump=None):
                 pending = []
         return t_fwd, t_dec, decoded_utts
 
-    decode_pass()                       # warm-up (tree pools, shapes)
-    t_fwd, t_dec, decoded_utts = decode_pass()
+    if decode:
+        decode_pass()                   # warm-up (tree pools, shapes)
+        t_fwd, t_dec, decoded_utts = decode_pass()
     model.check_rnn_error()
 
     result = None
@@ -876,7 +887,8 @@ def measure_c5(args, rank, local_rank, world, dump=None):
                 'seconds_forward_incl_features': round(t_fwd, 4),
                 'value_incl_forward': round(audio_s / (t_dec + t_fwd), 2),
                 'note': 'evaluation path: eval-mode forward per batch, logits kept, beam search '
-                        'in grouped launches (CTCModel.decode_many), host conversion included'},
+                        'in grouped launches (CTCModel.decode_many), host conversion included'}
+            if decode else None,
             'roofline': {
                 'kernel': 'prnn_bwd{}_kernel<LSTM> over the whole bucket sequence (launches of '
                           'T\'/2 steps x 2 directions, batch {})'.format(
@@ -900,6 +912,8 @@ def measure_c5(args, rank, local_rank, world, dump=None):
                                'achieved': round(rnn_flops / (fwd_ms * 1e-3) / 1e12, 2)
                                if fwd_ms else None}},
         }
+        if not decode:
+            del result['decode']
     if result is not None and 'mean_time_steps_per_launch' in result.get('roofline', {}):
         # (PMC passes over this very bucket sequence: mean bytes per launch, mean steps per launch)
         result['roofline'].update(pmc_traffic('c5', 'rnn_bwd',
@@ -1114,7 +1128,8 @@ def merge_release_modes(legs, stub):
     """N > 1: fold the measurements of the release modes ({'held': line, 'early': line}) and of
     the stubbed step into ONE result line - the better mode's line, with every mode's step time,
     per-rank spread and exposed all-reduce time (= its step minus the stubbed step) under
-    ``allreduce.modes``."""
+    ``allreduce.modes``.  ``stub`` None (a plain run measures no stubbed step): the same line
+    without the exposed all-reduce figures."""
     valid = [m for m in legs if 'failed' not in legs[m]['allreduce']] or list(legs)
     best = min(valid, key=lambda m: legs[m]['ms_per_step'])
     result = legs[best]
@@ -1123,17 +1138,20 @@ def merge_release_modes(legs, stub):
             'failed': leg['allreduce'].get('failed'),
             'mode': leg['allreduce']['mode'],     # early falls back to held at H = 2048
             'launches_per_step': leg['allreduce']['launches_per_step'],
-            'rank_ms_per_step': leg['allreduce']['rank_ms_per_step'],
-            'exposed_allreduce_ms': round(leg['ms_per_step'] - stub['ms_per_step'], 3),
-            'exposed_allreduce_frac_of_step': round(
-                (leg['ms_per_step'] - stub['ms_per_step']) / leg['ms_per_step'], 4)}
+            'rank_ms_per_step': leg['allreduce']['rank_ms_per_step']}
         for m, leg in legs.items()}
     result['allreduce']['chosen'] = best
-    result['allreduce']['stubbed_ms_per_step'] = stub['ms_per_step']
-    result['allreduce']['exposed_allreduce_ms'] = round(
-        result['ms_per_step'] - stub['ms_per_step'], 3)
-    result['allreduce']['exposed_allreduce_frac_of_step'] = round(
-        (result['ms_per_step'] - stub['ms_per_step']) / result['ms_per_step'], 4)
+    if stub is not None:
+        for m, leg in legs.items():
+            result['allreduce']['modes'][m].update({
+                'exposed_allreduce_ms': round(leg['ms_per_step'] - stub['ms_per_step'], 3),
+                'exposed_allreduce_frac_of_step': round(
+                    (leg['ms_per_step'] - stub['ms_per_step']) / leg['ms_per_step'], 4)})
+        result['allreduce']['stubbed_ms_per_step'] = stub['ms_per_step']
+        result['allreduce']['exposed_allreduce_ms'] = round(
+            result['ms_per_step'] - stub['ms_per_step'], 3)
+        result['allreduce']['exposed_allreduce_frac_of_step'] = round(
+            (result['ms_per_step'] - stub['ms_per_step']) / result['ms_per_step'], 4)
     # (a mode in which any rank reported an error - e.g. a recurrence time-out under the early
     # release - is never the chosen one while another mode ran clean)
     result['allreduce']['choice_rule'] = 'fastest mode without a failed rank'
@@ -1141,7 +1159,7 @@ def merge_release_modes(legs, stub):
     front = {}
     for key, val in result.items():
         front[key] = val
-        if key == 'value':
+        if key == 'value' and stub is not None:
             front['exposed_allreduce_frac_of_step'] = \
                 result['allreduce']['exposed_allreduce_frac_of_step']
     return front
@@ -1174,21 +1192,27 @@ def main():
     ap.add_argument('--steps', type=int, default=8)
     ap.add_argument('--warmup', type=int, default=2)
     ap.add_argument('--workload', default='c3', choices=sorted(WORKLOADS))
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline measurement, everything else the benchmark measures '
+                         'or checks: other workloads and arithmetics, parity probe, CPU baseline '
+                         '(N = 1), C5\'s decode and from-disk epoch, the stubbed step (N > 1)')
+    ap.add_argument('--no-cpu-baseline', action='store_true',
+                    help='skip the CPU baseline of a --full N = 1 run')
     ap.add_argument('--no-other-workloads', action='store_true',
-                    help='skip the secondary C2 measurement of the default N = 1 run')
+                    help='skip the secondary measurements (C2, C3 variants, C5, the reference\'s '
+                         'models) of a --full N = 1 run')
     ap.add_argument('--leg-budget', type=float, default=900.0,
                     help='N > 1: seconds of wall clock after which no further release-mode leg is '
-                         'started (the stubbed leg always runs)')
+                         'started (the stubbed leg of a --full run always runs)')
     ap.add_argument('--no-reference-models', action='store_true',
                     help='skip ref_default / ref_best (the reference\'s own configurations) among '
-                         'the other workloads of the default N = 1 run')
+                         'the other workloads of a --full N = 1 run')
     ap.add_argument('--dropout', type=float, default=0.1,
                     help='dense_dropout_rate (reference default 0.1)')
     ap.add_argument('--rnn-bwd-whole-chip', action='store_true',
                     help='persistent backward recurrence on all 256 CUs (default: 128)')
     ap.add_argument('--no-parity-probe', action='store_true',
-                    help='skip the CTC-loss / logits delta against the oracle (N = 1)')
+                    help='skip the CTC-loss / logits delta against the oracle (--full, N = 1)')
     ap.add_argument('--parity-probe', default='full', choices=('full', 'small'),
                     help='shape of the parity probe: the timed workload\'s own (default) or '
                          'batch 4 x T\' = 100')
@@ -1203,7 +1227,7 @@ def main():
                          'both release modes, what ring kernels beside the persistent recurrences '
                          'cost; reported under `collective_stand_in`')
     ap.add_argument('--c5-batches', type=int, default=24,
-                    help='bucketed batches in the C5 sequence of the default N = 1 run')
+                    help='bucketed batches in the C5 sequence of a --full N = 1 run')
     ap.add_argument('--dump-outputs', metavar='DIR', default=None,
                     help='write what the last timed step of the headline workload computed as '
                          'DIR/<name>.npy (bench.dump_outputs; N > 1: rank 0, first release mode)')
@@ -1258,9 +1282,10 @@ def main():
 
     other, exit_code = {}, 0
     if args.workload == 'c5':
-        result = measure_c5(args, rank, local_rank, world, dump=args.dump_outputs)
+        result = measure_c5(args, rank, local_rank, world, dump=args.dump_outputs,
+                            decode=args.full)
         cfg = frames = batch = seconds = None
-        if world == 1:
+        if world == 1 and args.full:
             try:
                 other['c5_from_disk'] = measure_c5_from_disk(args, local_rank)
             except Exception as err:        # noqa: BLE001
@@ -1271,8 +1296,8 @@ def main():
     else:
         # N > 1: the driver runs this once per N, so the run itself is the experiment - both
         # release modes of the gradient buckets back to back (each: warm-up + K timed steps under
-        # the contract's protocol), then the same step with the collectives stubbed out.  `value`
-        # is the better mode's; everything measured is in `allreduce.modes`.
+        # the contract's protocol), then - --full - the same step with the collectives stubbed
+        # out.  `value` is the better mode's; everything measured is in `allreduce.modes`.
         forced = os.environ.get('CTCASR_ALLREDUCE_EARLY')
         legs, skipped = {}, []
         for mode in (('early',) if forced == '1' else ('held',) if forced == '0'
@@ -1288,7 +1313,8 @@ def main():
             legs[mode], shape = measure(args.workload, args, rank, local_rank, world,
                                         allreduce_early=(mode == 'early'),
                                         dump=None if legs else args.dump_outputs)
-        stub, _ = measure(args.workload, args, rank, local_rank, world, reduce=False)
+        stub = measure(args.workload, args, rank, local_rank, world, reduce=False)[0] \
+            if args.full else None
         cfg, frames, batch, seconds = shape
         result = merge_release_modes(legs, stub) if rank == 0 else None
         if rank == 0 and skipped:
@@ -1297,7 +1323,7 @@ def main():
                     args.leg_budget) for m in skipped}
         if rank == 0 and 'failed' in result['allreduce']:
             exit_code = 4                # every measured mode failed: the line says why
-    if world == 1 and args.workload == 'c3' and not args.no_other_workloads:
+    if world == 1 and args.workload == 'c3' and args.full and not args.no_other_workloads:
         # (secondary measurements: a failure here is reported in the line, it does not take the
         # headline measurement down with it)
         try:
@@ -1331,7 +1357,7 @@ def main():
             other['c5_from_disk'] = measure_c5_from_disk(args, local_rank)
         except Exception as err:        # noqa: BLE001
             other['c5_from_disk'] = {'error': '{}: {}'.format(type(err).__name__, err)}
-    if world == 1 and args.workload == 'c3' and not args.no_other_workloads and \
+    if world == 1 and args.workload == 'c3' and args.full and not args.no_other_workloads and \
             not args.no_reference_models:
         # the reference's own configurations: its flag defaults (asr/params.py:43-50: 3 conv + 4 x
         # ReLU-RNN-2048, batch 16) and its best published model (testruns.md: 3 conv + 4 x
@@ -1391,7 +1417,7 @@ def main():
                 result['devices_shared'] = True      # not a measurement: plumbing check only
         if other:
             result['other_workloads'] = other
-        if world == 1 and not args.no_parity_probe:
+        if world == 1 and args.full and not args.no_parity_probe:
             # BASELINE.json's metric, second half: CTC loss (and logits) delta vs the oracle, AT
             # THE SHAPE THE NUMBER ABOVE WAS MEASURED ON (C3: 5 layers, batch 32, 999 frames ->
             # T' = 500), once per GEMM arithmetic; the small shape only if the host cannot finish
@@ -1427,7 +1453,7 @@ def main():
                                                                        or 1.0)) or
                         variant['logits_max_abs_delta'] > 1e-3):
                     exit_code = 3                    # the line is printed, the run fails
-        if world == 1 and not args.no_cpu_baseline and args.workload != 'c5':
+        if world == 1 and args.full and not args.no_cpu_baseline and args.workload != 'c5':
             result['cpu_baseline'] = cpu_baseline(workload_cfg_kwargs(args.workload), batch,
                                                   seconds, frames)
             if result['cpu_baseline']['value']:

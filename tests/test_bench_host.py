@@ -81,6 +81,29 @@ def test_release_modes_are_folded_into_one_line():
     assert 'failed' not in line['allreduce']
 
 
+def test_release_modes_fold_without_a_stubbed_step():
+    """A plain N > 1 run (no --full) measures no stubbed step: the same choice of mode and the
+    same per-mode figures, without the exposed all-reduce time that needs the stub."""
+    sys.path.insert(0, ROOT)
+    import bench
+
+    def leg(mode, ms, value):
+        return {'metric': 'm', 'value': value, 'ms_per_step': ms, 'allreduce': {
+            'mode': mode, 'launches_per_step': 9.0,
+            'rank_ms_per_step': {'min': ms - 0.5, 'max': ms, 'all': [ms - 0.5, ms]}}}
+
+    line = bench.merge_release_modes({'held': leg('held', 101.0, 6336.6),
+                                      'early': leg('early', 99.5, 6432.2)}, None)
+    assert list(line) == ['metric', 'value', 'ms_per_step', 'allreduce']
+    assert line['value'] == 6432.2 and line['allreduce']['chosen'] == 'early'
+    assert line['allreduce']['choice_rule'] == 'fastest mode without a failed rank'
+    modes = line['allreduce']['modes']
+    assert set(modes) == {'held', 'early'}
+    assert modes['held']['ms_per_step'] == 101.0 and modes['early']['launches_per_step'] == 9.0
+    assert not any('exposed' in key for mode in modes.values() for key in mode)
+    assert not any(key.startswith(('exposed', 'stubbed')) for key in line['allreduce'])
+
+
 def test_c5_bucket_sequence_is_fixed_and_bucketed():
     """The C5 workload's batches: seeded (the same sequence every run), every batch from ONE
     bucket (its utterances differ by well under a second), lengths inside the corpus filter."""

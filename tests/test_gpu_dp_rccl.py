@@ -205,12 +205,12 @@ def test_nccl_world_size_one_reducer_forced_on_both_release_modes():
 
 
 def test_bench_two_ranks_on_one_gpu_report_both_release_modes():
-    """bench.py --gpus 2 as the driver starts it (two processes, torchrun environment), here with
-    both ranks on the one GPU and gloo as the transport (tools/two_rank_one_gpu.py): the line
-    must carry both release modes, the stubbed step and the per-rank spread."""
+    """bench.py --gpus 2 --full as the driver starts it (two processes, torchrun environment),
+    here with both ranks on the one GPU and gloo as the transport (tools/two_rank_one_gpu.py): the
+    line must carry both release modes, the stubbed step and the per-rank spread."""
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     run = subprocess.run([sys.executable, os.path.join(root, 'tools', 'two_rank_one_gpu.py'),
-                          '--workload', 'tiny', '--steps', '2', '--warmup', '1'],
+                          '--workload', 'tiny', '--steps', '2', '--warmup', '1', '--full'],
                          capture_output=True, text=True, timeout=900)
     assert run.returncode == 0, run.stderr[-3000:]
     lines = [ln for ln in run.stdout.splitlines() if ln.startswith('{')]
