@@ -298,9 +298,21 @@ def ctc_loss_fwd_bwd(logits, labels, label_offsets, seq_len, max_label_len, blan
     return loss, grad, status
 
 
+def _decode_shape(what, logits, seq_len):
+    """(T, B, C) of a decoder's ``logits``; refuses anything but [T, B, C] with one length per
+    utterance - the kernels index ``seq_len`` by the batch of ``logits``."""
+    if logits.dim() != 3:
+        raise CtcAsrError('{}: logits must be [T, B, C] (got {} dimensions).'
+                          .format(what, logits.dim()))
+    if seq_len.numel() != logits.shape[1]:
+        raise CtcAsrError('{}: seq_len holds {} lengths for a batch of {}.'
+                          .format(what, seq_len.numel(), logits.shape[1]))
+    return logits.shape
+
+
 @_on_tensor_device
 def ctc_greedy_decode(logits, seq_len, blank=None, out=None, out_len=None):
-    num_steps, batch, classes = logits.shape
+    num_steps, batch, classes = _decode_shape('ctc_greedy_decode', logits, seq_len)
     blank = classes - 1 if blank is None else blank
     dev = logits.device
     out = torch.empty((batch, num_steps), dtype=torch.int32, device=dev) if out is None else out
@@ -318,7 +330,7 @@ def ctc_beam_workspace_bytes(num_steps, batch, classes, beam_width):
 
 @_on_tensor_device
 def ctc_beam_decode(logits, seq_len, beam_width, blank=None, normalization='max'):
-    num_steps, batch, classes = logits.shape
+    num_steps, batch, classes = _decode_shape('ctc_beam_decode', logits, seq_len)
     blank = classes - 1 if blank is None else blank
     dev = logits.device
     out = torch.empty((batch, num_steps), dtype=torch.int32, device=dev)

@@ -115,6 +115,7 @@ int oracle_ctc_loss(const float *logits, int T, int B, int C, const int *labels,
 typedef struct {
     int parent, label;
     int first_child;          /* index of child for label 0, children are allocated as a block */
+    int entered;              /* this prefix has been in the beam at least once */
     float o_total, o_blank, o_label;
     float n_total, n_blank, n_label;
 } node_t;
@@ -171,7 +172,7 @@ static int ensure_children(pool_t *p, int idx, int C) {
     p->n[idx].first_child = p->count;
     for (int c = 0; c < C; ++c) {
         node_t *ch = &p->n[p->count + c];
-        ch->parent = idx; ch->label = c; ch->first_child = -1;
+        ch->parent = idx; ch->label = c; ch->first_child = -1; ch->entered = 0;
         ch->o_total = ch->o_blank = ch->o_label = -INFINITY;
         ch->n_total = ch->n_blank = ch->n_label = -INFINITY;
     }
@@ -180,10 +181,14 @@ static int ensure_children(pool_t *p, int idx, int C) {
 }
 
 /* norm_mode 0: subtract the frame maximum (TensorFlow 1.12); 1: full log-softmax (TF >= 1.14).
- * out[B, T] (row padded with 0), out_len[B], logp[B] = total of the winning prefix. */
-int oracle_ctc_beam_decode(const float *logits, int T, int B, int C, const int *seq_len,
-                           int beam_width, int blank, int norm_mode, int *out, int *out_len,
-                           float *logp) {
+ * out[B, T] (row padded with 0), out_len[B], logp[B] = total of the winning prefix.
+ * nodes[B] (may be NULL): the prefixes that were in the beam at least once, the root included -
+ * what an implementation that creates a tree node when a prefix first enters the beam has
+ * created by the end (this one allocates a branch's children as a block, so its own pool count
+ * says nothing about that). */
+static int beam_decode(const float *logits, int T, int B, int C, const int *seq_len,
+                       int beam_width, int blank, int norm_mode, int *out, int *out_len,
+                       float *logp, long long *nodes) {
     float *x = (float *)malloc(sizeof(float) * C);
     int *heap = (int *)malloc(sizeof(int) * (beam_width + 1));
     int *branches = (int *)malloc(sizeof(int) * (beam_width + 1));
@@ -192,7 +197,8 @@ int oracle_ctc_beam_decode(const float *logits, int T, int B, int C, const int *
         pool.cap = 1 + C * 64; pool.count = 1;
         pool.n = (node_t *)malloc(sizeof(node_t) * (size_t)pool.cap);
         node_t *root = &pool.n[0];
-        root->parent = -1; root->label = -1; root->first_child = -1;
+        root->parent = -1; root->label = -1; root->first_child = -1; root->entered = 1;
+        long long entered = 1;
         root->o_total = root->o_blank = root->o_label = -INFINITY;
         root->n_total = 0.f; root->n_blank = 0.f; root->n_label = -INFINITY;
         int nleaves = 1; heap[0] = 0;
@@ -253,6 +259,7 @@ int oracle_ctc_beam_decode(const float *logits, int T, int B, int C, const int *
                     int cand = ch->n_total != -INFINITY &&
                                (nleaves < beam_width || ch->n_total > pool.n[heap[0]].n_total);
                     if (cand) {
+                        if (!ch->entered) { ch->entered = 1; ++entered; }
                         if (nleaves == beam_width) {
                             node_t *bot = &pool.n[heap[0]];
                             bot->n_total = bot->n_blank = bot->n_label = -INFINITY;
@@ -279,8 +286,24 @@ int oracle_ctc_beam_decode(const float *logits, int T, int B, int C, const int *
         int k = n;
         for (int i = best; pool.n[i].parent >= 0; i = pool.n[i].parent) out[(size_t)b * T + --k] = pool.n[i].label;
         logp[b] = pool.n[best].n_total;
+        if (nodes) nodes[b] = entered;
         free(pool.n);
     }
     free(x); free(heap); free(branches);
     return 0;
+}
+
+int oracle_ctc_beam_decode(const float *logits, int T, int B, int C, const int *seq_len,
+                           int beam_width, int blank, int norm_mode, int *out, int *out_len,
+                           float *logp) {
+    return beam_decode(logits, T, B, C, seq_len, beam_width, blank, norm_mode, out, out_len, logp,
+                       NULL);
+}
+
+/* The same search; nodes[B] as described above. */
+int oracle_ctc_beam_decode_nodes(const float *logits, int T, int B, int C, const int *seq_len,
+                                 int beam_width, int blank, int norm_mode, int *out, int *out_len,
+                                 float *logp, long long *nodes) {
+    return beam_decode(logits, T, B, C, seq_len, beam_width, blank, norm_mode, out, out_len, logp,
+                       nodes);
 }

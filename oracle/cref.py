@@ -28,8 +28,7 @@ def build(force=False):
 def lib():
     global _lib
     if _lib is None:
-        if not os.path.exists(_LIB_PATH):
-            build()
+        build()      # (no-op when the library is newer than its source)
         _lib = ctypes.CDLL(_LIB_PATH)
     return _lib
 
@@ -66,8 +65,10 @@ def ctc_loss(logits, labels, seq_len, blank=None):
     return loss, grad, status
 
 
-def beam_search_decode(logits, seq_len, beam_width, blank=None, normalization='max'):
-    """(list of B label lists, logp f32[B]) — see ``oracle_ctc_beam_decode``."""
+def beam_search_decode(logits, seq_len, beam_width, blank=None, normalization='max',
+                       return_nodes=False):
+    """(list of B label lists, logp f32[B]) — see ``oracle_ctc_beam_decode``.  With
+    ``return_nodes`` a third value: i64[B], the prefixes that were in the beam at least once."""
     logits = np.ascontiguousarray(logits, dtype=np.float32)
     num_steps, batch, num_classes = logits.shape
     blank = num_classes - 1 if blank is None else blank
@@ -76,10 +77,12 @@ def beam_search_decode(logits, seq_len, beam_width, blank=None, normalization='m
     out_len = np.zeros(batch, dtype=np.int32)
     logp = np.zeros(batch, dtype=np.float32)
     mode = {'max': 0, 'log_softmax': 1}[normalization]
-    rc = lib().oracle_ctc_beam_decode(_ptr(logits, ctypes.c_float), num_steps, batch, num_classes,
-                                      _ptr(seq_len, ctypes.c_int), int(beam_width), blank, mode,
-                                      _ptr(out, ctypes.c_int), _ptr(out_len, ctypes.c_int),
-                                      _ptr(logp, ctypes.c_float))
+    nodes = np.zeros(batch, dtype=np.int64)
+    rc = lib().oracle_ctc_beam_decode_nodes(
+        _ptr(logits, ctypes.c_float), num_steps, batch, num_classes, _ptr(seq_len, ctypes.c_int),
+        int(beam_width), blank, mode, _ptr(out, ctypes.c_int), _ptr(out_len, ctypes.c_int),
+        _ptr(logp, ctypes.c_float), _ptr(nodes, ctypes.c_longlong))
     if rc != 0:
         raise RuntimeError('oracle_ctc_beam_decode failed')
-    return [out[b, :out_len[b]].tolist() for b in range(batch)], logp
+    paths = [out[b, :out_len[b]].tolist() for b in range(batch)]
+    return (paths, logp, nodes) if return_nodes else (paths, logp)

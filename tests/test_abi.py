@@ -128,6 +128,21 @@ def test_probe_builds_cannot_stand_in_for_the_product(lib, monkeypatch):
                 pass
 
 
+def test_decoders_refuse_a_seq_len_that_does_not_match_the_batch():
+    """Checked by the wrappers before anything else (the kernels index `seq_len` by the batch
+    of `logits`), so it shows without a GPU; the message names both numbers."""
+    import torch
+    from ctc_asr_amd import hip
+    logits = torch.zeros(6, 5, 29)
+    for call in (lambda x, n: hip.ctc_beam_decode(x, n, 8), hip.ctc_greedy_decode):
+        with pytest.raises(hip.CtcAsrError, match='4 lengths for a batch of 5'):
+            call(logits, torch.zeros(4, dtype=torch.int32))
+        with pytest.raises(hip.CtcAsrError, match='6 lengths for a batch of 5'):
+            call(logits, torch.zeros(6, dtype=torch.int32))
+        with pytest.raises(hip.CtcAsrError, match='2 dimensions'):
+            call(logits.reshape(30, 29), torch.zeros(5, dtype=torch.int32))
+
+
 def test_missing_library_fails_loudly(tmp_path):
     from ctc_asr_amd import hip
     with pytest.raises(hip.CtcAsrError):

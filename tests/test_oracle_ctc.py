@@ -105,6 +105,65 @@ def test_c_beam_search_equals_numpy_beam_search():
             assert p1 == p2 and np.allclose(s1, s2, atol=1e-5)
 
 
+def _edge_inputs():
+    """(logits [T, B, C], seq_len, blank) of the input classes the GPU beam search is held to in
+    test_gpu_beam_edges.py: rows of length 0 and 1, T = 1, the blank at 0 and mid, C = 2 with
+    either blank, C = 64, and -inf entries (a class for all frames, on alternate frames, the
+    blank on some frames)."""
+    rng = np.random.default_rng(12)
+    cases = []
+    for steps, classes, blank in ((12, 7, 0), (12, 7, 3), (1, 7, 6), (10, 2, 0), (10, 2, 1),
+                                  (12, 64, 63), (12, 64, 0)):
+        logits = (rng.normal(size=(steps, 4, classes)) * 2).astype(np.float32)
+        cases.append((logits, [steps, 0, 1, max(1, steps - 3)], blank))
+    for kind in range(3):
+        logits = (rng.normal(size=(14, 3, 7)) * 2).astype(np.float32)
+        if kind == 0:
+            logits[:, :, 2] = -np.inf
+        elif kind == 1:
+            logits[0::2, :, 2] = -np.inf
+            logits[1::2, :, 2] += 4.0
+        else:
+            logits[0::3, 0, 6] = -np.inf
+            logits[2::3, 1:, 6] = -np.inf
+        cases.append((logits, [14, 14, 9], 6))
+    return cases
+
+
+def test_c_beam_search_equals_numpy_beam_search_at_the_edge_inputs():
+    for logits, seq_len, blank in _edge_inputs():
+        for width in (1, 8, 100):
+            for norm in ('max', 'log_softmax'):
+                p1, s1 = octc.beam_search_decode(logits, seq_len, width, blank, norm)
+                p2, s2 = cref.beam_search_decode(logits, seq_len, width, blank, norm)
+                assert p1 == p2 and np.allclose(s1, s2, atol=1e-5), (logits.shape, blank, width)
+                for b, length in enumerate(seq_len):
+                    assert length > 0 or (p2[b] == [] and s2[b] == 0.0)
+
+
+def test_c_beam_search_counts_the_prefixes_that_entered_the_beam():
+    """`return_nodes`: with a beam wider than the prefix tree every labelling that fits into the
+    frames enters the beam once, and those are the keys of the exhaustive enumeration; a
+    masked class takes its labellings out; width 1 admits one new prefix per frame at most; the
+    paths and scores are those of the plain entry point."""
+    rng = np.random.default_rng(13)
+    logits = (rng.normal(size=(5, 4, 4)) * 2).astype(np.float32)
+    logits[:, 3, 0] = -np.inf
+    seq_len = [5, 0, 3, 5]
+    for blank in (3, 1):
+        for norm in ('max', 'log_softmax'):
+            paths, logp, nodes = cref.beam_search_decode(logits, seq_len, 1024, blank, norm,
+                                                         return_nodes=True)
+            want = [len([k for k, p in octc.brute_force_posteriors(logits[:n, b], blank).items()
+                         if p > 0]) for b, n in enumerate(seq_len)]
+            assert nodes.tolist() == want and nodes[1] == 1
+            plain = cref.beam_search_decode(logits, seq_len, 1024, blank, norm)
+            assert plain[0] == paths and np.array_equal(plain[1], logp)
+            _, _, narrow = cref.beam_search_decode(logits, seq_len, 1, blank, norm,
+                                                   return_nodes=True)
+            assert (narrow <= 1 + np.array(seq_len)).all() and (narrow >= 1).all()
+
+
 def test_dense_to_label_lists_drops_padding_zeros():
     assert octc.dense_to_label_lists(np.array([[3, 4, 0, 0], [0, 0, 0, 0], [1, 0, 2, 0]])) == \
         [[3, 4], [], [1, 2]]
