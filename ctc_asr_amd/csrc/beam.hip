@@ -17,6 +17,9 @@
 // prefix that leaves the beam and re-enters later is the same node, like TensorFlow's BeamEntry.
 // Ties in total are broken towards the older tree node (TensorFlow leaves them to gtl::TopN /
 // std::sort); node ages can differ from the CPU oracle's, so exact ties are not a parity case.
+// LM = true fuses a language model in where TensorFlow calls its BeamScorer (`BeamLm` below:
+// ExpandState / GetStateExpansionScore in both loops, GetStateEndExpansionScore at the end);
+// LM = false compiles all of it out and is the search as it was.
 #include "common.h"
 
 #define BEAM_THREADS 256
@@ -57,6 +60,27 @@ struct BeamLds {
     int freelist[BEAM_SLOTS];
     float x[BEAM_MAX_CLASSES];
     int misc[8];   // 0 nheap, 1 node count, 2 nfree
+};
+// ... with a language model: the automaton state of each leaf and the expansion score of the edge
+// that leads to it, both constants of the leaf's tree node.  They trail the plain layout, so the
+// search without a model addresses LDS exactly as before; 160 032 of the CU's 163 840 bytes.
+struct BeamLdsLm : BeamLds {
+    int lm_state[BEAM_SLOTS];
+    float lm_e[BEAM_SLOTS];
+};
+template <bool LM> struct BeamLdsOf { typedef BeamLds type; };
+template <> struct BeamLdsOf<true> { typedef BeamLdsLm type; };
+
+// The scorer of the fused search: a deterministic weighted automaton over label ids, TensorFlow's
+// BeamScorer with an integer state.  Entering label c in state s costs score[s * C + c] (the
+// expansion score, -inf: no such edge) and leads to next[s * C + c]; a hypothesis that ends in s
+// gets final[s] (NULL: nothing).  States read from `next` are clamped into [0, S), so the tables
+// are never indexed outside themselves, whatever they hold.
+struct BeamLm {
+    const int *next;
+    const float *score;
+    const float *final;
+    int states;
 };
 
 // a ranks below b in the heap order (lower total; equal totals: the younger node)
@@ -129,10 +153,14 @@ __device__ void bitonic_sort(unsigned long long *keys, int n_pow2, int tid) {
 // return, an evicted transient hands its slot straight to the child that pushed it out, the next
 // free slot and the next branch's children row (tree nodes, global memory) are fetched one
 // step ahead.  A serial sift through an LDS heap cost ~2 us per insertion; this ~0.4.
-template <int PER>
-__device__ void beam_expand(BeamLds &L, int lane, int W, int C, int blank, int nslots, int nheap0,
-                            int *pool_parent, int *pool_label, int *pool_children,
-                            int nodes_per_utt) {
+// LM: lane c also holds the model's edge (branch, c) - its score and the state it leads to, one
+// coalesced row load each per branch, fetched one branch ahead like the children row - and a
+// child's value is x[c] + (prev + score): TensorFlow's GetStateExpansionScore.  An edge of -inf
+// is no candidate and creates no node.
+template <int PER, bool LM>
+__device__ void beam_expand(typename BeamLdsOf<LM>::type &L, int lane, int W, int C, int blank,
+                            int nslots, int nheap0, int *pool_parent, int *pool_label,
+                            int *pool_children, int nodes_per_utt, const BeamLm &lm) {
     int nheap = nheap0, nfree = 0, nodes = L.misc[1];
     for (int base = 0; base < nslots; base += 64) {      // free slots, ordered
         const bool is_free = base + lane < nslots && !L.alive[base + lane];
@@ -182,12 +210,32 @@ __device__ void beam_expand(BeamLds &L, int lane, int W, int C, int blank, int n
     int kid_next = -1;
     if (nheap0 > 0 && lane < C)
         kid_next = gload(&pool_children[(size_t)L.node[L.branches[0]] * C + lane]);
+    // the model's rows of a branch's state, likewise (the blank's column is never read)
+    float lms_next = -INFINITY;
+    int lmn_next = 0;
+    auto lm_fetch = [&](int slot) {
+        if constexpr (LM) {
+            if (lane < C && lane != blank) {
+                const size_t at = (size_t)L.lm_state[slot] * C + lane;
+                lms_next = lm.score[at];
+                lmn_next = min(max(lm.next[at], 0), lm.states - 1);
+            }
+        }
+    };
+    if constexpr (LM) {
+        if (nheap0 > 0) lm_fetch(L.branches[0]);
+    }
     for (int j = 0; j < nheap0; ++j) {
         const int s = L.branches[j];
         const float ot = L.o_total[s];
         const int kidv = kid_next;           // tree nodes of this branch's children (-1: none yet)
         if (j + 1 < nheap0 && lane < C)
             kid_next = gload(&pool_children[(size_t)L.node[L.branches[j + 1]] * C + lane]);
+        const float lms = lms_next;          // the model's edges out of this branch's state
+        const int lmn = lmn_next;
+        if constexpr (LM) {
+            if (j + 1 < nheap0) lm_fetch(L.branches[j + 1]);
+        }
         // branches come in descending old total and the bottom only rises: once a branch cannot
         // beat the bottom of a full beam, no later one can
         if (nheap == W && !(ot > btot)) break;
@@ -202,8 +250,10 @@ __device__ void beam_expand(BeamLds &L, int lane, int W, int C, int blank, int n
         const int slabel = L.label[s];
         const unsigned long long active = L.kids_in_beam[s];
         float v = -INFINITY;
-        if (lane < C && lane != blank && !((active >> lane) & 1ull))
-            v = L.x[lane] + (lane == slabel ? L.o_blank[s] : ot);
+        if (lane < C && lane != blank && !((active >> lane) & 1ull)) {
+            if constexpr (LM) v = L.x[lane] + ((lane == slabel ? L.o_blank[s] : ot) + lms);
+            else v = L.x[lane] + (lane == slabel ? L.o_blank[s] : ot);
+        }
         // children that could enter right now; the bottom only rises while we insert
         unsigned long long cand = __ballot(v > -INFINITY && (nheap < W || v > btot));
         if (!cand) continue;
@@ -259,6 +309,11 @@ __device__ void beam_expand(BeamLds &L, int lane, int W, int C, int blank, int n
                 L.kids_in_beam[ns] = 0ull;
                 atomicOr(&L.kids_in_beam[s], 1ull << c);
             }
+            if constexpr (LM) {
+                const int st = __builtin_amdgcn_readlane(lmn, c);
+                const int e = __builtin_amdgcn_readlane(__float_as_int(lms), c);
+                if (lane == 0) { L.lm_state[ns] = st; L.lm_e[ns] = __int_as_float(e); }
+            }
             const unsigned long long nk = heap_key(vc, kid, ns);
             const unsigned nm = ((unsigned)s & 0xfffu) | ((unsigned)c << 12);
             if (full) {
@@ -281,13 +336,17 @@ __device__ void beam_expand(BeamLds &L, int lane, int W, int C, int blank, int n
     if (lane == 0) { L.misc[0] = nheap; L.misc[1] = nodes; }
 }
 
+// LM = false is the search without a model: every use of `lm` is compiled out.
+template <bool LM>
 __global__ void __launch_bounds__(BEAM_THREADS)
 beam_decode_kernel(const float *__restrict__ logits, const int *__restrict__ seq_len, int T, int B,
                    int C, int blank, int W, int norm_mode, int *__restrict__ out,
                    int *__restrict__ out_len, float *__restrict__ logp, int *pool_parent,
-                   int *pool_label, int *pool_slot, int *pool_children, int nodes_per_utt) {
+                   int *pool_label, int *pool_slot, int *pool_children, int nodes_per_utt,
+                   BeamLm lm) {
+    typedef typename BeamLdsOf<LM>::type Lds;
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    BeamLds &L = *reinterpret_cast<BeamLds *>(smem);
+    Lds &L = *reinterpret_cast<Lds *>(smem);
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
     int len = seq_len[b];
     len = len < 0 ? 0 : (len > T ? T : len);
@@ -304,6 +363,7 @@ beam_decode_kernel(const float *__restrict__ logits, const int *__restrict__ seq
     if (tid == 0) {
         L.node[0] = 0; L.label[0] = -1; L.parent[0] = -1; L.alive[0] = 1;
         L.n_total[0] = 0.f; L.n_blank[0] = 0.f; L.n_label[0] = -INFINITY;
+        if constexpr (LM) { L.lm_state[0] = 0; L.lm_e[0] = 0.f; }
         gstore(&pool_parent[0], -1); gstore(&pool_label[0], -1); gstore(&pool_slot[0], 0);
         L.heap[0] = 0;
         L.misc[0] = 1; L.misc[1] = 1; L.misc[3] = 0;
@@ -345,7 +405,13 @@ beam_decode_kernel(const float *__restrict__ logits, const int *__restrict__ seq
             const int lab = L.label[s];
             if (lab >= 0) {
                 const int ps = L.pslot[s];
-                if (ps >= 0) nl = lse2f(nl, lab == L.label[ps] ? L.o_blank[ps] : L.o_total[ps]);
+                if constexpr (LM) {
+                    if (ps >= 0)
+                        nl = lse2f(nl, (lab == L.label[ps] ? L.o_blank[ps] : L.o_total[ps]) +
+                                           L.lm_e[s]);
+                } else {
+                    if (ps >= 0) nl = lse2f(nl, lab == L.label[ps] ? L.o_blank[ps] : L.o_total[ps]);
+                }
                 nl += L.x[lab];
             }
             const float nb = L.o_total[s] + L.x[blank];
@@ -381,14 +447,14 @@ beam_decode_kernel(const float *__restrict__ logits, const int *__restrict__ seq
         if (tid < 64) {
             const int per = (W + 63) / 64;
             if (per <= 1)
-                beam_expand<1>(L, lane, W, C, blank, nslots, nheap0, pool_parent, pool_label,
-                               pool_children, nodes_per_utt);
+                beam_expand<1, LM>(L, lane, W, C, blank, nslots, nheap0, pool_parent, pool_label,
+                               pool_children, nodes_per_utt, lm);
             else if (per <= 4)
-                beam_expand<4>(L, lane, W, C, blank, nslots, nheap0, pool_parent, pool_label,
-                               pool_children, nodes_per_utt);
+                beam_expand<4, LM>(L, lane, W, C, blank, nslots, nheap0, pool_parent, pool_label,
+                               pool_children, nodes_per_utt, lm);
             else
-                beam_expand<16>(L, lane, W, C, blank, nslots, nheap0, pool_parent, pool_label,
-                                pool_children, nodes_per_utt);
+                beam_expand<16, LM>(L, lane, W, C, blank, nslots, nheap0, pool_parent, pool_label,
+                                pool_children, nodes_per_utt, lm);
         }
         __syncthreads();
         // ---- beam slots of the tree nodes for the next frame -----------------------------------
@@ -400,6 +466,15 @@ beam_decode_kernel(const float *__restrict__ logits, const int *__restrict__ seq
     }
 
     // ---- best leaf and its label path --------------------------------------------------------------
+    if constexpr (LM) {
+        // TensorFlow's TopPaths: the end score of each leaf's state joins its total first
+        if (lm.final) {
+            const int nheap = L.misc[0];
+            for (int i = tid; i < nheap; i += BEAM_THREADS)
+                L.n_total[L.heap[i]] += lm.final[L.lm_state[L.heap[i]]];
+            __syncthreads();
+        }
+    }
     if (tid == 0) {
         const int nheap = L.misc[0];
         int best = L.heap[0];
@@ -437,13 +512,16 @@ extern "C" size_t ctcasr_ctc_beam_workspace_bytes(int T, int B, int C, int beam_
     return (size_t)B * nodes_per_utt(T, beam_width, C) * (3 + (size_t)C) * sizeof(int) + 256;
 }
 
-extern "C" int ctcasr_ctc_beam_decode(const float *logits, const int32_t *seq_len, int T, int B,
-                                      int C, int blank, int beam_width, int norm_mode,
-                                      int32_t *out, int32_t *out_len, float *logp, void *workspace,
-                                      size_t workspace_bytes, ctcasr_stream_t stream) {
+namespace {
+
+// arguments, limits, workspace layout and launch of both entry points (lm: NULL without a model)
+int beam_launch(const float *logits, const int32_t *seq_len, int T, int B, int C, int blank,
+                int beam_width, int norm_mode, const BeamLm *lm, int32_t *out, int32_t *out_len,
+                float *logp, void *workspace, size_t workspace_bytes, ctcasr_stream_t stream) {
     if (!logits || !seq_len || !out || !out_len || T <= 0 || B <= 0 || C <= 1 || blank < 0 ||
         blank >= C || beam_width <= 0 || norm_mode < 0 || norm_mode > 1)
         return CTCASR_ERR_BAD_ARGUMENT;
+    if (lm && (!lm->next || !lm->score || lm->states < 1)) return CTCASR_ERR_BAD_ARGUMENT;
     if (beam_width > BEAM_MAX_WIDTH || C > BEAM_MAX_CLASSES) return CTCASR_ERR_UNSUPPORTED;
     if (!workspace || workspace_bytes < ctcasr_ctc_beam_workspace_bytes(T, B, C, beam_width))
         return CTCASR_ERR_WORKSPACE;
@@ -452,12 +530,47 @@ extern "C" int ctcasr_ctc_beam_decode(const float *logits, const int32_t *seq_le
     int *pool_label = pool_parent + (size_t)B * n;
     int *pool_slot = pool_label + (size_t)B * n;
     int *pool_children = pool_slot + (size_t)B * n;
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(&beam_decode_kernel),
-                            hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)sizeof(BeamLds)) != hipSuccess)
+    const void *kernel = lm ? reinterpret_cast<const void *>(&beam_decode_kernel<true>)
+                            : reinterpret_cast<const void *>(&beam_decode_kernel<false>);
+    const size_t lds = lm ? sizeof(BeamLdsLm) : sizeof(BeamLds);
+    if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
+        hipSuccess)
         return CTCASR_ERR_LAUNCH;
-    beam_decode_kernel<<<B, BEAM_THREADS, sizeof(BeamLds), (hipStream_t)stream>>>(
-        logits, seq_len, T, B, C, blank, beam_width, norm_mode, out, out_len, logp, pool_parent,
-        pool_label, pool_slot, pool_children, (int)n);
+    if (lm)
+        beam_decode_kernel<true><<<B, BEAM_THREADS, lds, (hipStream_t)stream>>>(
+            logits, seq_len, T, B, C, blank, beam_width, norm_mode, out, out_len, logp,
+            pool_parent, pool_label, pool_slot, pool_children, (int)n, *lm);
+    else
+        beam_decode_kernel<false><<<B, BEAM_THREADS, lds, (hipStream_t)stream>>>(
+            logits, seq_len, T, B, C, blank, beam_width, norm_mode, out, out_len, logp,
+            pool_parent, pool_label, pool_slot, pool_children, (int)n, BeamLm{});
     return ctcasr_launch_status();
+}
+
+}  // namespace
+
+extern "C" int ctcasr_ctc_beam_decode(const float *logits, const int32_t *seq_len, int T, int B,
+                                      int C, int blank, int beam_width, int norm_mode,
+                                      int32_t *out, int32_t *out_len, float *logp, void *workspace,
+                                      size_t workspace_bytes, ctcasr_stream_t stream) {
+    return beam_launch(logits, seq_len, T, B, C, blank, beam_width, norm_mode, nullptr, out,
+                       out_len, logp, workspace, workspace_bytes, stream);
+}
+
+// A leaf's state and edge score are constants of its tree node, and the branch's rows give them
+// again whenever the node re-enters the beam: the prefix tree itself carries nothing of the model,
+// and the fused search needs the plain search's pool.
+extern "C" size_t ctcasr_ctc_beam_lm_workspace_bytes(int T, int B, int C, int beam_width) {
+    return ctcasr_ctc_beam_workspace_bytes(T, B, C, beam_width);
+}
+
+extern "C" int ctcasr_ctc_beam_decode_lm(const float *logits, const int32_t *seq_len, int T, int B,
+                                         int C, int blank, int beam_width, int norm_mode,
+                                         const int32_t *lm_next, const float *lm_score,
+                                         const float *lm_final, int lm_states, int32_t *out,
+                                         int32_t *out_len, float *logp, void *workspace,
+                                         size_t workspace_bytes, ctcasr_stream_t stream) {
+    const BeamLm lm = {lm_next, lm_score, lm_final, lm_states};
+    return beam_launch(logits, seq_len, T, B, C, blank, beam_width, norm_mode, &lm, out, out_len,
+                       logp, workspace, workspace_bytes, stream);
 }

@@ -3,7 +3,8 @@
 Counterpart of ``asr/evaluate.py:18-43``: one pass over dev.csv (``--dev``) or test.csv with the
 model in evaluation mode; reports the CTC loss and the two ``eval_metric_ops`` of
 ``asr/model.py:111-118`` — mean edit distance and word error rate, each the unweighted mean over
-batches of the per-batch mean.  Decoding is the CTC beam search of width ``FLAGS.beam_width``.
+batches of the per-batch mean.  Decoding is the CTC beam search of width ``FLAGS.beam_width``,
+with the language model of ``--lm_path`` fused in when that flag is set.
 """
 
 import sys
@@ -11,16 +12,18 @@ import sys
 import numpy as np
 import torch
 
-from ctc_asr_amd import storage, summaries
+from ctc_asr_amd import lm, storage, summaries
 from ctc_asr_amd.input_functions import input_fn_generator
 from ctc_asr_amd.model import CTCModel, ModelConfig
 from ctc_asr_amd.params import FLAGS
 
 
-def evaluate_dataset(model, target, rank=0, world=1, max_batches=None, report_samples=True):
+def evaluate_dataset(model, target, rank=0, world=1, max_batches=None, report_samples=True,
+                     scorer=None):
     """{'loss', 'mean_edit_distance', 'word_error_rate', 'batches'} for one pass over
     ``target`` ('dev' or 'test'); with ``world > 1`` every rank scores its shard and the
-    per-batch means are averaged over ranks."""
+    per-batch means are averaged over ranks.  ``scorer``: a scaled `lm.LmScorer` to decode
+    with."""
     input_fn = input_fn_generator(target, device=model.device, rank=rank, world_size=world,
                                   seed=(FLAGS.random_seed or 1) if world > 1 else None)
     losses, meds, wers = [], [], []
@@ -32,7 +35,8 @@ def evaluate_dataset(model, target, rank=0, world=1, max_batches=None, report_sa
     def score_pending():
         nonlocal samples
         results = model.decode_many([(logits, seq_len, originals)
-                                     for logits, seq_len, originals, _, _ in pending])
+                                     for logits, seq_len, originals, _, _ in pending],
+                                    scorer=scorer)
         for (decoded, plaintext, summary), (_, _, _, labels, texts) in zip(results, pending):
             _, mean_ed, _, wer = model.error_rates_fn(labels, texts, decoded, plaintext)
             meds.append(float(mean_ed))
@@ -55,7 +59,7 @@ def evaluate_dataset(model, target, rank=0, world=1, max_batches=None, report_sa
         pending.append((logits, seq_len, originals, labels, features['label_plaintext']))
         # (the longest utterances bound the prefix-tree pool: size the group on them)
         group = model.decode_group_size(max(int(item[0].shape[0]) for item in pending),
-                                        int(logits.shape[1]))
+                                        int(logits.shape[1]), scorer=scorer)
         if len(pending) >= group:
             score_pending()
     if pending:
@@ -83,7 +87,7 @@ def main(argv=None):
     storage.restore_checkpoint(latest, model)
     target = 'dev' if FLAGS.dev else 'test'
     print('Evaluating checkpoint {} on the {} set.'.format(latest, target))
-    result = evaluate_dataset(model, target)
+    result = evaluate_dataset(model, target, scorer=lm.from_flags(model.cfg.num_classes))
     writer = summaries.SummaryWriter(FLAGS.train_dir, 'eval_' + target)
     for tag in ('loss', 'mean_edit_distance', 'word_error_rate'):       # eval_metric_ops + loss
         writer.scalar(tag, result[tag], model.step_count)

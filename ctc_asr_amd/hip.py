@@ -43,6 +43,9 @@ SIGNATURES = {
     'ctcasr_ctc_greedy_decode': (_c_int, [_c_p, _c_p] + [_c_int] * 4 + [_c_p, _c_p, _c_p]),
     'ctcasr_ctc_beam_workspace_bytes': (_c_sz, [_c_int] * 4),
     'ctcasr_ctc_beam_decode': (_c_int, [_c_p, _c_p] + [_c_int] * 6 + [_c_p] * 4 + [_c_sz, _c_p]),
+    'ctcasr_ctc_beam_lm_workspace_bytes': (_c_sz, [_c_int] * 4),
+    'ctcasr_ctc_beam_decode_lm': (_c_int, [_c_p, _c_p] + [_c_int] * 6 + [_c_p] * 3 + [_c_int] +
+                                  [_c_p] * 4 + [_c_sz, _c_p]),
     'ctcasr_ctc_align_workspace_bytes': (_c_sz, [_c_int] * 4),
     'ctcasr_ctc_align': (_c_int, [_c_p] * 4 + [_c_int] * 5 + [_c_p] * 5 + [_c_sz, _c_p]),
     'ctcasr_rnn_reserve_bytes': (_c_sz, [_c_int] * 4),
@@ -346,6 +349,39 @@ def ctc_beam_decode(logits, seq_len, beam_width, blank=None, normalization='max'
         _stream()), 'ctc_beam_decode')
     if bool((out_len < 0).any()):
         raise CtcAsrError('ctc_beam_decode: prefix-tree pool exhausted')
+    return out, out_len, logp
+
+
+def ctc_beam_lm_workspace_bytes(num_steps, batch, classes, beam_width):
+    return load().ctcasr_ctc_beam_lm_workspace_bytes(num_steps, batch, classes, int(beam_width))
+
+
+@_on_tensor_device
+def ctc_beam_decode_lm(logits, seq_len, beam_width, scorer, blank=None, normalization='max'):
+    """`ctc_beam_decode` with a language model fused into the search: ``scorer`` is an
+    `lm.LmScorer`, already scaled (`LmScorer.scaled`).  ``logp`` includes the model's scores."""
+    num_steps, batch, classes = _decode_shape('ctc_beam_decode_lm', logits, seq_len)
+    if scorer.num_classes != classes:
+        raise CtcAsrError('ctc_beam_decode_lm: the scorer has {} classes, the logits {}.'
+                          .format(scorer.num_classes, classes))
+    blank = classes - 1 if blank is None else blank
+    dev = logits.device
+    lm_next, lm_score, lm_final = scorer.to(dev)
+    out = torch.empty((batch, num_steps), dtype=torch.int32, device=dev)
+    out_len = torch.empty(batch, dtype=torch.int32, device=dev)
+    logp = torch.empty(batch, dtype=torch.float32, device=dev)
+    workspace = _workspace(load().ctcasr_ctc_beam_lm_workspace_bytes(num_steps, batch, classes,
+                                                                     int(beam_width)), dev)
+    _check(load().ctcasr_ctc_beam_decode_lm(
+        _dev(logits, name='logits'), _dev(seq_len, torch.int32, 'seq_len'), num_steps, batch,
+        classes, blank, int(beam_width), {'max': 0, 'log_softmax': 1}[normalization],
+        _dev(lm_next, torch.int32, 'lm_next'), _dev(lm_score, name='lm_score'),
+        _dev(lm_final, name='lm_final'), scorer.num_states,
+        _dev(out, torch.int32, 'out'), _dev(out_len, torch.int32, 'out_len'),
+        _dev(logp, name='logp'), _dev(workspace, torch.uint8, 'workspace'), workspace.numel(),
+        _stream()), 'ctc_beam_decode_lm')
+    if bool((out_len < 0).any()):
+        raise CtcAsrError('ctc_beam_decode_lm: prefix-tree pool exhausted')
     return out, out_len, logp
 
 

@@ -1841,13 +1841,17 @@ class CTCModel:
                 'mean_edit_distance': mean_ed, 'word_error_rate': wer}
 
     # ------------------------------------------------------------------ decode / score
-    def decode_fn(self, logits, seq_len, originals=None, beam_width=None, greedy=False):
+    def decode_fn(self, logits, seq_len, originals=None, beam_width=None, greedy=False,
+                  scorer=None):
         """CTC decode + plaintext (``asr/model.py:271-309``).  Returns (decoded: list of B int
         lists — the values of the reference's SparseTensor —, plaintext object[B], summary
-        object[2, B]).  ``greedy=True`` selects the greedy decoder instead of the beam search."""
+        object[2, B]).  ``greedy=True`` selects the greedy decoder instead of the beam search;
+        ``scorer`` (a scaled `lm.LmScorer`) fuses a language model into the beam search."""
         beam_width = self.cfg.beam_width if beam_width is None else beam_width
         if greedy:
             out, out_len = hip.ctc_greedy_decode(logits, seq_len)
+        elif scorer is not None:
+            out, out_len, _ = hip.ctc_beam_decode_lm(logits, seq_len, beam_width, scorer)
         else:
             out, out_len, _ = hip.ctc_beam_decode(logits, seq_len, beam_width)
         return self._decoded_to_text(out.cpu().numpy(), out_len.cpu().numpy(), originals)
@@ -1864,22 +1868,24 @@ class CTCModel:
         return decoded, plaintext, summary
 
     def decode_group_size(self, num_steps, batch, beam_width=None, budget_bytes=48 << 30,
-                          max_utterances=256):
+                          max_utterances=256, scorer=None):
         """How many batches of ``batch`` utterances `decode_many` should be given at once: the
         beam search runs one workgroup per utterance, so a single batch occupies 16 or 32 of the
         256 CUs and a group of batches decodes in about the time of one.  Bounded by the prefix
         tree pool (256 MB per utterance at width 1024, T' = 500) and ``max_utterances``."""
         beam_width = self.cfg.beam_width if beam_width is None else beam_width
-        per_utt = max(1, hip.ctc_beam_workspace_bytes(num_steps, 1, self.cfg.num_classes,
-                                                      beam_width))
+        sizer = hip.ctc_beam_workspace_bytes if scorer is None else \
+            hip.ctc_beam_lm_workspace_bytes
+        per_utt = max(1, sizer(num_steps, 1, self.cfg.num_classes, beam_width))
         utterances = max(batch, min(max_utterances, budget_bytes // per_utt))
         return max(1, int(utterances // batch))
 
-    def decode_many(self, batches, beam_width=None):
+    def decode_many(self, batches, beam_width=None, scorer=None):
         """Beam-search decode of several batches in ONE launch.  ``batches`` is a list of
         (logits [T'_i, B_i, C], seq_len [B_i], originals or None); returns one `decode_fn` result
         per batch - identical to decoding the batches one by one (an utterance's search does not
-        depend on its neighbours; frames past its length are never read)."""
+        depend on its neighbours; frames past its length are never read).  ``scorer``: as in
+        `decode_fn`."""
         beam_width = self.cfg.beam_width if beam_width is None else beam_width
         if not batches:
             return []
@@ -1894,7 +1900,10 @@ class CTCModel:
             joint[:logits.shape[0], start:stop] = logits
             lengths[start:stop] = seq_len
             start = stop
-        out, out_len, _ = hip.ctc_beam_decode(joint, lengths, beam_width)
+        if scorer is not None:
+            out, out_len, _ = hip.ctc_beam_decode_lm(joint, lengths, beam_width, scorer)
+        else:
+            out, out_len, _ = hip.ctc_beam_decode(joint, lengths, beam_width)
         out, out_len = out.cpu().numpy(), out_len.cpu().numpy()
         results, start = [], 0
         for logits, _, originals in batches:

@@ -218,6 +218,16 @@ FLAGS.define('string', 'align_csv', '', 'align.py: path;label;length manifest to
              'order.')
 FLAGS.define('string', 'align_output', '', 'align.py: JSON-lines output, one line per manifest row.')
 
+# Language model fused into the beam search (no counterpart in the reference): evaluate.py and
+# predict.py decode with the model of --lm_path; `python -m ctc_asr_amd.lm` builds one.
+FLAGS.define('string', 'lm_path', '', 'Character n-gram (.npz of ctc_asr_amd.lm) the beam search '
+             'scores with; empty: no language model.')
+FLAGS.define('float', 'lm_weight', 1.0, 'Weight of the language model\'s log-probabilities.')
+FLAGS.define('float', 'lm_bonus', 0.0, 'Added to the score of every emitted label.')
+FLAGS.define('int', 'lm_order', 5, 'lm.py: order of the n-gram to build.')
+FLAGS.define('string', 'lm_corpus_csv', '', 'lm.py: path;label;length manifest whose transcripts '
+             'the n-gram is built from.')
+
 # ####### Constants (asr/params.py:138-155). #########
 NP_FLOAT = np.float32
 

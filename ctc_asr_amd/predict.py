@@ -1,7 +1,9 @@
 """Transcribe one WAV file: ``python -m ctc_asr_amd.predict --input file.wav``
 (counterpart of ``asr/predict.py:44-67``; returns / prints {'decoded', 'plaintext'}).
 ``--timestamps`` adds ``'words'``: the decoded text aligned to the same logits
-(`CTCModel.align_fn`), one ``{'word', 'start', 'end', 'confidence'}`` per word."""
+(`CTCModel.align_fn`), one ``{'word', 'start', 'end', 'confidence'}`` per word.  ``--lm_path``
+decodes with that language model fused into the beam search (``--lm_weight``, ``--lm_bonus``);
+the timestamps are then those of the text it decoded."""
 
 import os
 import sys
@@ -9,17 +11,17 @@ import sys
 import numpy as np
 import torch
 
-from ctc_asr_amd import alignment, storage
+from ctc_asr_amd import alignment, lm, storage
 from ctc_asr_amd.input_functions import features_from_pcm, read_wav
 from ctc_asr_amd.model import CTCModel, ModelConfig
 from ctc_asr_amd.params import FLAGS
 
 
-def predict(model, wav_path, timestamps=False):
+def predict(model, wav_path, timestamps=False, scorer=None):
     feats, lengths = features_from_pcm([read_wav(wav_path)], model.device)
     logits, seq_len = model.inference_fn(feats, lengths, training=False)
     model.check_rnn_error()
-    decoded, plaintext, _ = model.decode_fn(logits, seq_len, None)
+    decoded, plaintext, _ = model.decode_fn(logits, seq_len, None, scorer=scorer)
     result = {'decoded': np.array(decoded[0], dtype=np.int32), 'plaintext': plaintext[0]}
     if timestamps:
         ids = [v for v in decoded[0] if v != 0]     # (id 0 renders as '' and is no label)
@@ -44,7 +46,7 @@ def main(argv=None):
         raise SystemExit('No checkpoint found in {}.'.format(FLAGS.train_dir))
     storage.restore_checkpoint(latest, model)
     print('Inputs: {}'.format(FLAGS.input))
-    print(predict(model, FLAGS.input, FLAGS.timestamps))
+    print(predict(model, FLAGS.input, FLAGS.timestamps, lm.from_flags(model.cfg.num_classes)))
     return 0
 
 

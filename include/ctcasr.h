@@ -112,6 +112,37 @@ int ctcasr_ctc_beam_decode(const float *logits, const int32_t *seq_len, int T, i
                            int32_t *out_len, float *logp, void *workspace,
                            size_t workspace_bytes, ctcasr_stream_t stream);
 
+/* Beam search with a language model fused in (no counterpart in the reference).  The model is a
+ * deterministic weighted automaton over label ids - TensorFlow's BeamScorer with an integer
+ * state; a back-off n-gram of any order and a word list both compile to it:
+ *   lm_next   int32 [lm_states, C]: the state after label c in state s; state 0 is the start
+ *   lm_score  float [lm_states, C]: the expansion score of that edge, weight and insertion bonus
+ *             already folded in; -inf forbids the edge (it is never a candidate and creates no
+ *             tree node).  +inf and NaN are the caller's to refuse.
+ *   lm_final  float [lm_states] or NULL: the end score of a hypothesis that ends in s
+ * The blank's column of both tables is never read.  Entries of lm_next are clamped into
+ * [0, lm_states): the tables are never indexed outside themselves, whatever they hold.
+ * The scorer enters where TensorFlow calls it.  A leaf's edge score e = lm_score[state(parent),
+ * label] and its state are constants of its tree node (root: state 0, e = 0).  Per frame, a leaf
+ * whose parent is in the beam gets new.label = lse(new.label, prev + e) before + x[label]; a
+ * proposed child is worth x[c] + (prev + lm_score[state(branch), c]), added in that order in
+ * fp32 (prev: the parent's old blank for a repeated label, else its old total).  At the end
+ * lm_final[state] joins every leaf's total before the best is chosen, and logp is that fused
+ * total.  With lm_states = 1, all scores 0 and no lm_final the result is bit for bit that of
+ * ctcasr_ctc_beam_decode.
+ * Tie rule, as in the plain search: the leaf with the lowest total leaves the beam first and,
+ * among equal totals, the youngest tree node; the best leaf among equal totals is the oldest.
+ * Arguments, limits, outputs (out_len -1: pool exhausted) and status codes are those of
+ * ctcasr_ctc_beam_decode; lm_states < 1 or a NULL lm_next / lm_score is
+ * CTCASR_ERR_BAD_ARGUMENT.  Workspace: ctcasr_ctc_beam_lm_workspace_bytes(T, B, C, beam_width)
+ * (the prefix tree carries nothing of the model: the size of the plain search's). */
+size_t ctcasr_ctc_beam_lm_workspace_bytes(int T, int B, int C, int beam_width);
+int ctcasr_ctc_beam_decode_lm(const float *logits, const int32_t *seq_len, int T, int B, int C,
+                              int blank, int beam_width, int norm_mode, const int32_t *lm_next,
+                              const float *lm_score, const float *lm_final, int lm_states,
+                              int32_t *out, int32_t *out_len, float *logp, void *workspace,
+                              size_t workspace_bytes, ctcasr_stream_t stream);
+
 /* ---- K11: CTC forced alignment ----------------------------------------------------------------
  * The Viterbi (max-sum) form of K9's alpha recursion: the single best alignment of each
  * utterance's label to its frames (no counterpart in the reference).  Inputs and status codes
