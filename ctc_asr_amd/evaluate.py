@@ -23,7 +23,11 @@ def evaluate_dataset(model, target, rank=0, world=1, max_batches=None, report_sa
     """{'loss', 'mean_edit_distance', 'word_error_rate', 'batches'} for one pass over
     ``target`` ('dev' or 'test'); with ``world > 1`` every rank scores its shard and the
     per-batch means are averaged over ranks.  ``scorer``: a scaled `lm.LmScorer` to decode
-    with."""
+    with.  When the decodes are scored on the GPU (``CTCASR_GPU_METRICS``, the default) the
+    result also holds the error breakdown summed over the set - 'label_errors' and
+    'word_errors', each {'substitutions', 'deletions', 'insertions', 'reference'} - and the
+    corpus-level 'corpus_label_error_rate' and 'corpus_word_error_rate': total errors over
+    total reference length."""
     input_fn = input_fn_generator(target, device=model.device, rank=rank, world_size=world,
                                   seed=(FLAGS.random_seed or 1) if world > 1 else None)
     losses, meds, wers = [], [], []
@@ -31,6 +35,8 @@ def evaluate_dataset(model, target, rank=0, world=1, max_batches=None, report_sa
     # several batches are decoded in ONE launch (`CTCModel.decode_many`) - same results, and a
     # group costs about what a single batch does.  The metrics stay per-batch means.
     pending, group, samples = [], None, None
+    # (S, D, I, reference length) summed over the set: labels, then words
+    totals = np.zeros((2, 4), dtype=np.int64)
 
     def score_pending():
         nonlocal samples
@@ -38,7 +44,14 @@ def evaluate_dataset(model, target, rank=0, world=1, max_batches=None, report_sa
                                      for logits, seq_len, originals, _, _ in pending],
                                     scorer=scorer)
         for (decoded, plaintext, summary), (_, _, _, labels, texts) in zip(results, pending):
-            _, mean_ed, _, wer = model.error_rates_fn(labels, texts, decoded, plaintext)
+            if model.gpu_metrics:
+                _, mean_ed, _, wer, label_counts, word_counts, reference = \
+                    model.error_counts_fn(labels, texts, decoded, plaintext)
+                totals[0, :3] += label_counts[:, 1:].sum(axis=0, dtype=np.int64)
+                totals[1, :3] += word_counts[:, 1:].sum(axis=0, dtype=np.int64)
+                totals[:, 3] += reference.sum(axis=0)
+            else:
+                _, mean_ed, _, wer = model.error_rates_fn(labels, texts, decoded, plaintext)
             meds.append(float(mean_ed))
             wers.append(float(wer))
             if samples is None:
@@ -67,13 +80,22 @@ def evaluate_dataset(model, target, rank=0, world=1, max_batches=None, report_sa
     if report_samples and rank == 0 and samples is not None:
         for dec, orig in list(zip(samples[0], samples[1]))[:FLAGS.num_samples_to_report]:
             print('  decoded: "{}"\n  original: "{}"'.format(dec, orig))
-    stats = torch.tensor([np.sum(losses), np.sum(meds), np.sum(wers), len(losses)],
-                         dtype=torch.float64, device=model.device)
+    # (the integer sums ride in the same float64 all_reduce: exact below 2^53)
+    stats = torch.tensor([np.sum(losses), np.sum(meds), np.sum(wers), len(losses)] +
+                         totals.reshape(-1).tolist(), dtype=torch.float64, device=model.device)
     if world > 1:
         torch.distributed.all_reduce(stats)
     count = max(float(stats[3]), 1.0)
-    return {'loss': float(stats[0]) / count, 'mean_edit_distance': float(stats[1]) / count,
-            'word_error_rate': float(stats[2]) / count, 'batches': int(stats[3])}
+    result = {'loss': float(stats[0]) / count, 'mean_edit_distance': float(stats[1]) / count,
+              'word_error_rate': float(stats[2]) / count, 'batches': int(stats[3])}
+    if model.gpu_metrics:
+        for name, row in (('label', stats[4:8].tolist()), ('word', stats[8:12].tolist())):
+            subs, dels, ins, reference = (int(v) for v in row)
+            result[name + '_errors'] = {'substitutions': subs, 'deletions': dels,
+                                        'insertions': ins, 'reference': reference}
+            result['corpus_{}_error_rate'.format(name)] = \
+                (subs + dels + ins) / reference if reference else float('nan')
+    return result
 
 
 def main(argv=None):

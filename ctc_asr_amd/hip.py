@@ -48,6 +48,8 @@ SIGNATURES = {
                                   [_c_p] * 4 + [_c_sz, _c_p]),
     'ctcasr_ctc_align_workspace_bytes': (_c_sz, [_c_int] * 4),
     'ctcasr_ctc_align': (_c_int, [_c_p] * 4 + [_c_int] * 5 + [_c_p] * 5 + [_c_sz, _c_p]),
+    'ctcasr_edit_distance_workspace_bytes': (_c_sz, [_c_int] * 3),
+    'ctcasr_edit_distance': (_c_int, [_c_p] * 6 + [_c_int] * 3 + [_c_p] * 6 + [_c_sz, _c_p]),
     'ctcasr_rnn_reserve_bytes': (_c_sz, [_c_int] * 4),
     'ctcasr_rnn_workspace_bytes': (_c_sz, [_c_int] * 4),
     'ctcasr_rnn_persistent_supported': (_c_int, [_c_int] * 4),
@@ -418,6 +420,55 @@ def ctc_align(logits, labels, label_offsets, seq_len, max_label_len, blank=None,
         _dev(status, torch.int32, 'status'), _dev(workspace, torch.uint8, 'workspace'),
         workspace.numel(), _stream()), 'ctc_align')
     return path, score, frame_logp, status
+
+
+def edit_distance_workspace_bytes(batch, max_hyp_len, max_ref_len):
+    return load().ctcasr_edit_distance_workspace_bytes(int(batch), int(max_hyp_len),
+                                                       int(max_ref_len))
+
+
+@_on_tensor_device
+def edit_distance(hyp, hyp_offsets, hyp_len, ref, ref_offsets, ref_len, max_hyp_len=None,
+                  max_ref_len=None, out=None):
+    """Batched edit distance with error counts.  Pair b compares ``hyp[hyp_offsets[b] .. +
+    hyp_len[b])`` with ``ref[ref_offsets[b] .. + ref_len[b])``; all six are int32 device tensors
+    (``hyp`` / ``ref`` of any shape, read flat).  Returns (distance, substitutions, deletions,
+    insertions, status), int32[B] each - the rows of ``out`` (int32 [5, B]) when that is given.
+    ``max_*_len`` default to the largest length of their side.  A non-zero status is data, not
+    an error: the caller reads it.  Refuses rows that leave their buffer."""
+    batch = hyp_len.numel()
+    for name, vector in (('hyp_offsets', hyp_offsets), ('ref_offsets', ref_offsets),
+                         ('ref_len', ref_len)):
+        if vector.numel() != batch:
+            raise CtcAsrError('edit_distance: {} holds {} entries for a batch of {}.'
+                              .format(name, vector.numel(), batch))
+    if batch < 1:
+        raise CtcAsrError('edit_distance: the batch is empty.')
+    args = [_dev(hyp, torch.int32, 'hyp'), _dev(hyp_offsets, torch.int32, 'hyp_offsets'),
+            _dev(hyp_len, torch.int32, 'hyp_len'), _dev(ref, torch.int32, 'ref'),
+            _dev(ref_offsets, torch.int32, 'ref_offsets'), _dev(ref_len, torch.int32, 'ref_len')]
+    # the ABI takes bare pointers: keep every row the kernel may read inside its buffer
+    hyp_len64, ref_len64 = hyp_len.long().clamp(min=0), ref_len.long().clamp(min=0)
+    hyp_off64, ref_off64 = hyp_offsets.long(), ref_offsets.long()
+    hyp_low, hyp_high, hyp_max, ref_low, ref_high, ref_max = torch.stack([
+        hyp_off64.min(), (hyp_off64 + hyp_len64).max(), hyp_len64.max(),
+        ref_off64.min(), (ref_off64 + ref_len64).max(), ref_len64.max()]).tolist()
+    if hyp_low < 0 or hyp_high > hyp.numel() or ref_low < 0 or ref_high > ref.numel():
+        raise CtcAsrError('edit_distance: a row lies outside its buffer.')
+    max_hyp_len = hyp_max if max_hyp_len is None else int(max_hyp_len)
+    max_ref_len = ref_max if max_ref_len is None else int(max_ref_len)
+    dev = hyp_len.device
+    if out is None:
+        out = torch.empty((5, batch), dtype=torch.int32, device=dev)
+    elif tuple(out.shape) != (5, batch):
+        raise CtcAsrError('edit_distance: out must be int32 [5, {}].'.format(batch))
+    _dev(out, torch.int32, 'out')
+    workspace = _workspace(edit_distance_workspace_bytes(batch, max_hyp_len, max_ref_len), dev)
+    _check(load().ctcasr_edit_distance(
+        *args, batch, max_hyp_len, max_ref_len, *[out[k].data_ptr() for k in range(5)],
+        _dev(workspace, torch.uint8, 'workspace'), workspace.numel(), _stream()),
+        'edit_distance')
+    return out[0], out[1], out[2], out[3], out[4]
 
 
 def rnn_reserve_bytes(cell, num_steps, batch, hidden):

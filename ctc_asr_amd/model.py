@@ -500,6 +500,9 @@ class CTCModel:
         # variant of the persistent backward recurrence (hip.RNN_*): default = 128 CUs, the
         # other half of the chip runs the weight-gradient GEMMs of the layer above
         self.rnn_bwd_flags = int(os.environ.get('CTCASR_RNN_BWD_FLAGS', str(hip.RNN_DEFAULT)))
+        # score decodes with the edit-distance kernel (`error_counts_fn`) instead of the host
+        # loops of `error_rates_fn`; the rates are the same either way
+        self.gpu_metrics = os.environ.get('CTCASR_GPU_METRICS', '1') == '1'
         self._rnn_ws = {}               # (cell, B, H) -> (zero-initialised workspace, T')
         self.dropout_seed = int(seed) * 0x9E3779B1 + 1
         self._acts = None
@@ -1834,9 +1837,9 @@ class CTCModel:
         decoded, plaintext, summary = self.decode_fn(
             logits, seq_length, np.array([t.encode('utf-8') if isinstance(t, str) else t
                                           for t in originals], dtype=object))
-        _, mean_ed, _, wer = self.error_rates_fn(labels, [t.decode('utf-8') if isinstance(t, bytes)
-                                                          else t for t in originals],
-                                                 decoded, plaintext)
+        score = self.error_counts_fn if self.gpu_metrics else self.error_rates_fn
+        _, mean_ed, _, wer = score(labels, [t.decode('utf-8') if isinstance(t, bytes) else t
+                                            for t in originals], decoded, plaintext)[:4]
         return {'loss': loss, 'decoded': decoded, 'plaintext': plaintext, 'summary': summary,
                 'mean_edit_distance': mean_ed, 'word_error_rate': wer}
 
@@ -1922,3 +1925,28 @@ class CTCModel:
         edit_distances, mean_ed = metrics.edit_distance_batch(decoded, truths)
         wers, wer = metrics.wer_batch(list(originals), list(decoded_texts))
         return edit_distances, mean_ed, wers, wer
+
+    def error_counts_fn(self, labels, originals, decoded, decoded_texts):
+        """`error_rates_fn` on the GPU, with the error breakdown: its four values, bit for bit,
+        then ``label_counts`` and ``word_counts`` (int32 ``[B, 4]`` of distance, substitutions,
+        deletions, insertions) and ``reference_lengths`` (int64 ``[B, 2]``: labels, words).  The
+        ``B`` label pairs and the ``B`` word pairs are scored in one launch of ``2B`` pairs."""
+        if isinstance(labels, torch.Tensor):
+            labels = labels.cpu().numpy()
+        truths = [[int(v) for v in row if int(v) != 0] for row in labels]
+        decoded = [list(row) for row in decoded]
+        if len(decoded) != len(truths):
+            raise ValueError('error_counts_fn(): batch sizes differ.')
+        if len(originals) != len(decoded_texts):
+            raise AssertionError('error_counts_fn(): originals and results differ in length.')
+        original_words, decoded_words = metrics.word_ids(originals, decoded_texts)
+        counts = metrics.error_counts(decoded + decoded_words, truths + original_words,
+                                      self.device)
+        label_counts, word_counts = counts[:len(truths)], counts[len(truths):]
+        reference_lengths = np.array([[len(t), len(w)] for t, w in zip(truths, original_words)],
+                                     dtype=np.int64).reshape(-1, 2)
+        edit_distances, mean_ed = metrics.edit_distance_batch_from_counts(
+            label_counts[:, 0], reference_lengths[:, 0])
+        wers, wer = metrics.wer_batch_from_counts(word_counts[:, 0], reference_lengths[:, 1])
+        return (edit_distances, mean_ed, wers, wer, label_counts, word_counts,
+                reference_lengths)

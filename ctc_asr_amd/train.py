@@ -58,8 +58,9 @@ def train_epoch(trainer, target, epoch, rank, world, writer=None, seed=None):
                         model.last_logits, model.last_seq_length,
                         np.array([t.encode('utf-8') for t in features['label_plaintext']],
                                  dtype=object))
-                    _, mean_ed, _, wer = model.error_rates_fn(
-                        labels, features['label_plaintext'], decoded, plaintext)
+                    score = model.error_counts_fn if model.gpu_metrics else model.error_rates_fn
+                    _, mean_ed, _, wer = score(
+                        labels, features['label_plaintext'], decoded, plaintext)[:4]
                     step = model.step_count
                     writer.scalar('loss', value, step)
                     writer.scalar('learning_rate', trainer.lr, step)

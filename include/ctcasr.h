@@ -168,6 +168,35 @@ int ctcasr_ctc_align(const float *logits, const int32_t *labels, const int32_t *
                      int32_t *path, float *score, float *frame_logp, int32_t *status,
                      void *workspace, size_t workspace_bytes, ctcasr_stream_t stream);
 
+/* ---- K13: edit distance ------------------------------------------------------------------------
+ * Replaces tf.edit_distance(decoded, labels) (asr/model.py:338) and the Levenshtein distance of
+ * asr/util/metrics.py:110-141, for a whole batch in one launch, and adds the error breakdown.
+ * Pair b compares hyp[hyp_offsets[b] .. + hyp_len[b]) with ref[ref_offsets[b] .. + ref_len[b]);
+ * symbols are arbitrary int32 (label ids, word ids).  Offsets plus lengths serve the decoders'
+ * dense out [B, T] / out_len (hyp_offsets[b] = b * T) and the CTC loss's packed labels alike;
+ * rows may overlap and hyp may be ref.  Unit costs.
+ *   distance       int32 [B]: the Levenshtein distance
+ *   substitutions  int32 [B] (S), deletions (D: reference symbols left unmatched), insertions
+ *                  (I: hypothesis symbols inserted); each of the three may be NULL
+ *   status         int32 [B]: 0 ok; 2 a length that is negative (the beam search's out_len = -1
+ *                  included) or above its max_*_len - the four outputs of that pair are -1
+ * Tie rule: the counts are those of the alignment with the fewest substitutions among all
+ * alignments of minimum distance - the lexicographic minimum of (distance, S), which does not
+ * depend on the order in which alignments are visited.  distance = S + D + I and
+ * D - I = ref_len - hyp_len, so (distance, S) fixes all four; results are bit-reproducible.
+ * A length of 0 on either side is valid (distance = the other length, all D or all I).  Every
+ * output is fully written.  max_hyp_len, max_ref_len <= 32767 (else CTCASR_ERR_UNSUPPORTED);
+ * B < 1 is CTCASR_ERR_BAD_ARGUMENT.  Workspace: ctcasr_edit_distance_workspace_bytes(B,
+ * max_hyp_len, max_ref_len) - 0 while the kernel's carry columns fit in LDS, and `workspace`
+ * may then be NULL. */
+size_t ctcasr_edit_distance_workspace_bytes(int B, int max_hyp_len, int max_ref_len);
+int ctcasr_edit_distance(const int32_t *hyp, const int32_t *hyp_offsets, const int32_t *hyp_len,
+                         const int32_t *ref, const int32_t *ref_offsets, const int32_t *ref_len,
+                         int B, int max_hyp_len, int max_ref_len, int32_t *distance,
+                         int32_t *substitutions, int32_t *deletions, int32_t *insertions,
+                         int32_t *status, void *workspace, size_t workspace_bytes,
+                         ctcasr_stream_t stream);
+
 /* ---- K4/K5: recurrence of one bidirectional RNN layer ----------------------------------------
  * Replaces the time loop of tfc.cudnn_rnn.Cudnn{LSTM,GRU,RNNRelu,RNNTanh}(direction=
  * 'bidirectional') (asr/model.py:194-215) and of stack_bidirectional_dynamic_rnn over
