@@ -14,6 +14,14 @@ __device__ __forceinline__ float uniform01(uint64_t seed, uint64_t idx) {
     return (float)(z >> 40) * (1.0f / 16777216.0f);
 }
 
+// min(max(v, 0), cutoff) that keeps a NaN: fmaxf(NaN, 0) is 0, which would hand a finite
+// activation to the next layer, a finite loss to ctcasr_step_guard, and the step would be applied.
+// (-inf -> 0, +inf -> cutoff as before.)
+__device__ __forceinline__ float relu_clip(float v, float cutoff) {
+    const float c = fminf(fmaxf(v, 0.f), cutoff);
+    return v != v ? v : c;
+}
+
 __global__ void __launch_bounds__(256)
 bias_act_fwd_kernel(float *__restrict__ y, const float *__restrict__ bias, int64_t n, int cols,
                     float cutoff, float rate, float inv_keep, uint64_t seed) {
@@ -22,7 +30,7 @@ bias_act_fwd_kernel(float *__restrict__ y, const float *__restrict__ bias, int64
         float v = y[i];
         if (bias) v += bias[i % cols];
         if (cutoff > 0.f) {
-            v = fminf(fmaxf(v, 0.f), cutoff);
+            v = relu_clip(v, cutoff);
             if (rate > 0.f) v = uniform01(seed, (uint64_t)i) >= rate ? v * inv_keep : 0.f;
         }
         y[i] = v;
@@ -41,8 +49,8 @@ bias_act_fwd_kernel_v4(float4 *__restrict__ y, const float4 *__restrict__ bias, 
             v.x += bb.x; v.y += bb.y; v.z += bb.z; v.w += bb.w;
         }
         if (cutoff > 0.f) {
-            v.x = fminf(fmaxf(v.x, 0.f), cutoff); v.y = fminf(fmaxf(v.y, 0.f), cutoff);
-            v.z = fminf(fmaxf(v.z, 0.f), cutoff); v.w = fminf(fmaxf(v.w, 0.f), cutoff);
+            v.x = relu_clip(v.x, cutoff); v.y = relu_clip(v.y, cutoff);
+            v.z = relu_clip(v.z, cutoff); v.w = relu_clip(v.w, cutoff);
             if (rate > 0.f) {
                 const uint64_t e = (uint64_t)i * 4;
                 v.x = uniform01(seed, e + 0) >= rate ? v.x * inv_keep : 0.f;

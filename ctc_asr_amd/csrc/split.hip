@@ -145,6 +145,10 @@ split_f16_cols_kernel(const float *__restrict__ x, int64_t ld_x, int64_t vecs, i
     unsigned h[2][8];
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
+        // (the rounded product, not an FMA into the remainder below: where x scale underflows
+        // the two differ in the sign of a zero second piece, and the pieces are defined bit
+        // for bit - tests/elementwise_reference.py)
+#pragma clang fp contract(off)
         const float s = f[i] * scale;
         const _Float16 h1 = (_Float16)s;
         const _Float16 h2 = (_Float16)(s - (float)h1);
@@ -197,6 +201,7 @@ split_f16_rows_kernel(const float *__restrict__ x, int64_t ld_x, int cols, int b
         unsigned h[2][8];
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
+#pragma clang fp contract(off)                               // (rounded: see split_f16_cols)
             const float s = f[u][i] * scale;
             const _Float16 h1 = (_Float16)s;
             const _Float16 h2 = (_Float16)(s - (float)h1);

@@ -229,6 +229,21 @@ def _stream():
     return torch.cuda.current_stream().cuda_stream
 
 
+def _expect_numel(what, name, tensor, want):
+    """The library takes raw pointers and trusts the lengths it is told: refuse an argument
+    that does not hold ``want`` elements before its address crosses the ABI."""
+    if tensor is not None and tensor.numel() != want:
+        raise CtcAsrError('{}: {} holds {} elements, {} expected.'
+                          .format(what, name, tensor.numel(), want))
+
+
+def _last_dim(what, name, tensor):
+    if tensor.dim() < 1 or tensor.shape[-1] < 1:
+        raise CtcAsrError('{}: {} needs a last dimension of at least one column (got shape {}).'
+                          .format(what, name, tuple(tensor.shape)))
+    return tensor.shape[-1]
+
+
 def _on_tensor_device(fn):
     """Run a launching wrapper with the device of its first GPU tensor argument current, so that
     the stream it launches on (`_stream`) and the memory it is given belong to the same GPU even
@@ -625,7 +640,10 @@ def rnn_bwd_f16_supported(cell, num_steps, batch, hidden, flags=RNN_F16):
 @_on_tensor_device
 def bias_act_fwd(y, bias, cutoff, dropout_rate=0.0, seed=0):
     """In place: y = dropout(min(max(y + bias, 0), cutoff)); cutoff <= 0 -> bias add only."""
-    cols = y.shape[-1]
+    cols = _last_dim('bias_act_fwd', 'y', y)
+    _expect_numel('bias_act_fwd', 'bias', bias, cols)
+    if y.numel() == 0:          # no rows: nothing to do (and an empty tensor has no address)
+        return y
     _check(load().ctcasr_bias_act_fwd(_dev(y, name='y'), _dev(bias, name='bias'),
                                       y.numel() // cols, cols, float(cutoff), float(dropout_rate),
                                       int(seed) & 0xFFFFFFFFFFFFFFFF, _stream()), 'bias_act_fwd')
@@ -634,8 +652,11 @@ def bias_act_fwd(y, bias, cutoff, dropout_rate=0.0, seed=0):
 
 @_on_tensor_device
 def bias_act_bwd(y, dy, cutoff, dropout_rate=0.0, dbias=None, dz=None):
-    cols = y.shape[-1]
+    cols = _last_dim('bias_act_bwd', 'y', y)
     dz = torch.empty_like(dy) if dz is None else dz
+    _expect_numel('bias_act_bwd', 'dy', dy, y.numel())
+    _expect_numel('bias_act_bwd', 'dz', dz, y.numel())
+    _expect_numel('bias_act_bwd', 'dbias', dbias, cols)
     _check(load().ctcasr_bias_act_bwd(_dev(y, name='y'), _dev(dy, name='dy'), _dev(dz, name='dz'),
                                       _dev(dbias, name='dbias'), y.numel() // cols, cols,
                                       float(cutoff), float(dropout_rate), _stream()),
@@ -647,6 +668,7 @@ def bias_act_bwd(y, dy, cutoff, dropout_rate=0.0, dbias=None, dz=None):
 def dropout(src, rate, seed, out=None):
     """out = src * mask(seed) / (1 - rate); same call (same seed) back-propagates a gradient."""
     out = torch.empty_like(src) if out is None else out
+    _expect_numel('dropout', 'out', out, src.numel())
     _check(load().ctcasr_dropout(_dev(src, name='src'), _dev(out, name='out'), src.numel(),
                                  float(rate), int(seed) & 0xFFFFFFFFFFFFFFFF, _stream()),
            'dropout')
@@ -655,7 +677,8 @@ def dropout(src, rate, seed, out=None):
 
 @_on_tensor_device
 def colsum_accumulate(dz, dbias):
-    cols = dz.shape[-1]
+    cols = _last_dim('colsum_accumulate', 'dz', dz)
+    _expect_numel('colsum_accumulate', 'dbias', dbias, cols)
     _check(load().ctcasr_colsum_accumulate(_dev(dz, name='dz'), _dev(dbias, name='dbias'),
                                            dz.numel() // cols, cols, _stream()),
            'colsum_accumulate')
@@ -750,8 +773,12 @@ def colmax_scale(x, scale=None, inv_scale=None):
     scale = torch.empty(cols, dtype=torch.float32, device=x.device) if scale is None else scale
     inv_scale = torch.empty(cols, dtype=torch.float32, device=x.device) \
         if inv_scale is None else inv_scale
+    _expect_numel('colmax_scale', 'scale', scale, cols)
+    _expect_numel('colmax_scale', 'inv_scale', inv_scale, cols)
     work = torch.empty(cols, dtype=torch.int32, device=x.device)
-    _check(load().ctcasr_colmax_scale(x.data_ptr(), rows, cols, x.stride(0) if rows > 1 else cols,
+    # (no rows: every scale is 1; an empty tensor has no address, the library wants one)
+    _check(load().ctcasr_colmax_scale(x.data_ptr() if rows else work.data_ptr(), rows, cols,
+                                      x.stride(0) if rows > 1 else cols,
                                       work.data_ptr(), _dev(scale, name='scale'),
                                       _dev(inv_scale, name='inv_scale'), _stream()), 'colmax_scale')
     return scale, inv_scale
@@ -764,6 +791,9 @@ def split_f16_cols(x, col_scale, scale, order, out=None):
     rows, cols = x.shape
     order = [int(v) for v in order]
     out = _f16_out(out, rows, len(order), cols, x.device)
+    if col_scale is None:
+        raise CtcAsrError('split_f16_cols: col_scale is required (one f32 scale per column).')
+    _expect_numel('split_f16_cols', 'col_scale', col_scale, cols)
     arr = (ctypes.c_int * len(order))(*order)
     _check(load().ctcasr_split_f16_cols(
         x.data_ptr(), rows, cols, x.stride(0) if rows > 1 else cols, _dev(col_scale, name='scale'),
@@ -1279,9 +1309,15 @@ def conv0_wrw(dz, x, out=None, act=None, relu_cutoff=0.0, dbias=None):
 @_on_tensor_device
 def transpose_batched(src, out=None):
     """src f32[N, R, C] -> out f32[N, C, R]."""
+    if src.dim() != 3:
+        raise CtcAsrError('transpose_batched: src must be [N, R, C] (got {} dimensions).'
+                          .format(src.dim()))
     batch, rows, cols = src.shape
     out = torch.empty((batch, cols, rows), dtype=torch.float32, device=src.device) \
         if out is None else out
+    if tuple(out.shape) != (batch, cols, rows):
+        raise CtcAsrError('transpose_batched: out must be [N, C, R] = {} (got {}).'
+                          .format((batch, cols, rows), tuple(out.shape)))
     _check(load().ctcasr_transpose_batched(_dev(src, name='src'), _dev(out, name='out'), batch,
                                            rows, cols, _stream()), 'transpose_batched')
     return out
@@ -1292,6 +1328,10 @@ def adam_step(param, grad, m, v, step, lr=1e-5, beta1=0.9, beta2=0.999, epsilon=
               grad_scale=1.0, skip=None):
     """TensorFlow-form Adam over the flat arenas.  ``skip`` (optional int32 device tensor): the
     update is dropped on the device when skip[0] != 0 (`step_guard`)."""
+    for name, tensor in (('grad', grad), ('m', m), ('v', v)):
+        _expect_numel('adam_step', name, tensor, param.numel())
+    if skip is not None and skip.numel() < 1:
+        raise CtcAsrError('adam_step: skip holds no word.')
     _check(load().ctcasr_adam_step(_dev(param, name='param'), _dev(grad, name='grad'),
                                    _dev(m, name='m'), _dev(v, name='v'), param.numel(), float(lr),
                                    float(beta1), float(beta2), float(epsilon), int(step),
@@ -1317,8 +1357,11 @@ def step_guard(status, per_utterance_loss, timeout_words=(0, 0), out=None, wgrad
     `wgrad16_gemm` tile on this device that gave up waiting for its turn), [1] = the time-out words
     or-ed (bit 30: the weight-gradient word).  Everything stays on the device
     (`adam_step(skip=out)`)."""
+    _expect_numel('step_guard', 'per_utterance_loss', per_utterance_loss, status.numel())
     if out is None:
         out = torch.empty(2, dtype=torch.int32, device=status.device)
+    elif out.numel() < 2:
+        raise CtcAsrError('step_guard: out holds {} words, 2 needed.'.format(out.numel()))
     sync = _WGRAD16_SYNC.get(status.device.index) if wgrad_word else None
     _check(load().ctcasr_step_guard(_dev(status, torch.int32, 'status'),
                                     _dev(per_utterance_loss, name='per_utterance_loss'),
@@ -1348,6 +1391,8 @@ def collective_traffic(scratch_a, scratch_b, workgroups, busy_us, payload_bytes)
 @_on_tensor_device
 def absmax(x, out):
     """out (one int32 word, zeroed by the caller) = max(out, bit pattern of max |x|)."""
+    if out.numel() < 1:
+        raise CtcAsrError('absmax: out holds no word.')
     _check(load().ctcasr_absmax(_dev(x.reshape(-1), name='x'), x.numel(),
                                 _dev(out, torch.int32, 'out'), _stream()), 'absmax')
     return out
