@@ -132,11 +132,15 @@ transpose_kernel(const float *__restrict__ in, float *__restrict__ out, int rows
 __global__ void __launch_bounds__(256)
 adam_kernel(float *__restrict__ p, const float *__restrict__ g, float *__restrict__ m,
             float *__restrict__ v, int64_t n, float lr_t, float b1, float b2, float eps,
-            float gscale, const int32_t *__restrict__ skip) {
+            float gscale, const int32_t *__restrict__ skip,
+            const float *__restrict__ gfactor) {
     // a step whose gradients are known to be garbage (infeasible CTC alignment, non-finite loss,
     // a persistent recurrence that gave up at a barrier: ctcasr_step_guard) must not touch the
     // parameters or the moments - decided on the device, the host finds out later
     if (skip && *skip) return;
+    // the clip factor of ctcasr_grad_norm, still on the device: one fp32 product with the scale,
+    // formed once (a factor of exactly 1 leaves gscale, and with it every result, as it was)
+    if (gfactor) gscale *= *gfactor;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     const int64_t n4 = n >> 2;
     float4 *p4 = reinterpret_cast<float4 *>(p);
@@ -333,9 +337,11 @@ extern "C" int ctcasr_transpose_batched(const float *in, float *out, int batch, 
     return ctcasr_launch_status();
 }
 
-extern "C" int ctcasr_adam_step(float *param, const float *grad, float *m, float *v, int64_t n,
-                                float lr, float beta1, float beta2, float epsilon, int64_t step,
-                                float grad_scale, const int32_t *skip, ctcasr_stream_t stream) {
+extern "C" int ctcasr_adam_step_clipped(float *param, const float *grad, float *m, float *v,
+                                        int64_t n, float lr, float beta1, float beta2,
+                                        float epsilon, int64_t step, float grad_scale,
+                                        const int32_t *skip, const float *grad_factor,
+                                        ctcasr_stream_t stream) {
     if (!param || !grad || !m || !v || n < 0 || step < 1) return CTCASR_ERR_BAD_ARGUMENT;
     if (n == 0) return CTCASR_OK;
     if ((reinterpret_cast<uintptr_t>(param) | reinterpret_cast<uintptr_t>(grad) |
@@ -352,8 +358,15 @@ extern "C" int ctcasr_adam_step(float *param, const float *grad, float *m, float
     int64_t want = (n / 4 + 1 + 255) / 256;
     const int blocks = (int)(want > ADAM_BLOCKS ? ADAM_BLOCKS : want < 1 ? 1 : want);
     adam_kernel<<<blocks, 256, 0, (hipStream_t)stream>>>(
-        param, grad, m, v, n, (float)lr_t, beta1, beta2, epsilon, grad_scale, skip);
+        param, grad, m, v, n, (float)lr_t, beta1, beta2, epsilon, grad_scale, skip, grad_factor);
     return ctcasr_launch_status();
+}
+
+extern "C" int ctcasr_adam_step(float *param, const float *grad, float *m, float *v, int64_t n,
+                                float lr, float beta1, float beta2, float epsilon, int64_t step,
+                                float grad_scale, const int32_t *skip, ctcasr_stream_t stream) {
+    return ctcasr_adam_step_clipped(param, grad, m, v, n, lr, beta1, beta2, epsilon, step,
+                                    grad_scale, skip, nullptr, stream);
 }
 
 extern "C" int ctcasr_step_guard(const int32_t *ctc_status, const float *per_utterance_loss,

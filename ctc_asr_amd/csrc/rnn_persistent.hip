@@ -4152,10 +4152,16 @@ size_t prnn_sync_bytes() { return sizeof(SyncWords); }
 // 0 = the default - for the test of that path).  Which variant of a persistent kernel runs is a
 // per-call argument (`flags` of ctcasr_rnn_fwd_steps / _bwd_steps).
 void wgrad16_set_spin_limit(long polls);      // (wgrad16.hip)
+extern int g_grad_norm_blocks;                // (grad_norm.hip)
 extern "C" int ctcasr_set_option(const char *name, int value) {
     if (!name) return CTCASR_ERR_BAD_ARGUMENT;
     if (strcmp(name, "rnn_kernel_events") == 0) { g_kernel_events = value ? 1 : 0; return CTCASR_OK; }
     if (strcmp(name, "wgrad16_spin_limit") == 0) { wgrad16_set_spin_limit(value); return CTCASR_OK; }
+    if (strcmp(name, "grad_norm_blocks") == 0) {
+        if (value < 0 || value > 65536) return CTCASR_ERR_BAD_ARGUMENT;
+        g_grad_norm_blocks = value;
+        return CTCASR_OK;
+    }
     return CTCASR_ERR_BAD_ARGUMENT;
 }
 

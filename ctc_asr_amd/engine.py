@@ -197,8 +197,22 @@ class Trainer:
 
     def __init__(self, cfg, flags=None, device=None, seed=0, params=None, world_size=1, rank=0,
                  bucket_bytes=64 << 20, conv_autotune=None, allreduce_early=None,
-                 force_reducer=False, reduce=True, collective_stand_in=None):
+                 force_reducer=False, reduce=True, collective_stand_in=None, max_grad_norm=None,
+                 report_grad_norms=None):
         self.world, self.rank = world_size, rank
+        # Clipping by global norm (``max_grad_norm`` > 0) and the per-layer norms
+        # (``report_grad_norms``): keyword arguments, else the flags of the same names, else off.
+        # With both off `train_step` launches exactly what it launches without them.
+        if max_grad_norm is None:
+            max_grad_norm = getattr(flags, 'max_grad_norm', 0.0) if flags is not None else 0.0
+        if report_grad_norms is None:
+            report_grad_norms = getattr(flags, 'report_grad_norms', False) \
+                if flags is not None else False
+        self.max_grad_norm = float(max_grad_norm)
+        self.report_grad_norms = bool(report_grad_norms)
+        self.last_grad_norms = None     # device float32: per layer (`CTCModel.grad_norm_names`)
+        self.last_clip_factor = None    # ... then the global norm; device float32[1]
+        self._clipped = None
         device = device or 'cuda:{}'.format(torch.cuda.current_device())
         self.model = CTCModel(cfg, device, seed=seed, params=params, conv_autotune=conv_autotune)
         self.lr = getattr(flags, 'learning_rate', 1e-5) if flags is not None else 1e-5
@@ -264,7 +278,7 @@ class Trainer:
         """Raise for any finished step whose CTC status reported an infeasible alignment /
         bad labels (``wait``: block until every pending step has finished)."""
         while self._pending_status:
-            event, host, step = self._pending_status[0]
+            event, host, step, norm_host = self._pending_status[0]
             if not wait and not event.query():
                 break
             event.synchronize()
@@ -283,6 +297,12 @@ class Trainer:
                 raise NanLossDuringTrainingError(
                     'NaN loss during training. [non-finite CTC loss in training step {}; its '
                     'update was not applied]'.format(step))
+            if norm_host is not None and not torch.isfinite(norm_host).all():
+                # a finite loss whose gradients hold an inf or a NaN: `ctcasr_grad_norm` raised the
+                # guard word itself
+                raise NanLossDuringTrainingError(
+                    'Non-finite gradients during training. [non-finite gradient norm in training '
+                    'step {}; its update was not applied]'.format(step))
 
     def drain_checks(self):
         """Wait for the steps in flight and raise what they have to report: CTC status of every
@@ -302,8 +322,8 @@ class Trainer:
             self._skipped_reconciled = dropped
             self.model.step_count -= new
             warnings.warn('{} training step(s) were dropped on the device (CTC status, non-finite '
-                          'loss or a kernel time-out); the step counter is back at {}.'.format(
-                              new, self.model.step_count), RuntimeWarning)
+                          'loss or gradient norm, or a kernel time-out); the step counter is back '
+                          'at {}.'.format(new, self.model.step_count), RuntimeWarning)
 
     def train_step(self, features, feature_len, labels, check=True):
         """forward + CTC + backward (+ all-reduce) + Adam on this rank's shard of the global
@@ -315,8 +335,10 @@ class Trainer:
         (where ``tf.nn.ctc_loss`` raises), a non-finite loss or a timed-out persistent kernel
         surfaces at most `max_steps_ahead` steps after the step that hit it (the guard word
         travels to pinned memory with the CTC status), and always before a checkpoint is
-        written.  Either way that step's update is dropped ON THE DEVICE (`CTCModel.step_guard`
-        -> the Adam kernel's skip flag): parameters and moments never see its gradients."""
+        written; with `max_grad_norm` / `report_grad_norms` on, so does a gradient norm that is
+        not finite behind a finite loss.  Either way that step's update is dropped ON THE DEVICE
+        (`CTCModel.step_guard` -> the Adam kernel's skip flag): parameters and moments never see
+        its gradients."""
         if len(self._step_done) >= self.max_steps_ahead:
             t0 = time.perf_counter()
             while len(self._step_done) >= self.max_steps_ahead:
@@ -338,22 +360,45 @@ class Trainer:
         # (N > 1: the guard words are max-reduced with the gradients, every replica drops the
         # step that one of them must not apply; the rank that hit it raises.)
         guard = self.model.step_guard()
+        norms_on = self.max_grad_norm > 0 or self.report_grad_norms
         if check:
             status = self.model.last_status
             host = torch.empty(status.numel() + 2, dtype=status.dtype, pin_memory=True)
             host[:status.numel()].copy_(status, non_blocking=True)
             host[status.numel():].copy_(guard, non_blocking=True)
-            copied = torch.cuda.Event()
-            copied.record(torch.cuda.current_stream(self.model.device))
-            self._pending_status.append((copied, host, self.model.step_count + 1))
+            if not norms_on:
+                copied = torch.cuda.Event()
+                copied.record(torch.cuda.current_stream(self.model.device))
+                self._pending_status.append((copied, host, self.model.step_count + 1, None))
         self.reducer.finish(guard)      # (N > 1: the guard words become their maxima over ranks)
+        grad_factor = None
+        if norms_on:
+            # AFTER the all-reduce, on the summed gradients: every rank then reads bit-identical
+            # values, the kernel's summation order is fixed, so every rank computes the identical
+            # norm and the identical factor (and raises the guard word on the same steps) - the
+            # replicas stay replicated without another collective.  1 / world: the norm of the
+            # MEAN gradient, what Adam applies.  Nothing comes back to the host here: the factor
+            # stays on the device and the Adam kernel reads it.
+            norms, grad_factor = self.model.grad_norms(1.0 / self.world, self.max_grad_norm, guard)
+            self.last_grad_norms, self.last_clip_factor = norms, grad_factor
+            if self._clipped is None:
+                self._clipped = torch.zeros(1, dtype=torch.int32, device=self.model.device)
+            # (a factor of 0 is a dropped step - `skipped_step_count()` - not a clipped one)
+            self._clipped += ((grad_factor > 0) & (grad_factor < 1)).to(torch.int32)
+            if check:
+                norm_host = torch.empty(1, dtype=torch.float32, pin_memory=True)
+                norm_host.copy_(norms[-1:], non_blocking=True)
+                copied = torch.cuda.Event()
+                copied.record(torch.cuda.current_stream(self.model.device))
+                self._pending_status.append((copied, host, self.model.step_count + 1, norm_host))
         # (how many updates the device has dropped so far: `skipped_step_count()` - a run whose
         # steps were silently skipped must not be reported as throughput)
         if self._skipped is None:
             self._skipped = torch.zeros(1, dtype=torch.int32, device=self.model.device)
         self._skipped += (guard[:1] != 0).to(torch.int32)
         self.model.apply_gradients(self.lr, self.beta1, self.beta2, self.eps,
-                                   grad_scale=1.0 / self.world, skip=guard)
+                                   grad_scale=1.0 / self.world, skip=guard,
+                                   grad_factor=grad_factor)
         done = torch.cuda.Event()
         done.record(torch.cuda.current_stream(self.model.device))
         self._step_done.append(done)
@@ -366,6 +411,12 @@ class Trainer:
         `drain_checks()` takes it back out.  A dropped step always raises at the next check of
         `train_step(check=True)` / `drain_checks()`."""
         return 0 if self._skipped is None else int(self._skipped.item())
+
+    def clipped_step_count(self):
+        """Training steps whose gradients were scaled down to `max_grad_norm` (clip factor below
+        1; a step dropped for a non-finite norm counts as skipped, not clipped) since this trainer
+        was built; synchronises."""
+        return 0 if self._clipped is None else int(self._clipped.item())
 
     def global_mean(self, value):
         """Average a device scalar over ranks (logged loss, eval metrics)."""

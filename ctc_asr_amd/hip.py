@@ -22,6 +22,9 @@ RNN_F16 = 16          # persistent LSTM / GRU kernels: the recurrent products as
 RNN_XCD_SPLIT = 32    # fp16-pipe kernels: one direction per half of the XCDs
 RNN_STAGGER = 64      # fp16-pipe LSTM-1024 backward, 24 / 32 rows: tiles staggered by half a step
 RNN_KPAIR = 128       # ... and the K axis split over pairs of workgroups (ABI v7)
+# ctcasr_grad_norm: floats per chunk of a segment, and the most segments a call takes
+GRAD_NORM_CHUNK = 8192
+GRAD_NORM_MAX_SEGMENTS = 64
 CELL_IDS = {'rnn_relu': 0, 'rnn_tanh': 1, 'lstm': 2, 'gru': 3}
 CELL_GATES = {'rnn_relu': 1, 'rnn_tanh': 1, 'lstm': 4, 'gru': 3}
 
@@ -133,6 +136,11 @@ SIGNATURES = {
     'ctcasr_features': (_c_int, [_c_p, _c_p] + [_c_int] * 5 + [_c_p, _c_p, _c_int, _c_p, _c_p,
                                  _c_sz, _c_p]),
     'ctcasr_adam_step': (_c_int, [_c_p] * 4 + [_c_i64] + [_c_f] * 4 + [_c_i64, _c_f, _c_p, _c_p]),
+    'ctcasr_adam_step_clipped': (_c_int, [_c_p] * 4 + [_c_i64] + [_c_f] * 4 +
+                                 [_c_i64, _c_f, _c_p, _c_p, _c_p]),
+    'ctcasr_grad_norm_workspace_bytes': (_c_sz, [_c_i64, _c_int]),
+    'ctcasr_grad_norm': (_c_int, [_c_p, _c_i64, _c_p, _c_int, _c_f, _c_f] + [_c_p] * 4 +
+                         [_c_sz, _c_p]),
     'ctcasr_step_guard': (_c_int, [_c_p, _c_p, _c_int, _c_p, _c_p, _c_p, _c_p, _c_p]),
     'ctcasr_rnn_timeout_word_offset': (_c_sz, [_c_int] * 5),
     'ctcasr_absmax': (_c_int, [_c_p, _c_i64, _c_p, _c_p]),
@@ -1325,18 +1333,72 @@ def transpose_batched(src, out=None):
 
 @_on_tensor_device
 def adam_step(param, grad, m, v, step, lr=1e-5, beta1=0.9, beta2=0.999, epsilon=1e-8,
-              grad_scale=1.0, skip=None):
+              grad_scale=1.0, skip=None, grad_factor=None):
     """TensorFlow-form Adam over the flat arenas.  ``skip`` (optional int32 device tensor): the
-    update is dropped on the device when skip[0] != 0 (`step_guard`)."""
+    update is dropped on the device when skip[0] != 0 (`step_guard`).  ``grad_factor`` (optional
+    float32 device tensor of one element, `grad_norm`'s clip factor): the gradients are scaled by
+    ``grad_scale * grad_factor[0]``, one float32 product, without the host reading the factor."""
     for name, tensor in (('grad', grad), ('m', m), ('v', v)):
         _expect_numel('adam_step', name, tensor, param.numel())
     if skip is not None and skip.numel() < 1:
         raise CtcAsrError('adam_step: skip holds no word.')
+    if grad_factor is not None:
+        _expect_numel('adam_step', 'grad_factor', grad_factor, 1)
+        _check(load().ctcasr_adam_step_clipped(
+            _dev(param, name='param'), _dev(grad, name='grad'), _dev(m, name='m'),
+            _dev(v, name='v'), param.numel(), float(lr), float(beta1), float(beta2),
+            float(epsilon), int(step), float(grad_scale), _dev(skip, torch.int32, 'skip'),
+            _dev(grad_factor, name='grad_factor'), _stream()), 'adam_step')
+        return
     _check(load().ctcasr_adam_step(_dev(param, name='param'), _dev(grad, name='grad'),
                                    _dev(m, name='m'), _dev(v, name='v'), param.numel(), float(lr),
                                    float(beta1), float(beta2), float(epsilon), int(step),
                                    float(grad_scale), _dev(skip, torch.int32, 'skip'), _stream()),
            'adam_step')
+
+
+def grad_norm_workspace_bytes(n, segments):
+    return load().ctcasr_grad_norm_workspace_bytes(int(n), int(segments))
+
+
+@_on_tensor_device
+def grad_norm(grad, seg_offsets, grad_scale=1.0, max_norm=0.0, skip=None, out=None,
+              workspace=None):
+    """Norms of the segments of the flat float32 ``grad`` and what follows from them, all on the
+    device: returns ``(norms, clip_factor)`` - ``norms`` float32[segments + 1], one per segment
+    and the global norm last, each ``grad_scale * sqrt(sum x^2)`` summed in float64 in a fixed
+    order; ``clip_factor`` float32[1] = ``max_norm / global`` where that clips, 0 when the global
+    norm is not finite, else exactly 1 (`adam_step(grad_factor=...)`).  ``seg_offsets``: int64
+    device tensor [segments + 1], ascending from 0 to ``grad.numel()``, interior entries multiples
+    of 4.  ``skip`` (the words of `step_guard`): [0] is raised when the global norm is not
+    finite, never cleared.  ``out``: a float32 device tensor of segments + 2 elements to hold the
+    norms followed by the factor; ``workspace``: uint8, `grad_norm_workspace_bytes`."""
+    segments = seg_offsets.numel() - 1
+    if segments < 1:
+        raise CtcAsrError('grad_norm: seg_offsets holds {} offsets, at least 2 needed.'
+                          .format(seg_offsets.numel()))
+    if segments > GRAD_NORM_MAX_SEGMENTS:
+        raise CtcAsrError('grad_norm: {} segments, at most {} supported.'
+                          .format(segments, GRAD_NORM_MAX_SEGMENTS))
+    if skip is not None and skip.numel() < 1:
+        raise CtcAsrError('grad_norm: skip holds no word.')
+    if out is None:
+        out = torch.empty(segments + 2, dtype=torch.float32, device=grad.device)
+    _expect_numel('grad_norm', 'out', out, segments + 2)
+    need = grad_norm_workspace_bytes(grad.numel(), segments)
+    if workspace is None:
+        workspace = _workspace(need, grad.device)
+    elif workspace.numel() < need:
+        raise CtcAsrError('grad_norm: workspace holds {} bytes, {} needed.'
+                          .format(workspace.numel(), need))
+    out_ptr = _dev(out, name='out')
+    _check(load().ctcasr_grad_norm(_dev(grad, name='grad'), grad.numel(),
+                                   _dev(seg_offsets, torch.int64, 'seg_offsets'), segments,
+                                   float(grad_scale), float(max_norm), out_ptr,
+                                   out_ptr + 4 * (segments + 1), _dev(skip, torch.int32, 'skip'),
+                                   _dev(workspace, torch.uint8, 'workspace'), workspace.numel(),
+                                   _stream()), 'grad_norm')
+    return out[:segments + 1], out[segments + 1:]
 
 
 def rnn_timeout_words(cell, workspace, num_steps, batch, hidden):

@@ -388,6 +388,7 @@ class CTCModel:
         if self.device.type != 'cuda':
             raise hip.CtcAsrError('CTCModel runs on the MI355X only; there is no CPU path.')
         self.arena = ParamArena(cfg, self.device)
+        self._grad_norm_state = None    # (offset table, workspace, result) of `grad_norms`
         self.arena.load(params if params is not None else init_params(cfg, seed))
         self.step_count = 0
         # weight-gradient GEMMs run on a low-priority side stream so that they fill the half of
@@ -1802,15 +1803,43 @@ class CTCModel:
                                           cfg.num_units_rnn)
         return hip.step_guard(self.last_status, self.last_per_utterance_loss, words)
 
+    @property
+    def grad_norm_names(self):
+        """Layer names in the order of the segments of `grad_norms` (the arena's layer slices);
+        the global norm follows them."""
+        return [name for name, _, _ in self.arena.layer_slices]
+
+    def grad_norms(self, grad_scale=1.0, max_norm=0.0, skip=None):
+        """(norms, clip_factor) of the gradient arena as it stands, on the device
+        (`hip.grad_norm`): one norm per layer slice in `grad_norm_names` order and the global
+        norm last, each times ``grad_scale``; the factor that brings the global norm down to
+        ``max_norm`` (1 where it need not, 0 - and ``skip[0]`` raised - where the norm is not
+        finite), for `apply_gradients(grad_factor=...)`.  The offset table, the workspace and the
+        result live as long as the model: a call allocates nothing and returns views of the same
+        tensor every time."""
+        if self._grad_norm_state is None:
+            slices = self.arena.layer_slices
+            offsets = torch.tensor([slices[0][1]] + [stop for _, _, stop in slices],
+                                   dtype=torch.int64, device=self.device)
+            workspace = torch.empty(
+                max(hip.grad_norm_workspace_bytes(self.arena.size, len(slices)), 256),
+                dtype=torch.uint8, device=self.device)
+            out = torch.zeros(len(slices) + 2, dtype=torch.float32, device=self.device)
+            self._grad_norm_state = (offsets, workspace, out)
+        offsets, workspace, out = self._grad_norm_state
+        return hip.grad_norm(self.arena.grad, offsets, grad_scale, max_norm, skip=skip, out=out,
+                             workspace=workspace)
+
     def apply_gradients(self, learning_rate=1e-5, beta1=0.9, beta2=0.999, epsilon=1e-8,
-                        grad_scale=1.0, skip=None):
+                        grad_scale=1.0, skip=None, grad_factor=None):
         """TensorFlow-form Adam over the whole arena in one launch (``asr/model.py:80-83``).
         ``skip``: the device flag of `step_guard` - parameters and moments stay untouched when
-        it is set (the step counter still advances)."""
+        it is set (the step counter still advances).  ``grad_factor``: the device-side clip
+        factor of `grad_norms`, multiplied into ``grad_scale`` by the kernel."""
         self.step_count += 1
         a = self.arena
         hip.adam_step(a.param, a.grad, a.m, a.v, self.step_count, learning_rate, beta1, beta2,
-                      epsilon, grad_scale, skip=skip)
+                      epsilon, grad_scale, skip=skip, grad_factor=grad_factor)
 
     # ------------------------------------------------------------------ estimator-style entry
     def model_fn(self, features, labels, mode, learning_rate=1e-5, adam=(0.9, 0.999, 1e-8)):

@@ -175,6 +175,13 @@ FLAGS.define('float', 'adam_beta1', 0.9, 'First-moment decay.')
 FLAGS.define('float', 'adam_beta2', 0.999, 'Second-moment decay.')
 FLAGS.define('float', 'adam_epsilon', 1e-8, 'Added to sqrt(v) (TensorFlow form).')
 
+# Gradient clipping by global norm and the per-layer norms (no counterpart in the reference, which
+# does not clip; both off: the training step launches what it always did).
+FLAGS.define('float', 'max_grad_norm', 0.0,
+             'Scale the gradients of a step so that their global L2 norm is at most this (0: off).')
+FLAGS.define('bool', 'report_grad_norms', False,
+             'Compute the global and per-layer gradient norms every step and log them.')
+
 # CTC decoder (asr/params.py:84-86).
 FLAGS.define('int', 'beam_width', 1024, 'Leaves kept by the CTC beam search (<= 1024).')
 
@@ -263,4 +270,9 @@ def get_parameters():
             FLAGS.feature_type, FLAGS.feature_normalization,
             FLAGS.features_drop_every_second_frame),
     ]
+    if FLAGS.max_grad_norm > 0 or FLAGS.report_grad_norms:
+        # (a row of its own, and only when switched on: the summary of a default run stays the
+        # reference's, line for line)
+        rows.append('\tGradients (max_grad_norm={}, report_grad_norms={});'.format(
+            FLAGS.max_grad_norm, FLAGS.report_grad_norms))
     return '\n'.join(rows)

@@ -50,8 +50,14 @@ def train_epoch(trainer, target, epoch, rank, world, writer=None, seed=None):
             if not math.isfinite(value):
                 raise NanLossDuringTrainingError('NaN loss during training.')
             window_loss = value
+            # (--max_grad_norm / --report_grad_norms: the norms of the step just read, identical
+            # on every rank; the host is synchronised here anyway)
+            grad_norms = None if trainer.last_grad_norms is None \
+                else trainer.last_grad_norms.tolist()
             if rank == 0:
                 line, examples_per_sec, audio_per_sec = logger.line(model.step_count, value)
+                if grad_norms is not None:
+                    line += '; grad_norm={:.4g}'.format(grad_norms[-1])
                 print('epoch {} '.format(epoch) + line)
                 if writer is not None:
                     decoded, plaintext, summary = model.decode_fn(
@@ -68,6 +74,12 @@ def train_epoch(trainer, target, epoch, rank, world, writer=None, seed=None):
                     writer.scalar('Metrics/word_error_rate', wer, step)
                     writer.scalar('examples_per_sec', examples_per_sec, step)
                     writer.scalar('audio_seconds_per_sec', audio_per_sec, step)
+                    if grad_norms is not None:
+                        writer.scalar('grad_norm', grad_norms[-1], step)
+                        for name, norm in zip(model.grad_norm_names, grad_norms):
+                            writer.scalar('grad_norm/' + name, norm, step)
+                        writer.scalar('clip_factor', float(trainer.last_clip_factor), step)
+                        writer.scalar('clipped_steps', trainer.clipped_step_count(), step)
                     writer.text('decoded_text', summary[:, :FLAGS.num_samples_to_report], step)
             else:
                 logger.line(model.step_count, value)

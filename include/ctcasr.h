@@ -647,6 +647,58 @@ int ctcasr_adam_step(float *param, const float *grad, float *m, float *v, int64_
 int ctcasr_step_guard(const int32_t *ctc_status, const float *per_utterance_loss, int batch,
                       const uint32_t *timeout_word0, const uint32_t *timeout_word1,
                       const int32_t *wgrad_word, int32_t *skip, ctcasr_stream_t stream);
+/* The same launch with a factor that is still on the device (ctcasr_grad_norm's clip_factor):
+ *   gr = grad[i] * (grad_scale * *grad_factor),   the inner product formed once in fp32.
+ * grad_factor == NULL is a factor of 1 - ctcasr_adam_step is this call with NULL - and a factor of
+ * exactly 1.0f gives that call's results bit for bit.  `skip` still wins over any factor. */
+int ctcasr_adam_step_clipped(float *param, const float *grad, float *m, float *v, int64_t n,
+                             float lr, float beta1, float beta2, float epsilon, int64_t step,
+                             float grad_scale, const int32_t *skip, const float *grad_factor,
+                             ctcasr_stream_t stream);
+
+/* ---- K14: gradient norms per segment, global norm, clip factor, guard -------------------------
+ * No counterpart in the reference (it does not clip).  One read of grad; nothing leaves the
+ * device, so the optimizer can be enqueued behind it without the host knowing a norm.
+ *   grad         fp32 [n], 16-byte aligned (the flat gradient arena)
+ *   seg_offsets  DEVICE int64 [segments + 1], ascending, [0] = 0, [segments] = n, every interior
+ *                offset a multiple of 4 (the arena starts every tensor on 16 bytes; its layer
+ *                slices are the segments).  Empty segments are allowed.  A table that breaks these
+ *                rules never makes the kernels read outside grad[0, n): they clamp every entry
+ *                into [0, n], make the table ascending and round every entry but the last down to
+ *                a multiple of 4 - the norms of such a table mean nothing.
+ *   norms        fp32 [segments + 1]: norms[s] = f32(grad_scale * sqrt(sum of x^2 over segment s)),
+ *                norms[segments] = the same over all segments, the global norm.
+ *   clip_factor  fp32 [1]: max_norm / global (ONE IEEE fp32 division of the two fp32 values) when
+ *                max_norm > 0 and global > max_norm; 0.0f when the global norm as fp32 is NaN or
+ *                +-inf (whatever max_norm is); exactly 1.0f otherwise.
+ *   skip         optional: the words of ctcasr_step_guard.  skip[0] = 1 when the global norm as
+ *                fp32 is not finite; otherwise left as it is (never cleared).  skip[1] untouched.
+ *   workspace    ctcasr_grad_norm_workspace_bytes(n, segments) bytes, 8-byte aligned (chunk sums;
+ *                nothing is allocated behind the caller).
+ * Arithmetic (pinned, like the tie rules of the decoders): every square is formed and added in
+ * fp64 - (double)x * (double)x is exact.  The order is fixed by the layout alone: each segment is
+ * cut, FROM ITS OWN START, into chunks of CTCASR_GRAD_NORM_CHUNK floats.  In a chunk, with
+ * q = index of a group of four floats, lane t = q % 256 adds the squares of its groups in
+ * ascending q, x y z w inside a group, starting from +0 (elements past the end of a short chunk
+ * count as +0); lanes 64w .. 64w + 63 are added by butterfly (v += v[lane ^ 32], ^ 16, ... ^ 1),
+ * the four w as ((w0 + w1) + w2) + w3.  A segment's chunk sums: lane l = chunk % 64 adds its
+ * chunks in ascending order, the 64 lanes by the same butterfly.  The global sum adds the segment
+ * sums in index order starting from +0.  Each norm: sqrt in fp64, times (double)grad_scale, ONE
+ * rounding to fp32.  No float atomics.  Hence: results are bit-reproducible, independent of the
+ * grid size, and norms[s] depends on the values and the length of segment s only - not on where
+ * the segment sits in grad, on `segments`, or on its neighbours.
+ * Errors: null grad (n > 0) / seg_offsets / norms / clip_factor, n < 0, segments < 1, grad not
+ * 16-byte aligned: CTCASR_ERR_BAD_ARGUMENT; segments > CTCASR_GRAD_NORM_MAX_SEGMENTS:
+ * CTCASR_ERR_UNSUPPORTED; workspace null, short or misaligned: CTCASR_ERR_WORKSPACE.
+ * ctcasr_set_option("grad_norm_blocks", k), 0 <= k <= 65536, sets the workgroup count of the
+ * reading launch (0: the default) - a tuning knob that changes no result. */
+#define CTCASR_GRAD_NORM_CHUNK 8192
+#define CTCASR_GRAD_NORM_MAX_SEGMENTS 64
+size_t ctcasr_grad_norm_workspace_bytes(int64_t n, int segments);
+int ctcasr_grad_norm(const float *grad, int64_t n, const int64_t *seg_offsets, int segments,
+                     float grad_scale, float max_norm, float *norms, float *clip_factor,
+                     int32_t *skip, void *workspace, size_t workspace_bytes,
+                     ctcasr_stream_t stream);
 /* byte offset inside the recurrence workspace of the sticky time-out word of row block `block`
  * (0 .. (B - 1) / 32), or (size_t)-1 when (cell, T, B, H) runs the streaming kernels / there is
  * no such block */
