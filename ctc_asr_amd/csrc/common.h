@@ -16,6 +16,21 @@ static inline int ctcasr_launch_status() {
 
 static inline size_t ctcasr_align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
+// splitmix64 finaliser over (seed, counter): the one counter-based generator of the library.
+// Dropout takes its top 24 bits as a uniform in [0, 1) (elementwise.hip), the augmentation draws
+// take them as an integer (augment.hip; pinned in include/ctcasr.h).
+__host__ __device__ __forceinline__ uint64_t splitmix64_mix(uint64_t seed, uint64_t idx) {
+    uint64_t z = seed + 0x9E3779B97F4A7C15ull * (idx + 1);
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    z ^= z >> 31;
+    return z;
+}
+// its top 24 bits
+__host__ __device__ __forceinline__ uint32_t splitmix64_r24(uint64_t seed, uint64_t idx) {
+    return (uint32_t)(splitmix64_mix(seed, idx) >> 40);
+}
+
 __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));

@@ -6,12 +6,9 @@
 namespace {
 
 // counter-based uniform in [0, 1): splitmix64 finaliser over (seed, element index)
+// (splitmix64_r24 of common.h)
 __device__ __forceinline__ float uniform01(uint64_t seed, uint64_t idx) {
-    uint64_t z = seed + 0x9E3779B97F4A7C15ull * (idx + 1);
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    z ^= z >> 31;
-    return (float)(z >> 40) * (1.0f / 16777216.0f);
+    return (float)splitmix64_r24(seed, idx) * (1.0f / 16777216.0f);
 }
 
 // min(max(v, 0), cutoff) that keeps a NaN: fmaxf(NaN, 0) is 0, which would hand a finite

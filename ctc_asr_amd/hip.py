@@ -25,6 +25,7 @@ RNN_KPAIR = 128       # ... and the K axis split over pairs of workgroups (ABI v
 # ctcasr_grad_norm: floats per chunk of a segment, and the most segments a call takes
 GRAD_NORM_CHUNK = 8192
 GRAD_NORM_MAX_SEGMENTS = 64
+SPEC_AUGMENT_MAX_MASKS = 16     # ctcasr_spec_augment: frequency masks, and time masks, per call
 CELL_IDS = {'rnn_relu': 0, 'rnn_tanh': 1, 'lstm': 2, 'gru': 3}
 CELL_GATES = {'rnn_relu': 1, 'rnn_tanh': 1, 'lstm': 4, 'gru': 3}
 
@@ -135,6 +136,10 @@ SIGNATURES = {
     'ctcasr_features_workspace_bytes': (_c_sz, [_c_int, _c_int]),
     'ctcasr_features': (_c_int, [_c_p, _c_p] + [_c_int] * 5 + [_c_p, _c_p, _c_int, _c_p, _c_p,
                                  _c_sz, _c_p]),
+    'ctcasr_spec_augment': (_c_int, [_c_p, _c_p, _c_int, _c_int, _c_u64] + [_c_int] * 5 +
+                            [_c_p, _c_p]),
+    'ctcasr_resample_num_samples': (_c_int, [_c_int, _c_int]),
+    'ctcasr_speed_perturb': (_c_int, [_c_p, _c_p, _c_p, _c_int, _c_int, _c_p, _c_int, _c_p, _c_p]),
     'ctcasr_adam_step': (_c_int, [_c_p] * 4 + [_c_i64] + [_c_f] * 4 + [_c_i64, _c_f, _c_p, _c_p]),
     'ctcasr_adam_step_clipped': (_c_int, [_c_p] * 4 + [_c_i64] + [_c_f] * 4 +
                                  [_c_i64, _c_f, _c_p, _c_p, _c_p]),
@@ -1499,3 +1504,80 @@ def features(pcm, num_samples, feature_type='mel', normalization='local',
         _dev(out, name='out'), out.shape[1], _dev(out_len, torch.int32, 'out_len'),
         _dev(workspace, torch.uint8, 'workspace'), workspace.numel(), _stream()), 'features')
     return out, out_len
+
+
+def _batch_of(what, name, tensor, batch):
+    """One entry per row of the batch, or a message that names both numbers."""
+    if tensor.numel() != batch:
+        raise CtcAsrError('{}: {} holds {} entries for a batch of {}.'
+                          .format(what, name, tensor.numel(), batch))
+
+
+@_on_tensor_device
+def spec_augment(features, lengths, seed, n_freq, freq_width, n_time, time_width,
+                 time_permille=1000, intervals=None):
+    """SpecAugment in place on ``features`` float32[B, T, 80] with ``lengths`` int32[B] (device):
+    ``n_freq`` bands of up to ``freq_width`` columns over the frames of each row, ``n_time`` spans
+    of up to ``min(time_width, length * time_permille / 1000)`` frames over all columns, stored
+    as 0.0 - the per-column mean under 'local' normalisation, and zero all the same under the
+    others.  The draws are integer functions of (``seed``, row, mask) pinned in
+    include/ctcasr.h.  ``intervals``: optional int32[B, n_freq + n_time, 2] device tensor that
+    receives (start, width) of every mask.  Returns ``features``."""
+    if features.dim() != 3 or features.shape[2] != 80:
+        raise CtcAsrError('spec_augment: features must be [B, T, 80] (got shape {}).'
+                          .format(tuple(features.shape)))
+    batch, frames = features.shape[0], features.shape[1]
+    _batch_of('spec_augment', 'lengths', lengths, batch)
+    for name, count in (('n_freq', n_freq), ('n_time', n_time)):
+        if not 0 <= int(count) <= SPEC_AUGMENT_MAX_MASKS:
+            raise CtcAsrError('spec_augment: {} is {}, 0..{} supported.'
+                              .format(name, count, SPEC_AUGMENT_MAX_MASKS))
+    _expect_numel('spec_augment', 'intervals', intervals,
+                  batch * (int(n_freq) + int(n_time)) * 2)
+    feat_ptr = _dev(features, name='features')
+    len_ptr = _dev(lengths, torch.int32, 'lengths')
+    int_ptr = _dev(intervals, torch.int32, 'intervals')
+    if batch == 0:
+        return features
+    _check(load().ctcasr_spec_augment(
+        feat_ptr, len_ptr, batch, frames, int(seed) & 0xFFFFFFFFFFFFFFFF, int(n_freq),
+        int(freq_width), int(n_time), int(time_width), int(time_permille), int_ptr, _stream()),
+        'spec_augment')
+    return features
+
+
+def resample_num_samples(n, percent):
+    """Samples that ``n`` samples come to at ``percent`` % speed: max(1, n * 100 // percent); 0
+    for n < 1 or a percent outside 50..200."""
+    return load().ctcasr_resample_num_samples(int(n), int(percent))
+
+
+@_on_tensor_device
+def speed_perturb(pcm, num_samples, percent, max_out=None):
+    """Resample every row of ``pcm`` int16[B, N] (``num_samples`` int32[B]) to ``percent`` int32[B]
+    per cent of its speed (50..200; 100 is a bit copy), all device tensors -> (int16[B, max_out],
+    int32[B]).  ``max_out``: columns of the result; callers that know the lengths on the host pass
+    the largest `resample_num_samples`.  Without it the result is sized for the slowest speed the
+    kernel serves (2 N), which costs no synchronisation.  A row longer than ``max_out`` is cut
+    to it and its count says so."""
+    if pcm.dim() != 2:
+        raise CtcAsrError('speed_perturb: pcm must be [B, N] (got {} dimensions).'
+                          .format(pcm.dim()))
+    batch, max_in = pcm.shape
+    _batch_of('speed_perturb', 'num_samples', num_samples, batch)
+    _batch_of('speed_perturb', 'percent', percent, batch)
+    pcm_ptr = _dev(pcm, torch.int16, 'pcm')
+    num_ptr = _dev(num_samples, torch.int32, 'num_samples')
+    pct_ptr = _dev(percent, torch.int32, 'percent')
+    if max_out is None:
+        max_out = 2 * max_in
+    max_out = max(int(max_out), 1)
+    out = torch.empty((batch, max_out), dtype=torch.int16, device=pcm.device)
+    out_samples = torch.empty(batch, dtype=torch.int32, device=pcm.device)
+    if batch == 0:
+        return out, out_samples
+    _check(load().ctcasr_speed_perturb(pcm_ptr, num_ptr, pct_ptr, batch, max_in,
+                                       _dev(out, torch.int16, 'out'), max_out,
+                                       _dev(out_samples, torch.int32, 'out_samples'), _stream()),
+           'speed_perturb')
+    return out, out_samples

@@ -31,7 +31,7 @@ from scipy.io import wavfile
 from ctc_asr_amd import hip
 from ctc_asr_amd.csv_helper import get_bucket_boundaries, read_csv_rows
 from ctc_asr_amd.labels import ctoi
-from ctc_asr_amd.params import CSV_HEADER_LABEL, CSV_HEADER_PATH, FLAGS
+from ctc_asr_amd.params import CSV_HEADER_LABEL, CSV_HEADER_PATH, FLAGS, parse_speed_perturb
 
 READER_THREADS = 8           # WAV files of one batch are read concurrently
 SUPPORTED_FEATURE_TYPES = ('mel', 'mfcc')
@@ -145,11 +145,17 @@ class _Staged:
     host until the GPU has worked off everything enqueued before it - the previous training
     steps - and with that the run-ahead that keeps the GPU fed (train.py from disk ran 35 % under
     the same steps from HBM).  Built by the reader thread; the consumer makes
-    its stream wait for ``ready`` and never blocks."""
+    its stream wait for ``ready`` and never blocks.
+
+    Items that carry a fourth entry (the speed of `host_batches(speed_percents=...)`) add their
+    percents to the same small buffer: ``percent`` (device) and ``perturbed_width``, the longest
+    row after `hip.speed_perturb`, known here from the host-side lengths."""
 
     def __init__(self, items, device, stream, ring=None):
         pcm = [it[0] for it in items]
         lengths = np.array([len(p) for p in pcm], dtype=np.int32)
+        percents = np.array([it[3] for it in items], dtype=np.int32) if len(items[0]) > 3 \
+            else np.zeros(0, dtype=np.int32)
         width = int(lengths.max())
         rows = [list(it[1]) for it in items]
         offsets = np.zeros(len(rows) + 1, dtype=np.int32)
@@ -164,12 +170,12 @@ class _Staged:
             view[row, :len(samples)] = samples
             view[row, len(samples):] = 0
         small = slot['small']
-        need = len(lengths) + len(flat) + len(offsets)
+        need = len(lengths) + len(flat) + len(offsets) + len(percents)
         if small.numel() < need:
             small = slot['small'] = torch.empty(2 * need, dtype=torch.int32).pin_memory()
-        cuts = np.cumsum([0, len(lengths), len(flat), len(offsets)])
+        cuts = np.cumsum([0, len(lengths), len(flat), len(offsets), len(percents)])
         packed = small.numpy()
-        for lo, hi, part in zip(cuts[:-1], cuts[1:], (lengths, flat, offsets)):
+        for lo, hi, part in zip(cuts[:-1], cuts[1:], (lengths, flat, offsets, percents)):
             packed[lo:hi] = part
         with torch.cuda.stream(stream):
             self.pcm = host_pcm.to(device, non_blocking=True)
@@ -181,6 +187,11 @@ class _Staged:
         self.packed_labels = (small_d[cuts[1]:cuts[2]], small_d[cuts[2]:cuts[3]],
                               max([len(r) for r in rows] + [1]), rows)
         self._keep = small_d
+        self.percent, self.perturbed_width = None, None
+        if len(percents):
+            self.percent = small_d[cuts[3]:cuts[4]]
+            self.perturbed_width = max(hip.resample_num_samples(n, p)
+                                       for n, p in zip(lengths, percents))
         label_width = max(len(r) for r in rows)
         self.labels = np.zeros((len(rows), max(label_width, 1)), dtype=np.int32)
         for row, ids in enumerate(rows):
@@ -212,7 +223,9 @@ class Batch:
     ``input_fn`` output (``asr/input_functions.py:112-120``), tensors already in HBM.
     ``packed_labels``: the same labels as `CTCModel.pack_labels` would upload them (what
     `Trainer.train_step` / `loss_fn` take without another host-to-device copy); ``pcm`` /
-    ``num_samples``: the raw audio the features were computed from (device tensors)."""
+    ``num_samples``: the raw audio the features were computed from (device tensors) - after
+    speed perturbation where that is on, while ``audio_seconds`` stays the duration of the
+    source audio."""
 
     def __init__(self, spectrogram, spectrogram_length, label_plaintext, labels, seconds,
                  packed_labels=None, pcm=None, num_samples=None):
@@ -227,9 +240,32 @@ class Batch:
         return iter((self.features, self.labels))
 
 
-def _make_batch(items, device, staged=None):
+class _Augmenter:
+    """Augmentation settings of ONE training iterator, read from the flags when it starts, and
+    its SpecAugment seeds: a 64-bit sequence stepped like `CTCModel._next_seed`, one value per
+    batch, so that two iterators with one seed mask alike (and two ranks of one epoch do not)."""
+
+    def __init__(self, seed, rank=0):
+        self.percents = parse_speed_perturb(FLAGS.speed_perturb)
+        self.spec = (FLAGS.specaug_freq_masks, FLAGS.specaug_freq_width,
+                     FLAGS.specaug_time_masks, FLAGS.specaug_time_width,
+                     FLAGS.specaug_time_permille) if FLAGS.spec_augment else None
+        self.seed = (int(seed) * 0x9E3779B1 + int(rank) * 0x85EBCA6B + 0x5A17) \
+            & 0xFFFFFFFFFFFFFFFF
+
+    def __bool__(self):
+        return bool(self.percents) or self.spec is not None
+
+    def next_seed(self):
+        self.seed = (self.seed * 6364136223846793005 + 1442695040888963407) & 0xFFFFFFFFFFFFFFFF
+        return self.seed
+
+
+def _make_batch(items, device, staged=None, augment=None):
     """Features of one batch on the current stream.  ``staged``: the batch's `_Staged` uploads
-    (made by the reader thread); without it they are made here."""
+    (made by the reader thread); without it they are made here.  ``augment``: the `_Augmenter`
+    of a training iterator - speed perturbation of the PCM, then the features, then SpecAugment,
+    all on this stream; without it exactly the launches of a plain batch."""
     if staged is None:
         staged = _Staged(items, device, torch.cuda.current_stream(device))
     main = torch.cuda.current_stream(device)
@@ -237,11 +273,19 @@ def _make_batch(items, device, staged=None):
     for tensor in (staged.pcm, staged._keep):
         tensor.record_stream(main)          # allocated on the upload stream, used on this one
     feature_type, feature_normalization = _check_feature_args(None, None)
-    feats, lengths = hip.features(staged.pcm, staged.num_samples, feature_type,
+    pcm, num_samples = staged.pcm, staged.num_samples
+    if staged.percent is not None:
+        pcm, num_samples = hip.speed_perturb(pcm, num_samples, staged.percent,
+                                             staged.perturbed_width)
+    feats, lengths = hip.features(pcm, num_samples, feature_type,
                                   feature_normalization, FLAGS.features_drop_every_second_frame,
                                   FLAGS.sampling_rate)
+    if augment is not None and augment.spec is not None:
+        n_freq, freq_width, n_time, time_width, permille = augment.spec
+        hip.spec_augment(feats, lengths, augment.next_seed(), n_freq, freq_width, n_time,
+                         time_width, permille)
     return Batch(feats, lengths, staged.texts, staged.labels, staged.seconds,
-                 staged.packed_labels, staged.pcm, staged.num_samples)
+                 staged.packed_labels, pcm, num_samples)
 
 
 def _example_stream(csv_path, shuffle, rng):
@@ -291,14 +335,23 @@ def _group_batches(stream, use_buckets, boundaries, batch_size):
             yield buckets[key]
 
 
-def host_batches(csv_path, use_buckets, boundaries, rank=0, world_size=1, seed=None):
+def host_batches(csv_path, use_buckets, boundaries, rank=0, world_size=1, seed=None,
+                 speed_percents=()):
     """Host side of one epoch for one rank: yields lists of (int16 PCM, label ids, label text).
     Groups of ``world_size * batch_size`` utterances are formed exactly as a single process would
     form them (every rank walks the same seeded order), a rank keeps its contiguous share and only
-    reads the WAV files of that share."""
+    reads the WAV files of that share.
+
+    ``speed_percents``: every utterance of a group gets one of these speeds, appended to its tuple
+    as a fourth entry.  They come from a generator of their own, seeded from the epoch's seed,
+    NOT from the shuffling one - the flag changes no batch's composition - and every rank draws
+    the whole group's list and keeps its slice, as it does with the group itself."""
     rng = random.Random(seed) if (seed is not None or world_size > 1) else random.Random()
     if world_size > 1 and seed is None:
-        rng = random.Random(FLAGS.random_seed or 1)
+        seed = FLAGS.random_seed or 1
+        rng = random.Random(seed)
+    speed_rng = random.Random() if seed is None else random.Random('speed:{}'.format(seed))
+    speed_percents = list(speed_percents)
     stream = _example_stream(csv_path, use_buckets, rng)
     if use_buckets:
         stream = _shuffle_buffer(stream, FLAGS.shuffle_buffer_size, rng)
@@ -307,12 +360,18 @@ def host_batches(csv_path, use_buckets, boundaries, rank=0, world_size=1, seed=N
     try:
         for group in groups:
             part = group
+            speeds = [speed_rng.choice(speed_percents) for _ in group] if speed_percents else None
             if world_size > 1:
                 per_rank = len(group) // world_size
                 part = group[rank * per_rank:(rank + 1) * per_rank]
+                speeds = speeds and speeds[rank * per_rank:(rank + 1) * per_rank]
             if part:
                 audio = list(readers.map(read_wav, [it[0] for it in part]))
-                yield [(pcm, it[1], it[2]) for pcm, it in zip(audio, part)]
+                if speeds:
+                    yield [(pcm, it[1], it[2], percent)
+                           for pcm, it, percent in zip(audio, part, speeds)]
+                else:
+                    yield [(pcm, it[1], it[2]) for pcm, it in zip(audio, part)]
     finally:
         readers.shutdown(wait=False)
 
@@ -325,6 +384,10 @@ def input_fn_generator(target, device='cuda', rank=0, world_size=1, seed=None, p
     ranks walk the same seeded order) and every rank keeps its contiguous shard, so the time
     extent matches across ranks and nobody waits in the all-reduce; a ragged last group is cut
     to a multiple of ``world_size``.
+
+    ``--spec_augment`` / ``--speed_perturb`` act on the two training targets only: 'dev' and
+    'test' batches are the same with the flags on and off.  Buckets are formed on the source
+    lengths; an utterance slowed or sped up stays in its bucket.
     """
     if target == 'train_bucket':
         csv_path, use_buckets = FLAGS.train_csv, True
@@ -338,16 +401,26 @@ def input_fn_generator(target, device='cuda', rank=0, world_size=1, seed=None, p
         raise ValueError('Invalid target: "{}"'.format(target))
     boundaries = get_bucket_boundaries(csv_path, FLAGS.num_buckets) if use_buckets else []
 
+    training = target in ('train_bucket', 'train_batch')
+
     def input_fn():
         assert os.path.exists(csv_path) and os.path.isfile(csv_path)
+        augment = None
+        if training and (FLAGS.spec_augment or FLAGS.speed_perturb):
+            # (seeded like the epoch where it has a seed; otherwise like its shuffle: fresh)
+            augment = _Augmenter(seed if seed is not None else random.getrandbits(63), rank)
 
         def host_side():
-            return host_batches(csv_path, use_buckets, boundaries, rank, world_size, seed)
+            if augment is None or not augment.percents:
+                return host_batches(csv_path, use_buckets, boundaries, rank, world_size, seed)
+            return host_batches(csv_path, use_buckets, boundaries, rank, world_size, seed,
+                                augment.percents)
 
         if prefetch <= 0:
             for items in host_side():
                 yield _make_batch(items, torch.device(device) if torch.device(device).index
-                                  is not None else torch.device('cuda', torch.cuda.current_device()))
+                                  is not None else torch.device('cuda', torch.cuda.current_device()),
+                                  augment=augment)
             return
         # WAV reading, label packing and the uploads run ahead on a host thread (the reference's
         # prefetch(64)): pinned staging buffers, asynchronous copies on an upload stream
@@ -387,6 +460,6 @@ def input_fn_generator(target, device='cuda', rank=0, world_size=1, seed=None, p
                 return
             if isinstance(got, BaseException):
                 raise got
-            yield _make_batch(got[0], dev, got[1])
+            yield _make_batch(got[0], dev, got[1], augment)
 
     return input_fn

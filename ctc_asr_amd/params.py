@@ -18,10 +18,11 @@ BASE_PATH = os.path.realpath(os.path.join(os.path.dirname(os.path.realpath(__fil
 
 
 class _Flag:
-    __slots__ = ('name', 'kind', 'default', 'value', 'help')
+    __slots__ = ('name', 'kind', 'default', 'value', 'help', 'check')
 
-    def __init__(self, name, kind, default, help_text):
+    def __init__(self, name, kind, default, help_text, check=None):
         self.name, self.kind, self.default, self.help = name, kind, default, help_text
+        self.check = check
         self.value = list(default) if kind == 'multi_int' else default
 
 
@@ -32,10 +33,12 @@ class FlagValues:
         object.__setattr__(self, '_flags', {})
 
     # -- definition -------------------------------------------------------------------------
-    def define(self, kind, name, default, help_text=''):
+    def define(self, kind, name, default, help_text='', check=None):
+        """``check(value)``: raises ValueError for a value the flag refuses - when the command line
+        is parsed or the flag is assigned, not when it is first used."""
         if name in self._flags:
             raise ValueError('Duplicate flag "{}".'.format(name))
-        self._flags[name] = _Flag(name, kind, default, help_text)
+        self._flags[name] = _Flag(name, kind, default, help_text, check)
 
     # -- access -----------------------------------------------------------------------------
     def __getattr__(self, name):
@@ -68,8 +71,15 @@ class FlagValues:
         return self
 
     # -- parsing ----------------------------------------------------------------------------
+    @classmethod
+    def _convert(cls, flag, raw):
+        value = cls._convert_kind(flag, raw)
+        if flag.check is not None:
+            flag.check(value)
+        return value
+
     @staticmethod
-    def _convert(flag, raw):
+    def _convert_kind(flag, raw):
         if flag.kind == 'string':
             return str(raw)
         if flag.kind == 'int':
@@ -182,6 +192,56 @@ FLAGS.define('float', 'max_grad_norm', 0.0,
 FLAGS.define('bool', 'report_grad_norms', False,
              'Compute the global and per-layer gradient norms every step and log them.')
 
+# Augmentation of training batches on the device (no counterpart in the reference, which does not
+# augment; all off: a training batch launches what it always did).  Only the targets
+# 'train_bucket' and 'train_batch' augment; evaluate / predict / align never do.
+SPECAUG_MAX_MASKS = 16          # CTCASR_SPEC_AUGMENT_MAX_MASKS
+SPEED_PERCENT_RANGE = (50, 200)
+
+
+def _int_range(name, low, high=None):
+    def check(value):
+        if value < low or (high is not None and value > high):
+            raise ValueError('--{}={} is outside {}..{}.'.format(
+                name, value, low, 'unbounded' if high is None else high))
+    return check
+
+
+def parse_speed_perturb(text):
+    """'90,100,110' -> [90, 100, 110]; '' -> []; ValueError for anything else."""
+    percents = []
+    for part in str(text).replace(',', ' ').split():
+        try:
+            percent = int(part)
+        except ValueError:
+            raise ValueError('--speed_perturb: "{}" is not a whole percent.'.format(part))
+        if not SPEED_PERCENT_RANGE[0] <= percent <= SPEED_PERCENT_RANGE[1]:
+            raise ValueError('--speed_perturb: {} is outside {}..{} percent.'.format(
+                percent, *SPEED_PERCENT_RANGE))
+        percents.append(percent)
+    return percents
+
+
+FLAGS.define('bool', 'spec_augment', False,
+             'Mask the features of training batches (SpecAugment): masked cells are set to 0.0, '
+             "the per-column mean under 'local' normalisation (zero is written under 'none' and "
+             "'local_scalar' too).")
+FLAGS.define('int', 'specaug_freq_masks', 2, 'Number of frequency masks (0..16).',
+             _int_range('specaug_freq_masks', 0, SPECAUG_MAX_MASKS))
+FLAGS.define('int', 'specaug_freq_width', 27, 'Largest frequency mask, in feature columns.',
+             _int_range('specaug_freq_width', 0))
+FLAGS.define('int', 'specaug_time_masks', 2, 'Number of time masks (0..16).',
+             _int_range('specaug_time_masks', 0, SPECAUG_MAX_MASKS))
+FLAGS.define('int', 'specaug_time_width', 100, 'Largest time mask, in frames.',
+             _int_range('specaug_time_width', 0))
+FLAGS.define('int', 'specaug_time_permille', 1000,
+             'Cap on a time mask as a share of the utterance, in thousandths (0..1000).',
+             _int_range('specaug_time_permille', 0, 1000))
+FLAGS.define('string', 'speed_perturb', '',
+             'Comma list of speeds in percent (50..200), for example 90,100,110: every training '
+             'utterance is resampled to one of them, drawn uniformly; empty: off.',
+             parse_speed_perturb)
+
 # CTC decoder (asr/params.py:84-86).
 FLAGS.define('int', 'beam_width', 1024, 'Leaves kept by the CTC beam search (<= 1024).')
 
@@ -275,4 +335,10 @@ def get_parameters():
         # reference's, line for line)
         rows.append('\tGradients (max_grad_norm={}, report_grad_norms={});'.format(
             FLAGS.max_grad_norm, FLAGS.report_grad_norms))
+    if FLAGS.spec_augment or FLAGS.speed_perturb:
+        rows.append('\tAugmentation (spec_augment={}, freq_masks={} x {}, time_masks={} x {}, '
+                    'time_permille={}, speed_perturb={});'.format(
+                        FLAGS.spec_augment, FLAGS.specaug_freq_masks, FLAGS.specaug_freq_width,
+                        FLAGS.specaug_time_masks, FLAGS.specaug_time_width,
+                        FLAGS.specaug_time_permille, FLAGS.speed_perturb or 'off'))
     return '\n'.join(rows)

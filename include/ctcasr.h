@@ -749,6 +749,76 @@ int ctcasr_features(const int16_t *pcm, const int32_t *num_samples, int B, int m
                     const void *tables, float *out, int out_frames, int32_t *out_len,
                     void *workspace, size_t workspace_bytes, ctcasr_stream_t stream);
 
+/* ---- K15: augmentation of training batches ----------------------------------------------------
+ * No counterpart in the reference (it does not augment).  Two kernels around ctcasr_features:
+ * speed perturbation of the PCM before it, SpecAugment masks on the features after it.  Left out
+ * on purpose: time warping, noise mixing, and any mask fill other than zero.
+ *
+ * Counter generator (integers only, so that a host reference reproduces every draw):
+ *   r24(seed, idx)      = the top 24 bits (z >> 40) of the splitmix64 finaliser over
+ *                         z = seed + 0x9E3779B97F4A7C15 * (idx + 1), the generator of the dropout
+ *                         masks (bias_act_fwd / dropout)
+ *   below(seed, idx, n) = (r24(seed, idx) * n) >> 24 in 64 bits, 1 <= n <= 2^24: uniform over
+ *                         [0, n), never n.  (A larger n is still well defined; not every value
+ *                         is reached.)
+ *
+ * ctcasr_spec_augment: in place on the output of ctcasr_features (after normalisation and the
+ * frame drop).
+ *   features   float32 [B, out_frames, 80]
+ *   lengths    int32 [B] frames per row; L = lengths[b] clamped into [0, out_frames]
+ *   Row b, frequency mask i < n_freq: w  = below(seed, 64 b + 2 i,     min(freq_width, 80) + 1),
+ *                                     f0 = below(seed, 64 b + 2 i + 1, 80 - w + 1):
+ *                                     columns [f0, f0 + w) of frames [0, L).
+ *   Row b, time mask i < n_time:      cap = min(time_width, L * time_permille / 1000) (integer
+ *                                     division),
+ *                                     w  = below(seed, 64 b + 32 + 2 i,     cap + 1),
+ *                                     t0 = below(seed, 64 b + 32 + 2 i + 1, L - w + 1):
+ *                                     all 80 columns of frames [t0, t0 + w).
+ *   A row with L == 0 gets no masks.  Masks may overlap.
+ *   Every masked cell is STORED +0.0f whatever it held (a NaN included: a store, not a multiply);
+ *   no other cell is stored to and no cell is read, so cells outside the masks and frames at or
+ *   beyond L keep their bits, and the traffic is the masked area.  Zero is the per-column mean
+ *   under 'local' normalisation; under 'none' and 'local_scalar' zero is written all the same.
+ *   intervals  optional int32 [B, n_freq + n_time, 2]: (start, width) of every mask, the
+ *              frequency masks first; all zero for a row with L == 0.  May be NULL.
+ * Errors (CTCASR_ERR_BAD_ARGUMENT, before any launch): null features / lengths, B < 1,
+ * out_frames < 0, n_freq or n_time outside [0, CTCASR_SPEC_AUGMENT_MAX_MASKS], a negative width,
+ * time_permille outside [0, 1000]; out_frames >= 2^24: CTCASR_ERR_UNSUPPORTED.
+ * n_freq == n_time == 0 launches nothing.
+ *
+ * ctcasr_speed_perturb: band-limited resampling of each row by its own factor; percent[b] = P
+ * plays row b P / 100 times as fast (P in [50, 200]).
+ *   pcm, num_samples   int16 [B, max_in], int32 [B]     percent   int32 [B]      (all device)
+ *   out, out_samples   int16 [B, max_out], int32 [B]
+ *   n_out = max(1, n * 100 / P) (integer division, 64-bit product, at most INT32_MAX) =
+ *   ctcasr_resample_num_samples(n, P), pure host arithmetic, 0 for n < 1 or P outside [50, 200].
+ *   Output sample j sits at input position t = j * P / 100: integer part t0 = (j * P) / 100 and
+ *   phase p = (j * P) % 100 in 64-bit integers (no float position that drifts over a long row).
+ *   y[j] = sum over input samples k in [0, n) of x[k] * h(t - k), x = 0 outside, with
+ *     c = 95 / max(P, 100)                        (= 0.95 * min(1, 100 / P): the cut-off)
+ *     h(d) = c * sinc(c d) * 0.5 * (1 + cos(pi c d / 12)) for |c d| < 12, else 0;
+ *     sinc(u) = sin(pi u) / (pi u), sinc(0) = 1   (a Hann-windowed sinc of 12 zero crossings a side)
+ *   Taps: k = t0 + m for m in [-R, R + 1], R = 12 * max(P, 100) / 95 (integer division): 26 taps up
+ *   to P = 100, 52 at P = 200.  The weight of (p, m) is h(p / 100 - m) evaluated in fp64 and
+ *   rounded once to fp32; a row has at most 100 distinct phases.  The sum is fp32, starting from
+ *   +0, one fused multiply-add per tap in ascending k; the result is rounded to nearest even and
+ *   saturated to [-32768, 32767].
+ *   A row with P == 100 is a bit copy.  A row whose n is outside [1, max_in] or whose P is outside
+ *   [50, 200] reads none of its PCM and gets count 0 and an all-zero row, as in ctcasr_features.
+ *   Columns [n_out, max_out) are zero.  A row whose n_out exceeds max_out is cut to max_out and
+ *   out_samples reports max_out (the host cannot check this without a synchronisation; size
+ *   max_out with ctcasr_resample_num_samples).
+ * Errors (CTCASR_ERR_BAD_ARGUMENT): a null pointer, B < 1, max_in < 1, max_out < 1; max_in or
+ * max_out above 2^30: CTCASR_ERR_UNSUPPORTED. */
+#define CTCASR_SPEC_AUGMENT_MAX_MASKS 16
+int ctcasr_spec_augment(float *features, const int32_t *lengths, int B, int out_frames,
+                        uint64_t seed, int n_freq, int freq_width, int n_time, int time_width,
+                        int time_permille, int32_t *intervals, ctcasr_stream_t stream);
+int ctcasr_resample_num_samples(int num_samples, int percent);
+int ctcasr_speed_perturb(const int16_t *pcm, const int32_t *num_samples, const int32_t *percent,
+                         int B, int max_in, int16_t *out, int max_out, int32_t *out_samples,
+                         ctcasr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
