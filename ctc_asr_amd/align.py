@@ -72,7 +72,7 @@ def main(argv=None):
     latest = storage.latest_checkpoint(FLAGS.train_dir)
     if latest is None:
         raise SystemExit('No checkpoint found in {}.'.format(FLAGS.train_dir))
-    storage.restore_checkpoint(latest, model)
+    storage.restore_checkpoint(latest, model, weights='ema' if FLAGS.eval_ema else 'param')
     count = 0
     with open(FLAGS.align_output, 'w', encoding='utf-8') as handle:
         for result in align_rows(model, rows, FLAGS.corpus_dir, FLAGS.batch_size,

@@ -126,6 +126,16 @@ transpose_kernel(const float *__restrict__ in, float *__restrict__ out, int rows
     }
 }
 
+// one element of the Adam update, on the fields `f` of pp / gg / mm / vv: the one statement of it
+// that adam_kernel and adam_ema_kernel share, so that both leave the same bits
+#define ADAM_LANE(f)                                                      \
+        {                                                                 \
+            float gr = gg.f * gscale;                                     \
+            mm.f = b1 * mm.f + (1.f - b1) * gr;                           \
+            vv.f = b2 * vv.f + (1.f - b2) * gr * gr;                      \
+            pp.f -= lr_t * mm.f / (sqrtf(vv.f) + eps);                    \
+        }
+
 __global__ void __launch_bounds__(256)
 adam_kernel(float *__restrict__ p, const float *__restrict__ g, float *__restrict__ m,
             float *__restrict__ v, int64_t n, float lr_t, float b1, float b2, float eps,
@@ -146,15 +156,7 @@ adam_kernel(float *__restrict__ p, const float *__restrict__ g, float *__restric
     float4 *v4 = reinterpret_cast<float4 *>(v);
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
         float4 pp = p4[i], gg = g4[i], mm = m4[i], vv = v4[i];
-#define ADAM_LANE(f)                                                      \
-        {                                                                 \
-            float gr = gg.f * gscale;                                     \
-            mm.f = b1 * mm.f + (1.f - b1) * gr;                           \
-            vv.f = b2 * vv.f + (1.f - b2) * gr * gr;                      \
-            pp.f -= lr_t * mm.f / (sqrtf(vv.f) + eps);                    \
-        }
         ADAM_LANE(x) ADAM_LANE(y) ADAM_LANE(z) ADAM_LANE(w)
-#undef ADAM_LANE
         p4[i] = pp; m4[i] = mm; v4[i] = vv;
     }
     // tail (n % 4 elements)
@@ -167,6 +169,45 @@ adam_kernel(float *__restrict__ p, const float *__restrict__ g, float *__restric
         p[i] -= lr_t * mm / (sqrtf(vv) + eps);
     }
 }
+
+// adam_kernel with the exponential moving average of the parameters in the same pass: the
+// parameter this launch has just formed goes from its registers into
+//   ema += alpha * (param_new - ema)
+// (fp32; TensorFlow's assign_sub(ema, (1 - decay) * (ema - param))), 36 B per parameter instead of
+// 28 + 12 for a second launch.  `skip` leaves the average alone as well.
+__global__ void __launch_bounds__(256)
+adam_ema_kernel(float *__restrict__ p, const float *__restrict__ g, float *__restrict__ m,
+                float *__restrict__ v, float *__restrict__ e, int64_t n, float lr_t, float b1,
+                float b2, float eps, float gscale, const int32_t *__restrict__ skip,
+                const float *__restrict__ gfactor, float alpha) {
+    if (skip && *skip) return;
+    if (gfactor) gscale *= *gfactor;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    const int64_t n4 = n >> 2;
+    float4 *p4 = reinterpret_cast<float4 *>(p);
+    const float4 *g4 = reinterpret_cast<const float4 *>(g);
+    float4 *m4 = reinterpret_cast<float4 *>(m);
+    float4 *v4 = reinterpret_cast<float4 *>(v);
+    float4 *e4 = reinterpret_cast<float4 *>(e);
+#define EMA_LANE(f) ee.f = ee.f + alpha * (pp.f - ee.f);
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+        float4 pp = p4[i], gg = g4[i], mm = m4[i], vv = v4[i], ee = e4[i];
+        ADAM_LANE(x) ADAM_LANE(y) ADAM_LANE(z) ADAM_LANE(w)
+        EMA_LANE(x) EMA_LANE(y) EMA_LANE(z) EMA_LANE(w)
+        p4[i] = pp; m4[i] = mm; v4[i] = vv; e4[i] = ee;
+    }
+    // tail (n % 4 elements): the same two statements on one-field records
+    struct One { float x; };
+    for (int64_t i = (n4 << 2) + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+         i += stride) {
+        One pp{p[i]}, gg{g[i]}, mm{m[i]}, vv{v[i]}, ee{e[i]};
+        ADAM_LANE(x)
+        EMA_LANE(x)
+        m[i] = mm.x; v[i] = vv.x; p[i] = pp.x; e[i] = ee.x;
+    }
+#undef EMA_LANE
+}
+#undef ADAM_LANE
 
 // skip[0] = any CTC status word != 0 | any per-utterance loss not finite | any time-out word set;
 // skip[1] = the time-out words or-ed together, bit 30 = the weight-gradient kernel's give-up word
@@ -356,6 +397,29 @@ extern "C" int ctcasr_adam_step_clipped(float *param, const float *grad, float *
     const int blocks = (int)(want > ADAM_BLOCKS ? ADAM_BLOCKS : want < 1 ? 1 : want);
     adam_kernel<<<blocks, 256, 0, (hipStream_t)stream>>>(
         param, grad, m, v, n, (float)lr_t, beta1, beta2, epsilon, grad_scale, skip, grad_factor);
+    return ctcasr_launch_status();
+}
+
+extern "C" int ctcasr_adam_step_ema(float *param, const float *grad, float *m, float *v,
+                                    float *ema, int64_t n, float lr, float beta1, float beta2,
+                                    float epsilon, int64_t step, float grad_scale,
+                                    const int32_t *skip, const float *grad_factor,
+                                    float ema_alpha, ctcasr_stream_t stream) {
+    if (!param || !grad || !m || !v || !ema || n < 0 || step < 1) return CTCASR_ERR_BAD_ARGUMENT;
+    if (!(ema_alpha >= 0.f && ema_alpha <= 1.f)) return CTCASR_ERR_BAD_ARGUMENT;   // (NaN too)
+    if (n == 0) return CTCASR_OK;
+    if ((reinterpret_cast<uintptr_t>(param) | reinterpret_cast<uintptr_t>(grad) |
+         reinterpret_cast<uintptr_t>(m) | reinterpret_cast<uintptr_t>(v) |
+         reinterpret_cast<uintptr_t>(ema)) % 16 != 0)
+        return CTCASR_ERR_BAD_ARGUMENT;
+    // lr_t and the grid exactly as ctcasr_adam_step_clipped forms them
+    const double lr_t = (double)lr * sqrt(1.0 - pow((double)beta2, (double)step)) /
+                        (1.0 - pow((double)beta1, (double)step));
+    int64_t want = (n / 4 + 1 + 255) / 256;
+    const int blocks = (int)(want > ADAM_BLOCKS ? ADAM_BLOCKS : want < 1 ? 1 : want);
+    adam_ema_kernel<<<blocks, 256, 0, (hipStream_t)stream>>>(
+        param, grad, m, v, ema, n, (float)lr_t, beta1, beta2, epsilon, grad_scale, skip,
+        grad_factor, ema_alpha);
     return ctcasr_launch_status();
 }
 

@@ -9,6 +9,7 @@ as the backward pass has finished that layer so the collective overlaps the rest
 """
 
 import collections
+import types
 import warnings
 import os
 import time
@@ -16,6 +17,7 @@ import time
 import torch
 import torch.distributed as dist
 
+from ctc_asr_amd import params as _params
 from ctc_asr_amd.model import CTCModel
 
 
@@ -198,8 +200,32 @@ class Trainer:
     def __init__(self, cfg, flags=None, device=None, seed=0, params=None, world_size=1, rank=0,
                  bucket_bytes=64 << 20, conv_autotune=None, allreduce_early=None,
                  force_reducer=False, reduce=True, collective_stand_in=None, max_grad_norm=None,
-                 report_grad_norms=None):
+                 report_grad_norms=None, grad_accum_steps=None, ema_decay=None, lr_schedule=None):
         self.world, self.rank = world_size, rank
+
+        def flag(name, default):
+            return getattr(flags, name, default) if flags is not None else default
+
+        # The schedule of a run (keyword arguments, else the flags of the same names, else off):
+        # ``grad_accum_steps`` micro-batches are summed into one update, ``ema_decay`` > 0 keeps
+        # an exponential moving average of the parameters in the Adam launch, ``lr_schedule`` /
+        # --lr_warmup_steps move the learning rate with the update count.  With all three off
+        # `train_step` launches exactly what it launches without them.
+        self.grad_accum_steps = int(flag('grad_accum_steps', 1) if grad_accum_steps is None
+                                    else grad_accum_steps)
+        if not 1 <= self.grad_accum_steps <= 1024:
+            raise ValueError('grad_accum_steps={} is outside 1..1024.'.format(
+                self.grad_accum_steps))
+        self.ema_decay = float(flag('ema_decay', 0.0) if ema_decay is None else ema_decay)
+        if not 0.0 <= self.ema_decay < 1.0:
+            raise ValueError('ema_decay={} is outside 0 <= d < 1.'.format(self.ema_decay))
+        self.lr_schedule = str(flag('lr_schedule', 'constant') if lr_schedule is None
+                               else lr_schedule)
+        if self.lr_schedule not in _params.LR_SCHEDULES:
+            raise ValueError('lr_schedule={} is none of {}.'.format(
+                self.lr_schedule, ', '.join(_params.LR_SCHEDULES)))
+        self._micro = 0                 # micro-steps of the open update that have run
+        self._accum_guard = None        # ... and their guard words, or-ed, on the device
         # Clipping by global norm (``max_grad_norm`` > 0) and the per-layer norms
         # (``report_grad_norms``): keyword arguments, else the flags of the same names, else off.
         # With both off `train_step` launches exactly what it launches without them.
@@ -214,8 +240,20 @@ class Trainer:
         self.last_clip_factor = None    # ... then the global norm; device float32[1]
         self._clipped = None
         device = device or 'cuda:{}'.format(torch.cuda.current_device())
-        self.model = CTCModel(cfg, device, seed=seed, params=params, conv_autotune=conv_autotune)
+        self.model = CTCModel(cfg, device, seed=seed, params=params, conv_autotune=conv_autotune,
+                              ema=self.ema_decay > 0)
         self.lr = getattr(flags, 'learning_rate', 1e-5) if flags is not None else 1e-5
+        # what `params.learning_rate_at` reads; under 'constant' without warm-up `self.lr` is left
+        # alone (it is the flag's value already, and callers may set it)
+        defaults = _params.FLAGS.defaults_dict()
+        self._lr_flags = types.SimpleNamespace(
+            learning_rate=self.lr, lr_schedule=self.lr_schedule,
+            **{name: flag(name, defaults[name])
+               for name in ('learning_rate_decay_factor', 'steps_per_decay', 'minimum_lr',
+                            'lr_warmup_steps', 'lr_total_steps')})
+        self.lr_scheduled = self.lr_schedule != 'constant' or self._lr_flags.lr_warmup_steps > 0
+        if self.lr_scheduled:
+            _params.learning_rate_at(1, self._lr_flags)     # (refuses an incomplete schedule now)
         self.beta1 = getattr(flags, 'adam_beta1', 0.9) if flags is not None else 0.9
         self.beta2 = getattr(flags, 'adam_beta2', 0.999) if flags is not None else 0.999
         self.eps = getattr(flags, 'adam_epsilon', 1e-8) if flags is not None else 1e-8
@@ -254,6 +292,7 @@ class Trainer:
         if world_size > 1:   # identical replicas: rank 0's initial parameters win
             dist.broadcast(self.model.arena.param, src=0)
             self.model.arena.touch()
+            self.model.arena.seed_ema()
         # The host enqueues a step several times faster than the GPU runs it.  Left alone it
         # runs ahead without bound: every step's activations (5 GB at C3) are then allocated
         # anew - blocks freed by the host are still in use by steps the GPU has not reached -
@@ -288,7 +327,7 @@ class Trainer:
                 CTCModel.check_status(host[:-2])
             except ValueError as err:
                 raise type(err)('{} [training step {}; its update was not applied]'.format(
-                    err, step)) from None
+                    err, step)) from None   # (``step``: "7", or "7 (micro-step 1 of 2)")
             if words[-1] != 0:
                 # a persistent recurrence gave up at a grid barrier in that step: the sticky word
                 # is read (and the barrier words reset) by the synchronous poll, which raises
@@ -307,7 +346,10 @@ class Trainer:
     def drain_checks(self):
         """Wait for the steps in flight and raise what they have to report: CTC status of every
         pending step, then the persistent kernels' time-out word.  `train.train_epoch` calls
-        this where it reads the loss anyway, at the end of an epoch and before a checkpoint."""
+        this where it reads the loss anyway, at the end of an epoch and before a checkpoint.
+        Refuses inside an open update (`accumulating`): its micro-steps' gradients are in the
+        arena and no step has been counted for them."""
+        self._refuse_open_update('drain_checks')
         self._check_finished_steps(wait=True)
         self.model.check_rnn_error()
         self._steps_since_poll = 0
@@ -325,6 +367,32 @@ class Trainer:
                           'loss or gradient norm, or a kernel time-out); the step counter is back '
                           'at {}.'.format(new, self.model.step_count), RuntimeWarning)
 
+    @property
+    def accumulating(self):
+        """True while an update is open: some, not all, of its ``grad_accum_steps`` micro-steps
+        have run."""
+        return self._micro > 0
+
+    def _refuse_open_update(self, what):
+        if self.accumulating:
+            raise RuntimeError('{}: update {} is open ({} of {} micro-steps have run); finish it '
+                               'or `abandon_update()` first.'.format(
+                                   what, self.model.step_count + 1, self._micro,
+                                   self.grad_accum_steps))
+
+    def abandon_update(self):
+        """Drop the open update, if any: the gradients its micro-steps left in the arena are
+        cleared by the next one's first backward pass, nothing was counted.  What
+        `train.train_epoch` does with a ragged last group.  The micro-steps' deferred checks
+        stay queued."""
+        self._micro, self._accum_guard = 0, None
+
+    def save_checkpoint(self, train_dir, epoch, extra=None):
+        """`storage.save_checkpoint` of this trainer's model; refuses inside an open update."""
+        from ctc_asr_amd import storage
+        self._refuse_open_update('save_checkpoint')
+        return storage.save_checkpoint(train_dir, self.model, epoch, extra)
+
     def train_step(self, features, feature_len, labels, check=True):
         """forward + CTC + backward (+ all-reduce) + Adam on this rank's shard of the global
         batch; returns the local mean loss (device scalar).  The global loss is the mean over
@@ -338,7 +406,13 @@ class Trainer:
         written; with `max_grad_norm` / `report_grad_norms` on, so does a gradient norm that is
         not finite behind a finite loss.  Either way that step's update is dropped ON THE DEVICE
         (`CTCModel.step_guard` -> the Adam kernel's skip flag): parameters and moments never see
-        its gradients."""
+        its gradients.
+
+        ``grad_accum_steps`` = k > 1: a call is one MICRO-step.  The first k - 1 of an update run
+        forward + backward into the gradient arena (the first clears it, the others add), or
+        their guard words into one kept on the device and return; the k-th also runs the reducer
+        hooks, the norms and Adam, on the summed arena with 1 / (world * k).  One raised guard
+        word in any of them drops the whole update.  `model.step_count` counts updates."""
         if len(self._step_done) >= self.max_steps_ahead:
             t0 = time.perf_counter()
             while len(self._step_done) >= self.max_steps_ahead:
@@ -352,8 +426,17 @@ class Trainer:
                 self._check_finished_steps(wait=True)
                 self.model.check_rnn_error()
                 self._steps_since_poll = 0
-        loss = self.model.forward_backward(features, feature_len, labels,
-                                           reduce_hook=self.reducer, check=False)
+        accum = self.grad_accum_steps
+        last = self._micro == accum - 1
+        label = self.model.step_count + 1
+        if accum > 1:
+            label = '{} (micro-step {} of {})'.format(label, self._micro + 1, accum)
+            loss = self.model.forward_backward(features, feature_len, labels,
+                                               reduce_hook=self.reducer if last else None,
+                                               check=False, accumulate=self._micro > 0)
+        else:
+            loss = self.model.forward_backward(features, feature_len, labels,
+                                               reduce_hook=self.reducer, check=False)
         # Invalid gradients never reach the parameters: the guard word is computed on the device
         # from this step's CTC status, its loss and the recurrence time-out words, and the Adam
         # kernel drops the update when it is set - whenever the host gets to look.
@@ -366,10 +449,23 @@ class Trainer:
             host = torch.empty(status.numel() + 2, dtype=status.dtype, pin_memory=True)
             host[:status.numel()].copy_(status, non_blocking=True)
             host[status.numel():].copy_(guard, non_blocking=True)
-            if not norms_on:
+            if not norms_on or not last:
                 copied = torch.cuda.Event()
                 copied.record(torch.cuda.current_stream(self.model.device))
-                self._pending_status.append((copied, host, self.model.step_count + 1, None))
+                self._pending_status.append((copied, host, label, None))
+        if accum > 1:
+            # (the host copy above holds this micro-step's own words: its check names it)
+            if self._accum_guard is not None:
+                guard |= self._accum_guard
+            if not last:
+                self._accum_guard = guard
+                self._micro += 1
+                done = torch.cuda.Event()
+                done.record(torch.cuda.current_stream(self.model.device))
+                self._step_done.append(done)
+                return loss
+            self._micro, self._accum_guard = 0, None
+        grad_scale = 1.0 / self.world if accum == 1 else 1.0 / (self.world * accum)
         self.reducer.finish(guard)      # (N > 1: the guard words become their maxima over ranks)
         grad_factor = None
         if norms_on:
@@ -379,7 +475,7 @@ class Trainer:
             # replicas stay replicated without another collective.  1 / world: the norm of the
             # MEAN gradient, what Adam applies.  Nothing comes back to the host here: the factor
             # stays on the device and the Adam kernel reads it.
-            norms, grad_factor = self.model.grad_norms(1.0 / self.world, self.max_grad_norm, guard)
+            norms, grad_factor = self.model.grad_norms(grad_scale, self.max_grad_norm, guard)
             self.last_grad_norms, self.last_clip_factor = norms, grad_factor
             if self._clipped is None:
                 self._clipped = torch.zeros(1, dtype=torch.int32, device=self.model.device)
@@ -390,15 +486,22 @@ class Trainer:
                 norm_host.copy_(norms[-1:], non_blocking=True)
                 copied = torch.cuda.Event()
                 copied.record(torch.cuda.current_stream(self.model.device))
-                self._pending_status.append((copied, host, self.model.step_count + 1, norm_host))
+                self._pending_status.append((copied, host, label, norm_host))
         # (how many updates the device has dropped so far: `skipped_step_count()` - a run whose
         # steps were silently skipped must not be reported as throughput)
         if self._skipped is None:
             self._skipped = torch.zeros(1, dtype=torch.int32, device=self.model.device)
         self._skipped += (guard[:1] != 0).to(torch.int32)
-        self.model.apply_gradients(self.lr, self.beta1, self.beta2, self.eps,
-                                   grad_scale=1.0 / self.world, skip=guard,
-                                   grad_factor=grad_factor)
+        if self.lr_scheduled:
+            self.lr = _params.learning_rate_at(self.model.step_count + 1, self._lr_flags)
+        if self.ema_decay > 0:
+            self.model.apply_gradients(self.lr, self.beta1, self.beta2, self.eps,
+                                       grad_scale=grad_scale, skip=guard,
+                                       grad_factor=grad_factor, ema_decay=self.ema_decay)
+        else:
+            self.model.apply_gradients(self.lr, self.beta1, self.beta2, self.eps,
+                                       grad_scale=grad_scale, skip=guard,
+                                       grad_factor=grad_factor)
         done = torch.cuda.Event()
         done.record(torch.cuda.current_stream(self.model.device))
         self._step_done.append(done)

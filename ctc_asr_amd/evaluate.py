@@ -106,7 +106,7 @@ def main(argv=None):
     latest = storage.latest_checkpoint(FLAGS.train_dir)
     if latest is None:
         raise SystemExit('No checkpoint found in {}.'.format(FLAGS.train_dir))
-    storage.restore_checkpoint(latest, model)
+    storage.restore_checkpoint(latest, model, weights='ema' if FLAGS.eval_ema else 'param')
     target = 'dev' if FLAGS.dev else 'test'
     print('Evaluating checkpoint {} on the {} set.'.format(latest, target))
     result = evaluate_dataset(model, target, scorer=lm.from_flags(model.cfg.num_classes))

@@ -143,6 +143,8 @@ SIGNATURES = {
     'ctcasr_adam_step': (_c_int, [_c_p] * 4 + [_c_i64] + [_c_f] * 4 + [_c_i64, _c_f, _c_p, _c_p]),
     'ctcasr_adam_step_clipped': (_c_int, [_c_p] * 4 + [_c_i64] + [_c_f] * 4 +
                                  [_c_i64, _c_f, _c_p, _c_p, _c_p]),
+    'ctcasr_adam_step_ema': (_c_int, [_c_p] * 5 + [_c_i64] + [_c_f] * 4 +
+                             [_c_i64, _c_f, _c_p, _c_p, _c_f, _c_p]),
     'ctcasr_grad_norm_workspace_bytes': (_c_sz, [_c_i64, _c_int]),
     'ctcasr_grad_norm': (_c_int, [_c_p, _c_i64, _c_p, _c_int, _c_f, _c_f] + [_c_p] * 4 +
                          [_c_sz, _c_p]),
@@ -1338,15 +1340,33 @@ def transpose_batched(src, out=None):
 
 @_on_tensor_device
 def adam_step(param, grad, m, v, step, lr=1e-5, beta1=0.9, beta2=0.999, epsilon=1e-8,
-              grad_scale=1.0, skip=None, grad_factor=None):
+              grad_scale=1.0, skip=None, grad_factor=None, ema=None, ema_alpha=None):
     """TensorFlow-form Adam over the flat arenas.  ``skip`` (optional int32 device tensor): the
     update is dropped on the device when skip[0] != 0 (`step_guard`).  ``grad_factor`` (optional
     float32 device tensor of one element, `grad_norm`'s clip factor): the gradients are scaled by
-    ``grad_scale * grad_factor[0]``, one float32 product, without the host reading the factor."""
+    ``grad_scale * grad_factor[0]``, one float32 product, without the host reading the factor.
+    ``ema`` (optional float32 device tensor of ``param.numel()`` elements) with ``ema_alpha``
+    (a float in [0, 1]): the same launch also moves the average, ``ema += ema_alpha * (param_new
+    - ema)`` (`ctcasr_adam_step_ema`); param, m and v come out the same bits either way."""
     for name, tensor in (('grad', grad), ('m', m), ('v', v)):
         _expect_numel('adam_step', name, tensor, param.numel())
     if skip is not None and skip.numel() < 1:
         raise CtcAsrError('adam_step: skip holds no word.')
+    if ema is not None:
+        _expect_numel('adam_step', 'ema', ema, param.numel())
+        if ema_alpha is None:
+            raise CtcAsrError('adam_step: ema needs ema_alpha.')
+        if grad_factor is not None:
+            _expect_numel('adam_step', 'grad_factor', grad_factor, 1)
+        _check(load().ctcasr_adam_step_ema(
+            _dev(param, name='param'), _dev(grad, name='grad'), _dev(m, name='m'),
+            _dev(v, name='v'), _dev(ema, name='ema'), param.numel(), float(lr), float(beta1),
+            float(beta2), float(epsilon), int(step), float(grad_scale),
+            _dev(skip, torch.int32, 'skip'), _dev(grad_factor, name='grad_factor'),
+            float(ema_alpha), _stream()), 'adam_step')
+        return
+    if ema_alpha is not None:
+        raise CtcAsrError('adam_step: ema_alpha without ema.')
     if grad_factor is not None:
         _expect_numel('adam_step', 'grad_factor', grad_factor, 1)
         _check(load().ctcasr_adam_step_clipped(

@@ -14,6 +14,7 @@ the recurrence, CTC, softmax, activations epilogues, decoding and the optimiser 
 kernels behind ``include/ctcasr.h``.
 """
 
+import contextlib
 import math
 import os
 
@@ -22,6 +23,7 @@ import torch
 
 from ctc_asr_amd import hip, metrics, split_gemm
 from ctc_asr_amd.labels import num_classes
+from ctc_asr_amd.params import ema_alpha_at
 
 CONV_KERNEL_SIZES = ((11, 41), (11, 21), (11, 21))   # (time, freq), asr/util/tf_contrib.py:66
 CONV_STRIDES = ((2, 2), (1, 2), (1, 2))              # asr/util/tf_contrib.py:67
@@ -228,9 +230,12 @@ class ParamArena:
     ``[Cout, Cin, kt, kf]`` (what the convolution consumes); ``load`` / ``export`` convert.
     Every tensor starts on a 16-byte boundary.  Layers appear in forward order, so a layer's
     gradients are one contiguous slice (``layer_slices``) — the unit of the bucketed all-reduce.
+    ``ema=True`` adds a fifth arena, the exponential moving average of the parameters that
+    `hip.adam_step(ema=...)` keeps: a copy of ``param`` until the first update moves it
+    (`seed_ema`: at construction, after `load`, after a restore that carries no average).
     """
 
-    def __init__(self, cfg, device):
+    def __init__(self, cfg, device, ema=False):
         self.cfg, self.device = cfg, device
         self.offsets, self.shapes = {}, {}
         self.layer_slices = []          # [(layer_name, start, stop)] in forward order
@@ -251,6 +256,7 @@ class ParamArena:
         self.grad = torch.zeros(cursor, dtype=torch.float32, device=device)
         self.m = torch.zeros(cursor, dtype=torch.float32, device=device)
         self.v = torch.zeros(cursor, dtype=torch.float32, device=device)
+        self.ema = torch.zeros(cursor, dtype=torch.float32, device=device) if ema else None
         self.p = {n: self._view(self.param, n) for n in self.offsets}
         self.g = {n: self._view(self.grad, n) for n in self.offsets}
         self.version = 0                # bumped when the parameters are replaced wholesale
@@ -276,10 +282,21 @@ class ParamArena:
                 value = value.permute(3, 2, 0, 1)
             self.p[name].copy_(value.contiguous().to(self.device))
         self.version += 1
+        self.seed_ema()
+
+    def seed_ema(self):
+        """Start the average (if there is one) from the parameters as they stand."""
+        if self.ema is not None:
+            self.ema.copy_(self.param)
 
     def export(self, which='param'):
-        """name->numpy dict in the shared layout (``which``: 'param' or 'grad')."""
-        views = self.p if which == 'param' else self.g
+        """name->numpy dict in the shared layout (``which``: 'param', 'grad' or 'ema')."""
+        if which == 'ema':
+            if self.ema is None:
+                raise ValueError('export: this arena keeps no averaged parameters.')
+            views = {n: self._view(self.ema, n) for n in self.offsets}
+        else:
+            views = self.p if which == 'param' else self.g
         out = {}
         for name, view in views.items():
             value = view.detach().cpu()
@@ -367,7 +384,7 @@ class CTCModel:
     ``CTCModel`` with torch tensors in place of TensorFlow tensors; ``forward_backward`` /
     ``apply_gradients`` are the explicit counterparts of ``optimizer.minimize``."""
 
-    def __init__(self, cfg, device='cuda', seed=0, params=None, conv_autotune=None):
+    def __init__(self, cfg, device='cuda', seed=0, params=None, conv_autotune=None, ema=False):
         hip.load()
         # The reference's convolution stack (1 -> 32 -> 32 [-> 96] channels) runs entirely on this
         # package's own kernels - forward, data gradient and kernel gradient, any number of
@@ -387,7 +404,7 @@ class CTCModel:
         self.device = torch.device(device)
         if self.device.type != 'cuda':
             raise hip.CtcAsrError('CTCModel runs on the MI355X only; there is no CPU path.')
-        self.arena = ParamArena(cfg, self.device)
+        self.arena = ParamArena(cfg, self.device, ema=ema)
         self._grad_norm_state = None    # (offset table, workspace, result) of `grad_norms`
         self.arena.load(params if params is not None else init_params(cfg, seed))
         self.step_count = 0
@@ -1201,10 +1218,14 @@ class CTCModel:
                              .format(np.nonzero(bad == 2)[0].tolist()))
 
     # ------------------------------------------------------------------ backward
-    def backward(self, reduce_hook=None):
+    def backward(self, reduce_hook=None, accumulate=False):
         """Back-propagate ``dlogits`` (set by `loss_fn`) through the stack; fills the gradient
         arena.  ``reduce_hook(layer_name, start, stop)`` is called as soon as a layer's slice of
-        the arena is final (logits first, front-end last) — the bucketed all-reduce hook."""
+        the arena is final (logits first, front-end last) — the bucketed all-reduce hook.
+        ``accumulate``: the arena is not cleared first - this pass's gradients are ADDED to what
+        it holds (the micro-batches of one update, `engine.Trainer(grad_accum_steps=...)`); the
+        few gradients that are plain writes (library GEMMs with ``out=``, the convolutions'
+        kernel gradients) then go through a scratch tensor and one add."""
         cfg, p, g, acts = self.cfg, self.arena.p, self.arena.g, self._acts
         if acts is None or 'dlogits' not in acts:
             raise RuntimeError('backward() needs inference_fn() and loss_fn() first.')
@@ -1216,7 +1237,19 @@ class CTCModel:
 
         # (every weight gradient below ACCUMULATES into the arena - step ranges, directions and the
         # kernels' bias sums add their shares - so the arena starts from zero here)
-        self.arena.grad.zero_()
+        if not accumulate:
+            self.arena.grad.zero_()
+
+        def write(view, fn):
+            """``fn(out)`` WRITES a gradient into ``out``: the arena's view itself, or under
+            ``accumulate`` a scratch tensor that is then added to it."""
+            if not accumulate:
+                fn(view)
+                return
+            scratch = torch.empty_like(view)
+            fn(scratch)
+            view.add_(scratch)
+
         arith = acts.setdefault('arithmetic', {})
         training = acts['training']
         t_out, batch = acts['t_out'], acts['batch']
@@ -1275,7 +1308,7 @@ class CTCModel:
             hip.transpose_batched(p['rnn{}/w_hh'.format(i)], out=self._w_hh_t[i])
 
         # logits layer
-        torch.mm(acts['dense4'].t(), dlogits, out=g['logits/kernel'])
+        write(g['logits/kernel'], lambda out: torch.mm(acts['dense4'].t(), dlogits, out=out))
         hip.colsum_accumulate(dlogits, g['logits/bias'])
         d_dense4 = torch.mm(dlogits, p['logits/kernel'].t())
         done('logits')
@@ -1316,7 +1349,8 @@ class CTCModel:
                 inv = getattr(flat16, 'col_inv', None)
                 if inv is None:
                     inv = torch.ones(pieces.cols, dtype=torch.float32, device=dz.device)
-                g['dense4/kernel'].zero_()
+                if not accumulate:
+                    g['dense4/kernel'].zero_()
                 split_gemm.wgrad16(g['dense4/kernel'], pieces.buf, inv,
                                    split_gemm.Split(dz16, split_gemm.H_B), scale, 0,
                                    x_col_inv=dz_inv)
@@ -1326,9 +1360,9 @@ class CTCModel:
                 if acts['flat_split'] is None:      # (the forward pass used fp16 pieces)
                     acts['flat_split'] = split_gemm.split(acts['rnn_flat'], split_gemm.A_ORDER)
                 split_gemm.mm_tn_rows(g['dense4/kernel'], acts['flat_split'], dz_split, 0, rows,
-                                      accumulate=False)
+                                      accumulate=accumulate)
             else:
-                torch.mm(acts['rnn_flat'].t(), dz, out=g['dense4/kernel'])
+                write(g['dense4/kernel'], lambda out: torch.mm(acts['rnn_flat'].t(), dz, out=out))
             if early:
                 done('dense4')
 
@@ -1653,19 +1687,19 @@ class CTCModel:
                 if chunks > 1 or use_split:   # the earlier launches' shares are already in
                     partial_weight_grads(0, last, colmax=colmax)
                     return
-                torch.mm(dxw2d.t(), x.view(rows, -1),
-                         out=g[name + '/w_ih'].view(2 * gates * hidden, -1))
+                write(g[name + '/w_ih'].view(2 * gates * hidden, -1),
+                      lambda out: torch.mm(dxw2d.t(), x.view(rows, -1), out=out))
                 # (drec: the gradient w.r.t. the recurrent pre-activations - dxw itself, except for
                 # the GRU)
                 # dW_hh[d] = sum_t drec_t^T h_{t-1}: one GEMM per direction over shifted views
                 if t_out > 1:
                     gh = gates * hidden
-                    torch.mm(drec[1:, :, 0, :].reshape((t_out - 1) * batch, gh).t(),
-                             y[:-1, :, :hidden].reshape((t_out - 1) * batch, hidden),
-                             out=g[name + '/w_hh'][0])
-                    torch.mm(drec[:-1, :, 1, :].reshape((t_out - 1) * batch, gh).t(),
-                             y[1:, :, hidden:].reshape((t_out - 1) * batch, hidden),
-                             out=g[name + '/w_hh'][1])
+                    write(g[name + '/w_hh'][0], lambda out: torch.mm(
+                        drec[1:, :, 0, :].reshape((t_out - 1) * batch, gh).t(),
+                        y[:-1, :, :hidden].reshape((t_out - 1) * batch, hidden), out=out))
+                    write(g[name + '/w_hh'][1], lambda out: torch.mm(
+                        drec[:-1, :, 1, :].reshape((t_out - 1) * batch, gh).t(),
+                        y[1:, :, hidden:].reshape((t_out - 1) * batch, hidden), out=out))
 
             def layer_weight_grads(name=name, weight_grads=weight_grads):
                 weight_grads()
@@ -1726,8 +1760,9 @@ class CTCModel:
                     # first layer: kernel gradient straight from the features, no padded copy
                     wrw0 = hip.conv0_wrw16 if (self.conv_f16 and self.conv_wrw_f16) \
                         else hip.conv0_wrw
-                    wrw0(dz.permute(0, 2, 3, 1), acts['features'], out=g[name + '/kernel'],
-                         dbias=g[name + '/bias'] if fused_bwd else None, **mask)
+                    write(g[name + '/kernel'], lambda out: wrw0(
+                        dz.permute(0, 2, 3, 1), acts['features'], out=out,
+                        dbias=g[name + '/bias'] if fused_bwd else None, **mask))
                     done(name)
                     continue
                 conv_in = acts['conv_in'][i]
@@ -1738,14 +1773,14 @@ class CTCModel:
                     dz_phys = dz if tm else dz.permute(0, 2, 3, 1)
                     if acts['conv_f16'].get(i) and self.conv_wrw_f16:
                         # (the layer's input is bounded: the scale the forward pass used)
-                        hip.conv_s12_wrw16(dz_phys, conv_in.permute(0, 2, 3, 1),
-                                           acts['conv_f16'][i], out=g[name + '/kernel'],
-                                           time_major=tm,
-                                           dbias=g[name + '/bias'] if fused_bwd else None, **mask)
+                        write(g[name + '/kernel'], lambda out: hip.conv_s12_wrw16(
+                            dz_phys, conv_in.permute(0, 2, 3, 1), acts['conv_f16'][i], out=out,
+                            time_major=tm, dbias=g[name + '/bias'] if fused_bwd else None,
+                            **mask))
                     else:
-                        hip.conv_s12_wrw(dz_phys, conv_in.permute(0, 2, 3, 1),
-                                         out=g[name + '/kernel'], time_major=tm,
-                                         dbias=g[name + '/bias'] if fused_bwd else None, **mask)
+                        write(g[name + '/kernel'], lambda out: hip.conv_s12_wrw(
+                            dz_phys, conv_in.permute(0, 2, 3, 1), out=out, time_major=tm,
+                            dbias=g[name + '/bias'] if fused_bwd else None, **mask))
                     if i > 0 and acts['conv_f16'].get(i):
                         # (the fp16 pieces of this step's weights, packed by the forward pass)
                         dact = hip.conv_s12_bwd_data16(dz_phys, self._conv_packed16[i],
@@ -1760,7 +1795,10 @@ class CTCModel:
                     dz, conv_in, self._conv_kernel_cl(i), [p[name + '/bias'].shape[0]],
                     list(CONV_STRIDES[i]), [0, 0], [1, 1], False, [0, 0], 1,
                     [need_dx, True, False])
-                g[name + '/kernel'].copy_(dw)
+                if accumulate:
+                    g[name + '/kernel'].add_(dw)
+                else:
+                    g[name + '/kernel'].copy_(dw)
                 if need_dx:
                     dact = dxp[:, :, pt0:dxp.shape[2] - pt1, pf0:dxp.shape[3] - pf1] \
                         .permute(0, 2, 3, 1).contiguous()
@@ -1774,18 +1812,24 @@ class CTCModel:
                 dz = hip.bias_act_bwd(acts['dense_out'][i], dact.contiguous(), cfg.relu_cutoff,
                                       cfg.dense_dropout_rate if training else 0.0,
                                       g[name + '/bias'])
-                torch.mm(acts['dense_in'][i].t(), dz, out=g[name + '/kernel'])
+                write(g[name + '/kernel'],
+                      lambda out: torch.mm(acts['dense_in'][i].t(), dz, out=out))
                 if i > 0:
                     dact = torch.mm(dz, p[name + '/kernel'].t())
                 done(name)
         if side is not main:
             main.wait_stream(side)
 
-    def forward_backward(self, features, feature_len, labels, reduce_hook=None, check=True):
-        """One training forward + backward; returns the mean CTC loss (device scalar)."""
+    def forward_backward(self, features, feature_len, labels, reduce_hook=None, check=True,
+                         accumulate=False):
+        """One training forward + backward; returns the mean CTC loss (device scalar).
+        ``accumulate``: see `backward`."""
         logits, seq_length = self.inference_fn(features, feature_len, training=True)
         loss = self.loss_fn(logits, seq_length, labels, check=check)
-        self.backward(reduce_hook)
+        if accumulate:
+            self.backward(reduce_hook, accumulate=True)
+        else:
+            self.backward(reduce_hook)
         return loss
 
     def step_guard(self):
@@ -1831,15 +1875,48 @@ class CTCModel:
                              workspace=workspace)
 
     def apply_gradients(self, learning_rate=1e-5, beta1=0.9, beta2=0.999, epsilon=1e-8,
-                        grad_scale=1.0, skip=None, grad_factor=None):
+                        grad_scale=1.0, skip=None, grad_factor=None, ema_decay=0.0):
         """TensorFlow-form Adam over the whole arena in one launch (``asr/model.py:80-83``).
         ``skip``: the device flag of `step_guard` - parameters and moments stay untouched when
         it is set (the step counter still advances).  ``grad_factor``: the device-side clip
-        factor of `grad_norms`, multiplied into ``grad_scale`` by the kernel."""
-        self.step_count += 1
+        factor of `grad_norms`, multiplied into ``grad_scale`` by the kernel.  ``ema_decay`` > 0
+        (a model built with ``ema=True``): the same launch moves ``arena.ema`` towards the new
+        parameters with ``1 - decay_t``, ``decay_t = min(ema_decay, (1 + k) / (10 + k))`` for k
+        updates counted before this one (`params.ema_decay_at`)."""
         a = self.arena
-        hip.adam_step(a.param, a.grad, a.m, a.v, self.step_count, learning_rate, beta1, beta2,
-                      epsilon, grad_scale, skip=skip, grad_factor=grad_factor)
+        if ema_decay > 0.0 and a.ema is None:
+            raise hip.CtcAsrError('apply_gradients: ema_decay needs a model built with ema=True.')
+        alpha = ema_alpha_at(ema_decay, self.step_count) if ema_decay > 0.0 else None
+        self.step_count += 1
+        if alpha is None:
+            hip.adam_step(a.param, a.grad, a.m, a.v, self.step_count, learning_rate, beta1, beta2,
+                          epsilon, grad_scale, skip=skip, grad_factor=grad_factor)
+        else:
+            hip.adam_step(a.param, a.grad, a.m, a.v, self.step_count, learning_rate, beta1, beta2,
+                          epsilon, grad_scale, skip=skip, grad_factor=grad_factor, ema=a.ema,
+                          ema_alpha=alpha)
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Run the body with the averaged parameters in place of the trained ones (evaluation
+        between epochs): ``param`` and ``ema`` change places by copies through one scratch buffer
+        on the way in and back on the way out, also when the body raises; `ParamArena.touch` both
+        times, since everything derived from the parameters is stale."""
+        a = self.arena
+        if a.ema is None:
+            raise hip.CtcAsrError('ema_weights: the model was built without an average.')
+
+        def swap():
+            scratch = a.param.clone()
+            a.param.copy_(a.ema)
+            a.ema.copy_(scratch)
+            a.touch()
+
+        swap()
+        try:
+            yield self
+        finally:
+            swap()
 
     # ------------------------------------------------------------------ estimator-style entry
     def model_fn(self, features, labels, mode, learning_rate=1e-5, adam=(0.9, 0.999, 1e-8)):

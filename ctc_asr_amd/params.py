@@ -173,12 +173,111 @@ FLAGS.define('string', 'feature_normalization', 'local', "Per-utterance normalis
 FLAGS.define('bool', 'features_drop_every_second_frame', False,
              'Keep only every second feature frame (Deep Speech 1 style).')
 
-# Learning rate (asr/params.py:63-74; the three decay flags are inert in the reference too).
+# Learning rate (asr/params.py:63-74; the three decay flags are inert in the reference - here
+# --lr_schedule staircase makes them do what their help texts there say).
 FLAGS.define('int', 'max_epochs', 15, 'Total epochs (the first one walks the CSV in order).')
-FLAGS.define('float', 'learning_rate', 1e-5, 'Adam step size.')
-FLAGS.define('float', 'learning_rate_decay_factor', 4 / 5, 'Accepted, inert (as in the reference).')
-FLAGS.define('int', 'steps_per_decay', 75000, 'Accepted, inert.')
-FLAGS.define('float', 'minimum_lr', 1e-6, 'Accepted, inert. ')
+FLAGS.define('float', 'learning_rate', 1e-5, 'Adam step size (the initial one under a schedule).')
+FLAGS.define('float', 'learning_rate_decay_factor', 4 / 5,
+             'Factor the learning rate is multiplied by at each decay (--lr_schedule staircase).')
+FLAGS.define('int', 'steps_per_decay', 75000,
+             'Updates between two decays of the learning rate (--lr_schedule staircase).')
+FLAGS.define('float', 'minimum_lr', 1e-6,
+             'Floor of the staircase schedule; where the cosine schedule ends.')
+
+LR_SCHEDULES = ('constant', 'staircase', 'cosine')
+
+
+def _one_of(name, choices):
+    def check(value):
+        if value not in choices:
+            raise ValueError('--{}={} is none of {}.'.format(name, value, ', '.join(choices)))
+    return check
+
+
+def _int_range(name, low, high=None):
+    def check(value):
+        if value < low or (high is not None and value > high):
+            raise ValueError('--{}={} is outside {}..{}.'.format(
+                name, value, low, 'unbounded' if high is None else high))
+    return check
+
+
+def _ema_decay_check(value):
+    if not 0.0 <= value < 1.0:          # (a NaN fails both comparisons)
+        raise ValueError('--ema_decay={} is outside 0 <= d < 1.'.format(value))
+
+
+# The rest of the training recipe (no counterpart in the reference; all off by default: a training
+# step then launches what it always did).
+FLAGS.define('string', 'lr_schedule', 'constant',
+             'constant | staircase (learning_rate_decay_factor every steps_per_decay updates, '
+             'down to minimum_lr) | cosine (half a cosine down to minimum_lr over '
+             'lr_total_steps updates).', _one_of('lr_schedule', LR_SCHEDULES))
+FLAGS.define('int', 'lr_warmup_steps', 0,
+             'Updates over which any schedule ramps up linearly from zero (0: no warm-up).',
+             _int_range('lr_warmup_steps', 0))
+FLAGS.define('int', 'lr_total_steps', 0, 'Length of the cosine schedule in updates.')
+FLAGS.define('int', 'grad_accum_steps', 1,
+             'Micro-batches whose gradients are summed into one update (1..1024).',
+             _int_range('grad_accum_steps', 1, 1024))
+FLAGS.define('float', 'ema_decay', 0.0,
+             'Decay of the exponential moving average of the parameters, kept in the Adam '
+             'launch (0 <= d < 1; 0: off).', _ema_decay_check)
+FLAGS.define('bool', 'eval_ema', False,
+             'Evaluate, predict, align and export with the averaged parameters.')
+
+
+def learning_rate_at(update, flags=FLAGS):
+    """The learning rate of update number ``update`` (1-based), a pure function of the flags, in
+    float64: 'constant' - ``learning_rate``; 'staircase' - ``max(minimum_lr, learning_rate *
+    learning_rate_decay_factor ** ((update - 1) // steps_per_decay))``; 'cosine' - half a cosine
+    from ``learning_rate`` down to ``minimum_lr`` over ``lr_total_steps`` updates, ``minimum_lr``
+    after them; any of them times ``min(1, update / lr_warmup_steps)`` when that is positive.
+    Under 'constant' without warm-up the result is ``learning_rate`` itself, the same float."""
+    if update < 1:
+        raise ValueError('learning_rate_at: updates count from 1 (got {}).'.format(update))
+    base = flags.learning_rate
+    schedule = getattr(flags, 'lr_schedule', 'constant')
+    if schedule == 'constant':
+        rate = base
+    elif schedule == 'staircase':
+        if flags.steps_per_decay < 1:
+            raise ValueError('--lr_schedule staircase needs --steps_per_decay > 0.')
+        rate = max(float(flags.minimum_lr), float(base) * float(flags.learning_rate_decay_factor)
+                   ** ((int(update) - 1) // int(flags.steps_per_decay)))
+    elif schedule == 'cosine':
+        total = int(getattr(flags, 'lr_total_steps', 0))
+        if total <= 0:
+            raise ValueError('--lr_schedule cosine needs --lr_total_steps > 0.')
+        low = float(flags.minimum_lr)
+        if update >= total:
+            rate = low
+        else:
+            rate = low + 0.5 * (float(base) - low) * (1.0 + np.cos(np.pi * (update - 1) /
+                                                                   (total - 1)))
+            rate = float(rate)
+    else:
+        raise ValueError('Unknown --lr_schedule "{}".'.format(schedule))
+    warmup = int(getattr(flags, 'lr_warmup_steps', 0))
+    if warmup > 0 and update < warmup:
+        rate = float(rate) * (float(update) / warmup)
+    return rate
+
+
+def ema_decay_at(ema_decay, num_updates):
+    """``min(ema_decay, (1 + k) / (10 + k))`` with k = ``num_updates``, the updates counted BEFORE
+    this one: the decay ``tf.train.ExponentialMovingAverage(decay, num_updates)`` applies, so that
+    a young average follows the parameters instead of its own starting point.  float64."""
+    k = float(num_updates)
+    if k < 0:
+        raise ValueError('ema_decay_at: num_updates is negative.')
+    return min(float(ema_decay), (1.0 + k) / (10.0 + k))
+
+
+def ema_alpha_at(ema_decay, num_updates):
+    """``1 - ema_decay_at(...)`` in float64: what `hip.adam_step(ema_alpha=...)` is handed (it
+    rounds to float32 once, at the ABI)."""
+    return 1.0 - ema_decay_at(ema_decay, num_updates)
 
 # Adam (asr/params.py:76-82).
 FLAGS.define('float', 'adam_beta1', 0.9, 'First-moment decay.')
@@ -197,14 +296,6 @@ FLAGS.define('bool', 'report_grad_norms', False,
 # 'train_bucket' and 'train_batch' augment; evaluate / predict / align never do.
 SPECAUG_MAX_MASKS = 16          # CTCASR_SPEC_AUGMENT_MAX_MASKS
 SPEED_PERCENT_RANGE = (50, 200)
-
-
-def _int_range(name, low, high=None):
-    def check(value):
-        if value < low or (high is not None and value > high):
-            raise ValueError('--{}={} is outside {}..{}.'.format(
-                name, value, low, 'unbounded' if high is None else high))
-    return check
 
 
 def parse_speed_perturb(text):
@@ -341,4 +432,11 @@ def get_parameters():
                         FLAGS.spec_augment, FLAGS.specaug_freq_masks, FLAGS.specaug_freq_width,
                         FLAGS.specaug_time_masks, FLAGS.specaug_time_width,
                         FLAGS.specaug_time_permille, FLAGS.speed_perturb or 'off'))
+    if FLAGS.lr_schedule != 'constant' or FLAGS.lr_warmup_steps > 0 or \
+            FLAGS.grad_accum_steps > 1 or FLAGS.ema_decay > 0 or FLAGS.eval_ema:
+        rows.append('\tSchedule (lr_schedule={}, minimum_lr={}, warmup_steps={:,d}, '
+                    'total_steps={:,d}, grad_accum_steps={:,d}, ema_decay={}, eval_ema={});'
+                    .format(FLAGS.lr_schedule, FLAGS.minimum_lr, FLAGS.lr_warmup_steps,
+                            FLAGS.lr_total_steps, FLAGS.grad_accum_steps, FLAGS.ema_decay,
+                            FLAGS.eval_ema))
     return '\n'.join(rows)

@@ -44,7 +44,7 @@ def main(argv=None):
     latest = storage.latest_checkpoint(FLAGS.train_dir)
     if latest is None:
         raise SystemExit('No checkpoint found in {}.'.format(FLAGS.train_dir))
-    storage.restore_checkpoint(latest, model)
+    storage.restore_checkpoint(latest, model, weights='ema' if FLAGS.eval_ema else 'param')
     print('Inputs: {}'.format(FLAGS.input))
     print(predict(model, FLAGS.input, FLAGS.timestamps, lm.from_flags(model.cfg.num_classes)))
     return 0

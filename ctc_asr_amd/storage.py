@@ -46,6 +46,8 @@ def save_checkpoint(train_dir, model, epoch, extra=None):
     state = {'step': model.step_count, 'epoch': epoch, 'param': arena.param.cpu(),
              'm': arena.m.cpu(), 'v': arena.v.cpu(), 'dropout_seed': model.dropout_seed,
              'shapes': arena.shapes, 'offsets': arena.offsets, 'extra': extra or {}}
+    if getattr(arena, 'ema', None) is not None:
+        state['ema'] = arena.ema.cpu()      # the averaged parameters (--ema_decay)
     path = os.path.join(train_dir, 'model-{}.pt'.format(model.step_count))
     tmp = path + '.tmp'
     torch.save(state, tmp)
@@ -55,13 +57,24 @@ def save_checkpoint(train_dir, model, epoch, extra=None):
     return path
 
 
-def restore_checkpoint(path, model):
+def restore_checkpoint(path, model, weights='param'):
+    """``weights='ema'``: the averaged parameters of the checkpoint take the place of the trained
+    ones (evaluation with --eval_ema); a file without an average is refused.  An arena that keeps
+    an average takes the file's, or starts it from the parameters when the file has none (a
+    checkpoint written before --ema_decay was switched on)."""
+    if weights not in ('param', 'ema'):
+        raise ValueError("restore_checkpoint: weights must be 'param' or 'ema'.")
     state = torch.load(path, map_location='cpu', weights_only=False)
     arena = model.arena
     if state['shapes'] != arena.shapes:
         raise ValueError('Checkpoint {} was written for a different network layout.'.format(path))
-    arena.param.copy_(state['param'])
+    if weights == 'ema' and state.get('ema') is None:
+        raise ValueError('Checkpoint {} holds no averaged parameters (it was written without '
+                         '--ema_decay).'.format(path))
+    arena.param.copy_(state['ema' if weights == 'ema' else 'param'])
     arena.touch()
+    if getattr(arena, 'ema', None) is not None:
+        arena.ema.copy_(state['ema'] if state.get('ema') is not None else arena.param)
     arena.m.copy_(state['m'])
     arena.v.copy_(state['v'])
     model.step_count = int(state['step'])
@@ -69,13 +82,14 @@ def restore_checkpoint(path, model):
     return int(state['epoch'])
 
 
-def export_tf_checkpoint(train_dir, arena, cfg, global_step):
+def export_tf_checkpoint(train_dir, arena, cfg, global_step, weights='param'):
     """Write the parameters of ``arena`` (a `ParamArena`) as a TensorFlow checkpoint
     ``<train_dir>/model.ckpt-<global_step>`` and point ``<train_dir>/checkpoint`` at it.
     Optimizer slots are not written (the reference's cuDNN layers keep theirs as opaque
-    blobs); returns the checkpoint prefix."""
+    blobs); returns the checkpoint prefix.  ``weights='ema'`` (--eval_ema) writes the averaged
+    parameters under the same names."""
     os.makedirs(train_dir, exist_ok=True)
-    variables = tf_names.to_tf_variables(arena.export(), cfg)
+    variables = tf_names.to_tf_variables(arena.export(weights), cfg)
     variables['global_step'] = np.array(int(global_step), dtype=np.int64)
     name = 'model.ckpt-{}'.format(int(global_step))
     prefix = os.path.join(train_dir, name)

@@ -9,6 +9,7 @@ i.e. SortaGrad for a length-sorted manifest) -> dev evaluation -> epochs 2..max_
 (the reference's NanTensorHook, ``asr/model.py:368``).
 """
 
+import contextlib
 import math
 import os
 import sys
@@ -22,14 +23,17 @@ from ctc_asr_amd.engine import NanLossDuringTrainingError, Trainer, init_distrib
 from ctc_asr_amd.evaluate import evaluate_dataset
 from ctc_asr_amd.input_functions import input_fn_generator
 from ctc_asr_amd.model import ModelConfig
-from ctc_asr_amd.params import FLAGS, get_parameters
+from ctc_asr_amd.params import FLAGS, ema_decay_at, get_parameters
 
 
 def train_epoch(trainer, target, epoch, rank, world, writer=None, seed=None):
     """One pass over ``target``.  Every ``FLAGS.log_frequency`` steps (and at the first step)
     rank 0 prints the reference's LoggerHook line and records the summaries the reference
     records: loss, learning rate, and - from a beam-search decode of the batch just trained on -
-    mean edit distance, word error rate and ``num_samples_to_report`` decoded / original texts."""
+    mean edit distance, word error rate and ``num_samples_to_report`` decoded / original texts.
+    With --grad_accum_steps k > 1 a batch is a micro-step and the log lines come at the updates; a
+    ragged last group of fewer than k batches is dropped, as a data-parallel run cuts a ragged
+    final group of batches."""
     model = trainer.model
     if seed is None and world > 1:      # (every rank must walk the same shuffled order)
         seed = (FLAGS.random_seed or 1) * 1000 + epoch
@@ -44,7 +48,9 @@ def train_epoch(trainer, target, epoch, rank, world, writer=None, seed=None):
                                   batch.packed_labels)
         steps += 1
         logger.add_audio(batch.audio_seconds * world)
-        if model.step_count % FLAGS.log_frequency == 0 or steps == 1:
+        if trainer.accumulating:        # (an open update: nothing to log or check yet)
+            continue
+        if model.step_count % FLAGS.log_frequency == 0 or steps == trainer.grad_accum_steps:
             value = float(trainer.global_mean(loss))
             trainer.drain_checks()      # the loss read above synchronised anyway
             if not math.isfinite(value):
@@ -58,6 +64,13 @@ def train_epoch(trainer, target, epoch, rank, world, writer=None, seed=None):
                 line, examples_per_sec, audio_per_sec = logger.line(model.step_count, value)
                 if grad_norms is not None:
                     line += '; grad_norm={:.4g}'.format(grad_norms[-1])
+                ema_decay_t = None
+                if trainer.lr_scheduled:
+                    line += '; learning_rate={:.4g}'.format(trainer.lr)
+                if trainer.ema_decay > 0:
+                    # (of the update just applied: k = the updates counted before it)
+                    ema_decay_t = ema_decay_at(trainer.ema_decay, max(model.step_count - 1, 0))
+                    line += '; ema_decay_t={:.6g}'.format(ema_decay_t)
                 print('epoch {} '.format(epoch) + line)
                 if writer is not None:
                     decoded, plaintext, summary = model.decode_fn(
@@ -70,6 +83,8 @@ def train_epoch(trainer, target, epoch, rank, world, writer=None, seed=None):
                     step = model.step_count
                     writer.scalar('loss', value, step)
                     writer.scalar('learning_rate', trainer.lr, step)
+                    if ema_decay_t is not None:
+                        writer.scalar('ema_decay_t', ema_decay_t, step)
                     writer.scalar('Metrics/mean_edit_distance', mean_ed, step)
                     writer.scalar('Metrics/word_error_rate', wer, step)
                     writer.scalar('examples_per_sec', examples_per_sec, step)
@@ -85,6 +100,7 @@ def train_epoch(trainer, target, epoch, rank, world, writer=None, seed=None):
                 logger.line(model.step_count, value)
             # the decode and the summary records above are not training time
             logger.restart()
+    trainer.abandon_update()            # (a ragged last group of micro-batches is dropped)
     trainer.drain_checks()              # nothing unchecked reaches the checkpoint
     return steps, window_loss
 
@@ -109,7 +125,7 @@ def main(argv=None):
     start_epoch = 1
     latest = storage.latest_checkpoint(FLAGS.train_dir)
     if latest is not None:
-        start_epoch = storage.restore_checkpoint(latest, model) + 1
+        start_epoch = storage.restore_checkpoint(latest, model) + 1     # (and its average)
         if rank == 0:
             print('Restored {} (step {:,d}); continuing with epoch {}.'.format(
                 latest, model.step_count, start_epoch))
@@ -134,10 +150,17 @@ def main(argv=None):
             print('Starting epoch {} on {}.'.format(epoch, target))
         train_epoch(trainer, target, epoch, rank, world, writer)
         if rank == 0:
-            storage.save_checkpoint(FLAGS.train_dir, model, epoch)
+            trainer.save_checkpoint(FLAGS.train_dir, epoch)
             if os.environ.get('CTCASR_EXPORT_TF_CHECKPOINT') == '1':
-                storage.export_tf_checkpoint(FLAGS.train_dir, model.arena, cfg, model.step_count)
-        result = evaluate_dataset(model, 'dev', rank, world)
+                storage.export_tf_checkpoint(
+                    FLAGS.train_dir, model.arena, cfg, model.step_count,
+                    weights='ema' if FLAGS.eval_ema and trainer.ema_decay > 0 else 'param')
+        # --eval_ema: the dev set is scored with the averaged parameters, swapped in for the
+        # evaluation and back out (identical on every rank)
+        averaged = model.ema_weights() if FLAGS.eval_ema and trainer.ema_decay > 0 \
+            else contextlib.nullcontext()
+        with averaged:
+            result = evaluate_dataset(model, 'dev', rank, world)
         if rank == 0:
             for tag in ('loss', 'mean_edit_distance', 'word_error_rate'):
                 eval_writer.scalar(tag, result[tag], model.step_count)

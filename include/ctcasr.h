@@ -655,6 +655,22 @@ int ctcasr_adam_step_clipped(float *param, const float *grad, float *m, float *v
                              float lr, float beta1, float beta2, float epsilon, int64_t step,
                              float grad_scale, const int32_t *skip, const float *grad_factor,
                              ctcasr_stream_t stream);
+/* ... and with the exponential moving average of the parameters (K16) in the same launch: param,
+ * m and v come out as ctcasr_adam_step_clipped leaves them for the same arguments, bit for bit
+ * (the same expressions in the same order), and
+ *   ema[i] = ema[i] + ema_alpha * (param_new[i] - ema[i])        in fp32,
+ * TensorFlow's assign_sub(ema, (1 - decay) * (ema - param)): param_new is the fp32 value this
+ * launch has just formed, read from its registers; the subtraction, the product and the sum each
+ * round once (or the last two as one fused multiply-add - either way within 3 * 2^-24 *
+ * (|param_new| + |ema|) of the exact result).  ema_alpha = 1 - decay_t, formed by the host in
+ * float64 and rounded once; 0 leaves a finite average as it is.  A NaN or inf parameter reaches
+ * the average.  skip[0] != 0 leaves all four arrays untouched.  ema: fp32 [n], 16-byte aligned,
+ * NULL is CTCASR_ERR_BAD_ARGUMENT (callers without an average call the entries above), and so is
+ * an ema_alpha outside [0, 1] or NaN.  36 B of traffic per parameter instead of 28. */
+int ctcasr_adam_step_ema(float *param, const float *grad, float *m, float *v, float *ema,
+                         int64_t n, float lr, float beta1, float beta2, float epsilon,
+                         int64_t step, float grad_scale, const int32_t *skip,
+                         const float *grad_factor, float ema_alpha, ctcasr_stream_t stream);
 
 /* ---- K14: gradient norms per segment, global norm, clip factor, guard -------------------------
  * No counterpart in the reference (it does not clip).  One read of grad; nothing leaves the
