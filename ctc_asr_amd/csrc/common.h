@@ -41,6 +41,13 @@ __device__ __forceinline__ float wave_sum(float v) {
     for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
     return v;
 }
+// min(max(v, 0), cutoff) that keeps a NaN: fmaxf(NaN, 0) is 0, which would hand a finite
+// activation to the next layer, a finite loss to ctcasr_step_guard, and the step would be applied.
+// (-inf -> 0, +inf -> cutoff as before.)
+__device__ __forceinline__ float relu_clip(float v, float cutoff) {
+    const float c = fminf(fmaxf(v, 0.f), cutoff);
+    return v != v ? v : c;
+}
 // Gate non-linearities on the hardware transcendentals (v_exp_f32 / v_rcp_f32, ~1 ulp each) and
 // branch-free: the library expf / tanhf (range reduction, two divergent tanh paths, IEEE division)
 // cost ~250 VALU instructions per LSTM cell update inside every time step of the recurrence.

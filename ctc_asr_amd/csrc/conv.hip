@@ -183,14 +183,14 @@ conv_fwd_kernel(const float *__restrict__ x, const float4 *__restrict__ wp,
             const int t = t0 + (G::TT / 4) * wave + tt;
             if (t < T) {
                 // epilogue: bias, then min(max(., 0), cutoff) (tf_contrib.conv_layers' ReLU +
-                // tf.minimum) when cutoff > 0; the last layer of the stack writes time-major
+                // tf.minimum; a NaN stays a NaN: relu_clip) when cutoff > 0; the last layer of the stack writes time-major
                 // [T, B, FO, COUT] - the layout the recurrent stack reads - instead of NHWC
                 const size_t cell = y_time_major ? (size_t)t * gridDim.y + b : (size_t)b * T + t;
                 float *out = y + (cell * G::FO + fo) * COUT + n;
 #pragma unroll
                 for (int nt = 0; nt < NT; ++nt) {
                     float v = acc[ti][nt][r] + bias_v[nt];
-                    if (cutoff > 0.f) v = fminf(fmaxf(v, 0.f), cutoff);
+                    if (cutoff > 0.f) v = relu_clip(v, cutoff);
                     out[nt * 16] = v;
                 }
             }
@@ -628,9 +628,13 @@ conv0_fwd_kernel(const float *__restrict__ x, const float *__restrict__ w,
             const float *wrow = wl + ((kt * C0_KFP + 4 * j + kg) * C0_CO) + n;
             const float b0 = wrow[0], b1 = wrow[16];
             const int off = kt * C0_PW + 4 * j;
+            // kf = 41 .. 43 of the last group: the weights are zero, but 0 x NaN is NaN - a NaN
+            // feature must not reach outputs whose receptive field does not hold it
+            const bool pad_tap = 4 * j + kg >= C0_KF;
 #pragma unroll
             for (int ti = 0; ti < 10; ++ti) {
-                const float a = patch[base_a[ti] + off];
+                float a = patch[base_a[ti] + off];
+                if (4 * j + 3 >= C0_KF) a = pad_tap ? 0.f : a;
                 acc[ti][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b0, acc[ti][0], 0, 0, 0);
                 acc[ti][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b1, acc[ti][1], 0, 0, 0);
             }
@@ -648,8 +652,8 @@ conv0_fwd_kernel(const float *__restrict__ x, const float *__restrict__ w,
                 float *out = y + ((size_t)(b * t_out + t) * C0_FO + fo) * C0_CO + n;
                 float v0 = acc[ti][0][r] + bias0, v1 = acc[ti][1][r] + bias1;
                 if (cutoff > 0.f) {          // ReLU + tf.minimum(., relu_cutoff) of conv_layers
-                    v0 = fminf(fmaxf(v0, 0.f), cutoff);
-                    v1 = fminf(fmaxf(v1, 0.f), cutoff);
+                    v0 = relu_clip(v0, cutoff);
+                    v1 = relu_clip(v1, cutoff);
                 }
                 out[0] = v0;
                 out[16] = v1;

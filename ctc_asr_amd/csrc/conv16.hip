@@ -44,6 +44,13 @@ __device__ __forceinline__ unsigned f16_pieces(float s) {
            ((unsigned)__builtin_bit_cast(unsigned short, h2) << 16);
 }
 
+// clamp to the finite fp16 range that keeps a NaN (fmaxf(NaN, -65504) is -65504: a NaN input
+// would become a finite one, and the step guard would never see it)
+__device__ __forceinline__ float saturate_f16(float s) {
+    const float c = fminf(fmaxf(s, -65504.f), 65504.f);
+    return s != s ? s : c;
+}
+
 // scale that puts a magnitude with these bits into [2^14, 2^15) (1 for zero)
 __device__ __forceinline__ float scale_below_f16_max(unsigned max_bits) {
     const int e = (int)((max_bits >> 23) & 0xFF) - 127;
@@ -343,11 +350,11 @@ conv16_fwd_kernel(const float *__restrict__ x, float x_scale, const u32x4 *__res
             if (ts >= 0 && ts < T && fi >= 0 && fi < FI)
                 v = reinterpret_cast<const float4 *>(x)[((size_t)(b * T + ts) * FI + fi) * 8 + c4];
             // (saturating: an input outside the bound its scale was chosen for must not turn
-            // into inf - the caller only takes this kernel behind the clipped ReLU)
-            const unsigned q0 = f16_pieces(fminf(fmaxf(v.x * x_scale, -65504.f), 65504.f)),
-                           q1 = f16_pieces(fminf(fmaxf(v.y * x_scale, -65504.f), 65504.f)),
-                           q2 = f16_pieces(fminf(fmaxf(v.z * x_scale, -65504.f), 65504.f)),
-                           q3 = f16_pieces(fminf(fmaxf(v.w * x_scale, -65504.f), 65504.f));
+            // into inf - the caller only takes this kernel behind the clipped ReLU; a NaN stays)
+            const unsigned q0 = f16_pieces(saturate_f16(v.x * x_scale)),
+                           q1 = f16_pieces(saturate_f16(v.y * x_scale)),
+                           q2 = f16_pieces(saturate_f16(v.z * x_scale)),
+                           q3 = f16_pieces(saturate_f16(v.w * x_scale));
             char *cell = patch + (pr * G::PF + pos) * C16_CELL + 8 * c4;
             *reinterpret_cast<u32x2 *>(cell) =
                 (u32x2){(q0 & 0xFFFFu) | (q1 << 16), (q2 & 0xFFFFu) | (q3 << 16)};
@@ -415,7 +422,7 @@ conv16_fwd_kernel(const float *__restrict__ x, float x_scale, const u32x4 *__res
 #pragma unroll
                 for (int nt = 0; nt < NT; ++nt) {
                     float v = acc[ti][nt][r] * out_scale + bias_v[nt];
-                    if (cutoff > 0.f) v = fminf(fmaxf(v, 0.f), cutoff);
+                    if (cutoff > 0.f) v = relu_clip(v, cutoff);
                     out[nt * 16] = v;
                 }
             }
@@ -1000,6 +1007,11 @@ conv0_fwd16_kernel(const float *__restrict__ x, const u32x4 *__restrict__ packed
     for (int q = 0; q < Z0_QS; ++q) {
         const int gi = 4 * q + g, kt = gi / 6, kb = gi - 6 * kt;
         const int off = gi < Z0_GROUPS ? kt * Z0_PW + 8 * kb : 0;     // (weights are zero beyond)
+        // K group kb = 5 holds kf = 40 alone.  Its other seven weights are zero, but 0 x NaN is
+        // NaN: those seven A values are cleared, so that a NaN feature reaches the outputs whose
+        // receptive field holds it and no others.  (The groups beyond the last read the taps
+        // kt = 0, kf = 0 .. 7 of the same row again: inside its receptive field.)
+        const unsigned keep0 = kb == 5 ? 0x0000FFFFu : 0xFFFFFFFFu, keep = kb == 5 ? 0u : 0xFFFFFFFFu;
         Frag16 b1[2], b2[2];
 #pragma unroll
         for (int nt = 0; nt < 2; ++nt) {
@@ -1012,8 +1024,8 @@ conv0_fwd16_kernel(const float *__restrict__ x, const u32x4 *__restrict__ packed
             const u32x2 *p2 = reinterpret_cast<const u32x2 *>(copies + base_a[ti] + off + PLANE);
             const u32x2 lo1 = p1[0], hi1 = p1[1], lo2 = p2[0], hi2 = p2[1];
             Frag16 a1, a2;
-            a1.u = (u32x4){lo1.x, lo1.y, hi1.x, hi1.y};
-            a2.u = (u32x4){lo2.x, lo2.y, hi2.x, hi2.y};
+            a1.u = (u32x4){lo1.x & keep0, lo1.y & keep, hi1.x & keep, hi1.y & keep};
+            a2.u = (u32x4){lo2.x & keep0, lo2.y & keep, hi2.x & keep, hi2.y & keep};
 #pragma unroll
             for (int nt = 0; nt < 2; ++nt) {
                 acc[ti][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a1.h, b1[nt].h, acc[ti][nt], 0, 0, 0);
@@ -1035,8 +1047,8 @@ conv0_fwd16_kernel(const float *__restrict__ x, const u32x4 *__restrict__ packed
                 float *out = y + ((size_t)(b * t_out + t) * Z0_FO + fo) * 32 + n;
                 float v0 = acc[ti][0][r] * inv + bias0, v1 = acc[ti][1][r] * inv + bias1;
                 if (cutoff > 0.f) {
-                    v0 = fminf(fmaxf(v0, 0.f), cutoff);
-                    v1 = fminf(fmaxf(v1, 0.f), cutoff);
+                    v0 = relu_clip(v0, cutoff);
+                    v1 = relu_clip(v1, cutoff);
                 }
                 out[0] = v0;
                 out[16] = v1;

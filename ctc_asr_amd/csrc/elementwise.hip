@@ -11,14 +11,6 @@ __device__ __forceinline__ float uniform01(uint64_t seed, uint64_t idx) {
     return (float)splitmix64_r24(seed, idx) * (1.0f / 16777216.0f);
 }
 
-// min(max(v, 0), cutoff) that keeps a NaN: fmaxf(NaN, 0) is 0, which would hand a finite
-// activation to the next layer, a finite loss to ctcasr_step_guard, and the step would be applied.
-// (-inf -> 0, +inf -> cutoff as before.)
-__device__ __forceinline__ float relu_clip(float v, float cutoff) {
-    const float c = fminf(fmaxf(v, 0.f), cutoff);
-    return v != v ? v : c;
-}
-
 __global__ void __launch_bounds__(256)
 bias_act_fwd_kernel(float *__restrict__ y, const float *__restrict__ bias, int64_t n, int cols,
                     float cutoff, float rate, float inv_keep, uint64_t seed) {

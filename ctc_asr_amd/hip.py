@@ -1061,12 +1061,41 @@ def conv_s12_packed_floats(cout):
     return 2 * 11 * 21 * 32 * cout
 
 
+def _conv_dims(what, name, tensor, ndim):
+    """The conv wrappers read B, T, F, C off their arguments' shapes: an argument with another
+    number of dimensions is refused, not misread."""
+    if tensor.dim() != ndim:
+        raise CtcAsrError('{}: {} must have {} dimensions (got shape {}).'
+                          .format(what, name, ndim, tuple(tensor.shape)))
+    return tuple(int(d) for d in tensor.shape)
+
+
+def _conv_scale(what, x_scale):
+    x_scale = float(x_scale)
+    if not (x_scale > 0.0 and x_scale != float('inf')):
+        raise CtcAsrError('{}: x_scale must be a positive finite number (got {}).'
+                          .format(what, x_scale))
+    return x_scale
+
+
+def _conv_mask(what, dz, act, relu_cutoff, dbias, cout):
+    """``act`` is read at dz's own indices and ``dbias`` holds one sum per output channel."""
+    if act is not None:
+        if tuple(act.shape) != tuple(dz.shape):
+            raise CtcAsrError('{}: act must be shaped like dz {} (got {}).'
+                              .format(what, tuple(dz.shape), tuple(act.shape)))
+        if not float(relu_cutoff) > 0.0:
+            raise CtcAsrError('{}: act needs relu_cutoff > 0 (got {}).'.format(what, relu_cutoff))
+    _expect_numel(what, 'dbias', dbias, cout)
+
+
 @_on_tensor_device
 def conv_s12_pack_weights(weight, packed=None):
     """Fragment-ordered copies (backward, forward) of w f32[cout,32,11,21] ([Cout,Cin,kt,kf])."""
-    cout = weight.shape[0]
+    cout = weight.shape[0] if weight.dim() == 4 else 0
     if tuple(weight.shape[1:]) != (32, 11, 21) or cout not in (32, 96):
         raise CtcAsrError('the conv_s12 kernels cover w [32|96, 32, 11, 21] only.')
+    _expect_numel('conv_s12_pack_weights', 'packed', packed, conv_s12_packed_floats(cout))
     packed = torch.empty(conv_s12_packed_floats(cout), dtype=torch.float32,
                          device=weight.device) if packed is None else packed
     _check(load().ctcasr_conv_s12_pack_weights(_dev(weight, name='weight'),
@@ -1080,10 +1109,13 @@ def conv_s12_fwd(x, packed, cout, bias=None, out=None, relu_cutoff=0.0, time_maj
     """x f32[B,T,F,32] (NHWC) -> conv(x) + bias, f32[B,T,F/2,cout]; 11x21 taps, stride (1,2),
     TensorFlow SAME padding.  ``packed`` from `conv_s12_pack_weights`.  ``relu_cutoff`` > 0 fuses
     min(max(., 0), cutoff) into the epilogue; ``time_major`` writes [T,B,F/2,cout] instead."""
-    batch, frames, freq = x.shape[0], x.shape[1], x.shape[2]
-    if x.shape[3] != 32 or not conv_s12_supported(freq, cout):
+    batch, frames, freq, cin = _conv_dims('conv_s12_fwd', 'x', x, 4)
+    if cin != 32 or not conv_s12_supported(freq, cout):
         raise CtcAsrError('conv_s12_fwd: unsupported layer shape {} -> {} channels'.format(
             tuple(x.shape), cout))
+    _expect_numel('conv_s12_fwd', 'packed', packed, conv_s12_packed_floats(cout))
+    _expect_numel('conv_s12_fwd', 'bias', bias, cout)
+    _expect_numel('conv_s12_fwd', 'out', out, batch * frames * (freq // 2) * cout)
     shape = (frames, batch, freq // 2, cout) if time_major else (batch, frames, freq // 2, cout)
     out = torch.empty(shape, dtype=torch.float32, device=x.device) if out is None else out
     with _Timed('conv_s12_fwd'):
@@ -1098,7 +1130,7 @@ def conv_s12_fwd(x, packed, cout, bias=None, out=None, relu_cutoff=0.0, time_maj
 def conv_s12_pack_weights16(weight, packed=None):
     """weight f32[cout, 32, 11, 21] -> uint8 buffer for `conv_s12_fwd16`: the bit pattern of
     max |w| (found on the device) and the two fp16 pieces of w * s_w in fragment order."""
-    cout = weight.shape[0]
+    cout = weight.shape[0] if weight.dim() == 4 else 0
     nbytes = load().ctcasr_conv_s12_pack16_bytes(int(cout))
     if nbytes == 0 or tuple(weight.shape[1:]) != (32, 11, 21):
         raise CtcAsrError('conv_s12_pack_weights16: unsupported kernel shape {}'.format(
@@ -1117,14 +1149,19 @@ def conv_s12_fwd16(x, x_scale, packed16, cout, bias=None, out=None, relu_cutoff=
     """`conv_s12_fwd` with its products on the fp16 matrix pipe (two fp16 pieces per operand,
     three products, fp32 accumulation): for x with a known bound, bound * x_scale < 65504
     (``x_scale`` a power of two).  ``packed16`` from `conv_s12_pack_weights16`."""
-    batch, frames, freq = x.shape[0], x.shape[1], x.shape[2]
-    if x.shape[3] != 32 or not conv_s12_supported(freq, cout):
+    batch, frames, freq, cin = _conv_dims('conv_s12_fwd16', 'x', x, 4)
+    if cin != 32 or not conv_s12_supported(freq, cout):
         raise CtcAsrError('conv_s12_fwd16: unsupported layer shape {} -> {} channels'.format(
             tuple(x.shape), cout))
+    x_scale = _conv_scale('conv_s12_fwd16', x_scale)
+    _expect_numel('conv_s12_fwd16', 'packed16', packed16,
+                  load().ctcasr_conv_s12_pack16_bytes(int(cout)))
+    _expect_numel('conv_s12_fwd16', 'bias', bias, cout)
+    _expect_numel('conv_s12_fwd16', 'out', out, batch * frames * (freq // 2) * cout)
     shape = (frames, batch, freq // 2, cout) if time_major else (batch, frames, freq // 2, cout)
     out = torch.empty(shape, dtype=torch.float32, device=x.device) if out is None else out
     with _Timed('conv_s12_fwd'):
-        _check(load().ctcasr_conv_s12_fwd16(_dev(x, name='x'), float(x_scale),
+        _check(load().ctcasr_conv_s12_fwd16(_dev(x, name='x'), x_scale,
                                             _dev(packed16, torch.uint8, 'packed16'),
                                             _dev(bias, name='bias'), _dev(out, name='y'), batch,
                                             frames, freq, cout, float(relu_cutoff),
@@ -1132,17 +1169,24 @@ def conv_s12_fwd16(x, x_scale, packed16, cout, bias=None, out=None, relu_cutoff=
     return out
 
 
+def _conv_s12_dz(what, dz, time_major):
+    """(batch, frames, freq_out, cout) of a supported layer's dz, whichever way it is laid out."""
+    dims = _conv_dims(what, 'dz', dz, 4)
+    frames, batch = (dims[0], dims[1]) if time_major else (dims[1], dims[0])
+    if not conv_s12_supported(2 * dims[2], dims[3]):
+        raise CtcAsrError('{}: unsupported layer shape {}'.format(what, tuple(dz.shape)))
+    return batch, frames, dims[2], dims[3]
+
+
 @_on_tensor_device
 def conv_s12_bwd_data(dz, packed, out=None, time_major=False, act=None, relu_cutoff=0.0):
     """dz f32[B,T,F/2,cout] (NHWC; ``time_major``: [T,B,F/2,cout]) -> dx f32[B,T,F,32].
     ``act`` (the layer's stored output, same layout): dz is the gradient w.r.t. that output and
     the mask of min(max(., 0), relu_cutoff) is applied while dz is staged."""
-    if time_major:
-        frames, batch, freq_out, cout = dz.shape
-    else:
-        batch, frames, freq_out, cout = dz.shape
-    if not conv_s12_supported(2 * freq_out, cout):
-        raise CtcAsrError('conv_s12_bwd_data: unsupported layer shape {}'.format(tuple(dz.shape)))
+    batch, frames, freq_out, cout = _conv_s12_dz('conv_s12_bwd_data', dz, time_major)
+    _conv_mask('conv_s12_bwd_data', dz, act, relu_cutoff, None, cout)
+    _expect_numel('conv_s12_bwd_data', 'packed', packed, conv_s12_packed_floats(cout))
+    _expect_numel('conv_s12_bwd_data', 'out', out, batch * frames * 2 * freq_out * 32)
     out = torch.empty((batch, frames, 2 * freq_out, 32), dtype=torch.float32, device=dz.device) \
         if out is None else out
     with _Timed('conv_s12_bwd_data'):
@@ -1159,12 +1203,11 @@ def conv_s12_bwd_data16(dz, packed16, out=None, time_major=False, act=None, relu
     """`conv_s12_bwd_data` with its products on the fp16 matrix pipe: every dz cell (frame,
     position) is scaled by its own power of two while it is staged - no bound on dz is assumed.
     ``packed16`` from `conv_s12_pack_weights16`."""
-    if time_major:
-        frames, batch, freq_out, cout = dz.shape
-    else:
-        batch, frames, freq_out, cout = dz.shape
-    if not conv_s12_supported(2 * freq_out, cout):
-        raise CtcAsrError('conv_s12_bwd_data16: unsupported layer shape {}'.format(tuple(dz.shape)))
+    batch, frames, freq_out, cout = _conv_s12_dz('conv_s12_bwd_data16', dz, time_major)
+    _conv_mask('conv_s12_bwd_data16', dz, act, relu_cutoff, None, cout)
+    _expect_numel('conv_s12_bwd_data16', 'packed16', packed16,
+                  load().ctcasr_conv_s12_pack16_bytes(int(cout)))
+    _expect_numel('conv_s12_bwd_data16', 'out', out, batch * frames * 2 * freq_out * 32)
     out = torch.empty((batch, frames, 2 * freq_out, 32), dtype=torch.float32, device=dz.device) \
         if out is None else out
     with _Timed('conv_s12_bwd_data'):
@@ -1183,14 +1226,12 @@ def conv_s12_wrw(dz, x, out=None, time_major=False, act=None, relu_cutoff=0.0, d
     x f32[B,T,F,32] (NHWC) -> dw f32[cout,32,11,21].  ``act`` / ``relu_cutoff``: see
     `conv_s12_bwd_data`; ``dbias`` f32[cout] (zeroed by the caller) then receives the bias
     gradient, the column sums of the masked dz."""
-    if time_major:
-        frames, batch, freq_out, cout = dz.shape
-    else:
-        batch, frames, freq_out, cout = dz.shape
-    if tuple(x.shape) != (batch, frames, 2 * freq_out, 32) or \
-            not conv_s12_supported(2 * freq_out, cout):
+    batch, frames, freq_out, cout = _conv_s12_dz('conv_s12_wrw', dz, time_major)
+    if tuple(x.shape) != (batch, frames, 2 * freq_out, 32):
         raise CtcAsrError('conv_s12_wrw: unsupported layer shape {} / {}'.format(
             tuple(dz.shape), tuple(x.shape)))
+    _conv_mask('conv_s12_wrw', dz, act, relu_cutoff, dbias, cout)
+    _expect_numel('conv_s12_wrw', 'out', out, cout * 32 * 11 * 21)
     out = torch.empty((cout, 32, 11, 21), dtype=torch.float32, device=x.device) if out is None \
         else out
     workspace = _workspace(load().ctcasr_conv_s12_wrw_workspace_bytes(batch, frames,
@@ -1212,14 +1253,13 @@ def conv_s12_wrw16(dz, x, x_scale, out=None, time_major=False, act=None, relu_cu
     """`conv_s12_wrw` with its products on the fp16 matrix pipe: for x with a known bound,
     bound * x_scale < 65504 (``x_scale`` a power of two); dz is scaled per output channel on the
     device."""
-    if time_major:
-        frames, batch, freq_out, cout = dz.shape
-    else:
-        batch, frames, freq_out, cout = dz.shape
-    if tuple(x.shape) != (batch, frames, 2 * freq_out, 32) or \
-            not conv_s12_supported(2 * freq_out, cout):
+    batch, frames, freq_out, cout = _conv_s12_dz('conv_s12_wrw16', dz, time_major)
+    if tuple(x.shape) != (batch, frames, 2 * freq_out, 32):
         raise CtcAsrError('conv_s12_wrw16: unsupported layer shape {} / {}'.format(
             tuple(dz.shape), tuple(x.shape)))
+    x_scale = _conv_scale('conv_s12_wrw16', x_scale)
+    _conv_mask('conv_s12_wrw16', dz, act, relu_cutoff, dbias, cout)
+    _expect_numel('conv_s12_wrw16', 'out', out, cout * 32 * 11 * 21)
     out = torch.empty((cout, 32, 11, 21), dtype=torch.float32, device=x.device) if out is None \
         else out
     workspace = _workspace(load().ctcasr_conv_s12_wrw16_workspace_bytes(batch, frames,
@@ -1227,7 +1267,7 @@ def conv_s12_wrw16(dz, x, x_scale, out=None, time_major=False, act=None, relu_cu
                            x.device)
     with _Timed('conv_s12_wrw'):
         _check(load().ctcasr_conv_s12_wrw16(_dev(dz, name='dz'), _dev(x, name='x'),
-                                            float(x_scale), _dev(out, name='dw'), batch, frames,
+                                            x_scale, _dev(out, name='dw'), batch, frames,
                                             2 * freq_out, cout, 1 if time_major else 0,
                                             _dev(act, name='act'), float(relu_cutoff),
                                             _dev(dbias, name='dbias'),
@@ -1236,14 +1276,23 @@ def conv_s12_wrw16(dz, x, x_scale, out=None, time_major=False, act=None, relu_cu
     return out
 
 
+def _conv0_x(what, x):
+    batch, frames, freq = _conv_dims(what, 'x', x, 3)
+    if freq != 80:
+        raise CtcAsrError('{} covers x [B,T,80] only (got {}).'.format(what, tuple(x.shape)))
+    return batch, frames
+
+
 @_on_tensor_device
 def conv0_fwd(x, weight, bias=None, out=None, relu_cutoff=0.0):
     """First DS2 convolution: x f32[B,T,80] -> f32[B,ceil(T/2),40,32] (NHWC); weight
     f32[32,1,11,41], stride (2,2), TensorFlow SAME padding; ``relu_cutoff`` > 0 fuses
     min(max(., 0), cutoff) into the epilogue."""
-    batch, frames = x.shape[0], x.shape[1]
-    if x.shape[2] != 80 or tuple(weight.shape) != (32, 1, 11, 41):
+    batch, frames = _conv0_x('conv0_fwd', x)
+    if tuple(weight.shape) != (32, 1, 11, 41):
         raise CtcAsrError('conv0_fwd covers x [B,T,80] and w [32,1,11,41] only.')
+    _expect_numel('conv0_fwd', 'bias', bias, 32)
+    _expect_numel('conv0_fwd', 'out', out, batch * ((frames + 1) // 2) * 40 * 32)
     out = torch.empty((batch, (frames + 1) // 2, 40, 32), dtype=torch.float32,
                       device=x.device) if out is None else out
     with _Timed('conv0_fwd'):
@@ -1260,6 +1309,7 @@ def conv0_pack_weights16(weight, out=None):
     if tuple(weight.shape) != (32, 1, 11, 41):
         raise CtcAsrError('conv0_pack_weights16 covers w [32,1,11,41] only.')
     nbytes = load().ctcasr_conv0_pack16_bytes()
+    _expect_numel('conv0_pack_weights16', 'out', out, nbytes)
     out = torch.empty(nbytes, dtype=torch.uint8, device=weight.device) if out is None else out
     _check(load().ctcasr_conv0_pack_weights16(_dev(weight, name='weight'),
                                               _dev(out, torch.uint8, 'packed16'), _stream()),
@@ -1270,9 +1320,10 @@ def conv0_pack_weights16(weight, out=None):
 @_on_tensor_device
 def conv0_fwd16(x, packed16, bias=None, out=None, relu_cutoff=0.0):
     """`conv0_fwd` with its products on the fp16 matrix pipe (no bound on x is assumed)."""
-    batch, frames = x.shape[0], x.shape[1]
-    if x.shape[2] != 80:
-        raise CtcAsrError('conv0_fwd16 covers x [B,T,80] only.')
+    batch, frames = _conv0_x('conv0_fwd16', x)
+    _expect_numel('conv0_fwd16', 'packed16', packed16, load().ctcasr_conv0_pack16_bytes())
+    _expect_numel('conv0_fwd16', 'bias', bias, 32)
+    _expect_numel('conv0_fwd16', 'out', out, batch * ((frames + 1) // 2) * 40 * 32)
     out = torch.empty((batch, (frames + 1) // 2, 40, 32), dtype=torch.float32,
                       device=x.device) if out is None else out
     with _Timed('conv0_fwd'):
@@ -1285,9 +1336,11 @@ def conv0_fwd16(x, packed16, bias=None, out=None, relu_cutoff=0.0):
 @_on_tensor_device
 def conv0_wrw16(dz, x, out=None, act=None, relu_cutoff=0.0, dbias=None):
     """`conv0_wrw` with its products on the fp16 matrix pipe."""
-    batch, frames = x.shape[0], x.shape[1]
-    if x.shape[2] != 80 or tuple(dz.shape) != (batch, (frames + 1) // 2, 40, 32):
+    batch, frames = _conv0_x('conv0_wrw16', x)
+    if tuple(dz.shape) != (batch, (frames + 1) // 2, 40, 32):
         raise CtcAsrError('conv0_wrw16 covers x [B,T,80], dz [B,ceil(T/2),40,32] only.')
+    _conv_mask('conv0_wrw16', dz, act, relu_cutoff, dbias, 32)
+    _expect_numel('conv0_wrw16', 'out', out, 32 * 11 * 41)
     out = torch.empty((32, 1, 11, 41), dtype=torch.float32, device=x.device) if out is None \
         else out
     workspace = _workspace(load().ctcasr_conv0_wrw16_workspace_bytes(batch, frames), x.device)
@@ -1306,9 +1359,11 @@ def conv0_wrw(dz, x, out=None, act=None, relu_cutoff=0.0, dbias=None):
     """Kernel gradient of the first DS2 convolution: dz f32[B,ceil(T/2),40,32] (NHWC),
     x f32[B,T,80] -> dw f32[32,1,11,41]; ``act`` / ``relu_cutoff`` / ``dbias`` as in
     `conv_s12_wrw`."""
-    batch, frames = x.shape[0], x.shape[1]
-    if x.shape[2] != 80 or tuple(dz.shape) != (batch, (frames + 1) // 2, 40, 32):
+    batch, frames = _conv0_x('conv0_wrw', x)
+    if tuple(dz.shape) != (batch, (frames + 1) // 2, 40, 32):
         raise CtcAsrError('conv0_wrw covers x [B,T,80], dz [B,ceil(T/2),40,32] only.')
+    _conv_mask('conv0_wrw', dz, act, relu_cutoff, dbias, 32)
+    _expect_numel('conv0_wrw', 'out', out, 32 * 11 * 41)
     out = torch.empty((32, 1, 11, 41), dtype=torch.float32, device=x.device) if out is None \
         else out
     workspace = _workspace(load().ctcasr_conv0_wrw_workspace_bytes(batch, frames), x.device)
