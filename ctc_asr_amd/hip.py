@@ -26,6 +26,8 @@ RNN_KPAIR = 128       # ... and the K axis split over pairs of workgroups (ABI v
 GRAD_NORM_CHUNK = 8192
 GRAD_NORM_MAX_SEGMENTS = 64
 SPEC_AUGMENT_MAX_MASKS = 16     # ctcasr_spec_augment: frequency masks, and time masks, per call
+NOISE_MIX_CHUNK = 8192          # ctcasr_noise_mix: samples of a row per workgroup
+NOISE_MIX_SNR_DB = (-20, 60)    # ... and the SNR range it takes
 CELL_IDS = {'rnn_relu': 0, 'rnn_tanh': 1, 'lstm': 2, 'gru': 3}
 CELL_GATES = {'rnn_relu': 1, 'rnn_tanh': 1, 'lstm': 4, 'gru': 3}
 
@@ -140,6 +142,9 @@ SIGNATURES = {
                             [_c_p, _c_p]),
     'ctcasr_resample_num_samples': (_c_int, [_c_int, _c_int]),
     'ctcasr_speed_perturb': (_c_int, [_c_p, _c_p, _c_p, _c_int, _c_int, _c_p, _c_int, _c_p, _c_p]),
+    'ctcasr_noise_mix_workspace_bytes': (_c_sz, [_c_int]),
+    'ctcasr_noise_mix': (_c_int, [_c_p, _c_p, _c_int, _c_int, _c_p, _c_p, _c_int, _c_u64] +
+                         [_c_int] * 3 + [_c_p] * 5 + [_c_sz, _c_p]),
     'ctcasr_adam_step': (_c_int, [_c_p] * 4 + [_c_i64] + [_c_f] * 4 + [_c_i64, _c_f, _c_p, _c_p]),
     'ctcasr_adam_step_clipped': (_c_int, [_c_p] * 4 + [_c_i64] + [_c_f] * 4 +
                                  [_c_i64, _c_f, _c_p, _c_p, _c_p]),
@@ -1656,3 +1661,57 @@ def speed_perturb(pcm, num_samples, percent, max_out=None):
                                        _dev(out_samples, torch.int32, 'out_samples'), _stream()),
            'speed_perturb')
     return out, out_samples
+
+
+def noise_mix_workspace_bytes(batch):
+    return load().ctcasr_noise_mix_workspace_bytes(int(batch))
+
+
+@_on_tensor_device
+def noise_mix(pcm, num_samples, bank, clip_offsets, seed, snr_lo_db, snr_hi_db,
+              prob_permille=1000, out=None, draws=None, powers=None, gain=None):
+    """Mix noise into the rows of ``pcm`` int16[B, N] (``num_samples`` int32[B]) at a drawn SNR.
+    ``bank`` int16[*]: the noise clips back to back; ``clip_offsets`` int64[K + 1] (device): where
+    each starts, the last entry the bank's length.  Row b is mixed with probability
+    ``prob_permille`` / 1000, with a run of a drawn clip that starts at a drawn offset and wraps
+    at the clip's end, scaled to a whole number of dB drawn from ``snr_lo_db``..``snr_hi_db`` -
+    integer functions of (``seed``, row) pinned in include/ctcasr.h.  ``out``: int16[B, N],
+    ``pcm`` itself for in place; a new tensor when None.  Optional device tensors: ``draws``
+    int32[B, 4] (status, clip, offset, snr), ``powers`` int64[B, 2] (speech, noise), ``gain``
+    float32[B].  Returns ``out``."""
+    if pcm.dim() != 2:
+        raise CtcAsrError('noise_mix: pcm must be [B, N] (got {} dimensions).'.format(pcm.dim()))
+    batch, max_samples = pcm.shape
+    _batch_of('noise_mix', 'num_samples', num_samples, batch)
+    if clip_offsets.numel() < 2:
+        raise CtcAsrError('noise_mix: clip_offsets holds {} offsets, at least 2 needed.'
+                          .format(clip_offsets.numel()))
+    if bank.numel() < 1:
+        raise CtcAsrError('noise_mix: the noise bank is empty.')
+    if out is None:
+        out = torch.empty_like(pcm)
+    _expect_numel('noise_mix', 'out', out, batch * max_samples)
+    _expect_numel('noise_mix', 'draws', draws, batch * 4)
+    _expect_numel('noise_mix', 'powers', powers, batch * 2)
+    _expect_numel('noise_mix', 'gain', gain, batch)
+    pcm_ptr = _dev(pcm, torch.int16, 'pcm')
+    num_ptr = _dev(num_samples, torch.int32, 'num_samples')
+    bank_ptr = _dev(bank, torch.int16, 'bank')
+    off_ptr = _dev(clip_offsets, torch.int64, 'clip_offsets')
+    out_ptr = _dev(out, torch.int16, 'out')
+    draws_ptr = _dev(draws, torch.int32, 'draws')
+    powers_ptr = _dev(powers, torch.int64, 'powers')
+    gain_ptr = _dev(gain, torch.float32, 'gain')
+    for name, tensor in (('num_samples', num_samples), ('bank', bank),
+                         ('clip_offsets', clip_offsets), ('out', out), ('draws', draws),
+                         ('powers', powers), ('gain', gain)):
+        if tensor is not None and tensor.device != pcm.device:
+            raise CtcAsrError('noise_mix: {} lives on {}, pcm on {}.'
+                              .format(name, tensor.device, pcm.device))
+    workspace = _workspace(noise_mix_workspace_bytes(batch), pcm.device)
+    _check(load().ctcasr_noise_mix(
+        pcm_ptr, num_ptr, batch, max_samples, bank_ptr, off_ptr, clip_offsets.numel() - 1,
+        int(seed) & 0xFFFFFFFFFFFFFFFF, int(snr_lo_db), int(snr_hi_db), int(prob_permille),
+        out_ptr, draws_ptr, powers_ptr, gain_ptr, _dev(workspace, torch.uint8, 'workspace'),
+        workspace.numel(), _stream()), 'noise_mix')
+    return out

@@ -31,7 +31,8 @@ from scipy.io import wavfile
 from ctc_asr_amd import hip
 from ctc_asr_amd.csv_helper import get_bucket_boundaries, read_csv_rows
 from ctc_asr_amd.labels import ctoi
-from ctc_asr_amd.params import CSV_HEADER_LABEL, CSV_HEADER_PATH, FLAGS, parse_speed_perturb
+from ctc_asr_amd.params import (CSV_HEADER_LABEL, CSV_HEADER_PATH, FLAGS, check_noise_flags,
+                                parse_eval_noise_snr_db, parse_noise_snr_db, parse_speed_perturb)
 
 READER_THREADS = 8           # WAV files of one batch are read concurrently
 SUPPORTED_FEATURE_TYPES = ('mel', 'mfcc')
@@ -224,48 +225,76 @@ class Batch:
     ``packed_labels``: the same labels as `CTCModel.pack_labels` would upload them (what
     `Trainer.train_step` / `loss_fn` take without another host-to-device copy); ``pcm`` /
     ``num_samples``: the raw audio the features were computed from (device tensors) - after
-    speed perturbation where that is on, while ``audio_seconds`` stays the duration of the
-    source audio."""
+    speed perturbation and with the noise mixed in where those are on, while ``audio_seconds``
+    stays the duration of the source audio.  ``noise_draws``: int32[B, 4] device tensor, (status,
+    clip, offset, snr) of every row as `hip.noise_mix` reports them, or None for a batch that
+    went through no noise mixing."""
 
     def __init__(self, spectrogram, spectrogram_length, label_plaintext, labels, seconds,
-                 packed_labels=None, pcm=None, num_samples=None):
+                 packed_labels=None, pcm=None, num_samples=None, noise_draws=None):
         self.features = {'spectrogram': spectrogram, 'spectrogram_length': spectrogram_length,
                          'label_plaintext': label_plaintext}
         self.labels = labels
         self.audio_seconds = seconds
         self.packed_labels = packed_labels if packed_labels is not None else labels
         self.pcm, self.num_samples = pcm, num_samples
+        self.noise_draws = noise_draws
 
     def __iter__(self):      # (features, labels) = batch
         return iter((self.features, self.labels))
 
 
-class _Augmenter:
-    """Augmentation settings of ONE training iterator, read from the flags when it starts, and
-    its SpecAugment seeds: a 64-bit sequence stepped like `CTCModel._next_seed`, one value per
-    batch, so that two iterators with one seed mask alike (and two ranks of one epoch do not)."""
+EVAL_NOISE_SEED = 0x4E015E       # where the noise seeds of every 'dev' / 'test' iterator start
 
-    def __init__(self, seed, rank=0):
-        self.percents = parse_speed_perturb(FLAGS.speed_perturb)
+
+class _Augmenter:
+    """Augmentation settings of ONE iterator, read from the flags when it starts, and its
+    SpecAugment seeds: a 64-bit sequence stepped like `CTCModel._next_seed`, one value per
+    batch, so that two iterators with one seed mask alike (and two ranks of one epoch do not).
+    The noise has a sequence of its own, from another constant and stepped once per batch as
+    well: switching the noise on moves no mask and no speed.
+
+    ``training=False``: the iterator of 'dev' / 'test' - no speeds, no masks, and noise only under
+    --eval_noise_snr_db: every row, at that value, from seeds that do not depend on the epoch."""
+
+    def __init__(self, seed, rank=0, training=True, device='cuda'):
+        self.percents = parse_speed_perturb(FLAGS.speed_perturb) if training else []
         self.spec = (FLAGS.specaug_freq_masks, FLAGS.specaug_freq_width,
                      FLAGS.specaug_time_masks, FLAGS.specaug_time_width,
-                     FLAGS.specaug_time_permille) if FLAGS.spec_augment else None
+                     FLAGS.specaug_time_permille) if training and FLAGS.spec_augment else None
         self.seed = (int(seed) * 0x9E3779B1 + int(rank) * 0x85EBCA6B + 0x5A17) \
             & 0xFFFFFFFFFFFFFFFF
+        self.noise_seed = (int(seed) * 0x9E3779B1 + int(rank) * 0x85EBCA6B + 0x4E01) \
+            & 0xFFFFFFFFFFFFFFFF
+        self.noise = None          # (NoiseBank, snr_lo_db, snr_hi_db, permille)
+        check_noise_flags(FLAGS)
+        eval_snr = parse_eval_noise_snr_db(FLAGS.eval_noise_snr_db)
+        if FLAGS.noise_csv and (training or eval_snr is not None):
+            from ctc_asr_amd.noise import NoiseBank
+            if training:
+                self.noise = (NoiseBank.from_flags(device),) + \
+                    parse_noise_snr_db(FLAGS.noise_snr_db) + (FLAGS.noise_permille,)
+            else:
+                self.noise = (NoiseBank.from_flags(device), eval_snr, eval_snr, 1000)
 
     def __bool__(self):
-        return bool(self.percents) or self.spec is not None
+        return bool(self.percents) or self.spec is not None or self.noise is not None
 
     def next_seed(self):
         self.seed = (self.seed * 6364136223846793005 + 1442695040888963407) & 0xFFFFFFFFFFFFFFFF
         return self.seed
 
+    def next_noise_seed(self):
+        self.noise_seed = (self.noise_seed * 6364136223846793005 + 1442695040888963407) \
+            & 0xFFFFFFFFFFFFFFFF
+        return self.noise_seed
+
 
 def _make_batch(items, device, staged=None, augment=None):
     """Features of one batch on the current stream.  ``staged``: the batch's `_Staged` uploads
     (made by the reader thread); without it they are made here.  ``augment``: the `_Augmenter`
-    of a training iterator - speed perturbation of the PCM, then the features, then SpecAugment,
-    all on this stream; without it exactly the launches of a plain batch."""
+    of the iterator - speed perturbation of the PCM, then the noise, then the features, then
+    SpecAugment, all on this stream; without it exactly the launches of a plain batch."""
     if staged is None:
         staged = _Staged(items, device, torch.cuda.current_stream(device))
     main = torch.cuda.current_stream(device)
@@ -277,6 +306,14 @@ def _make_batch(items, device, staged=None, augment=None):
     if staged.percent is not None:
         pcm, num_samples = hip.speed_perturb(pcm, num_samples, staged.percent,
                                              staged.perturbed_width)
+    noise_draws = None
+    if augment is not None and augment.noise is not None:
+        # in place: the PCM of this batch is a tensor of its own (the upload, or the resampler's
+        # output), and rows that draw no noise are then not stored at all
+        bank, snr_lo, snr_hi, permille = augment.noise
+        noise_draws = torch.empty((pcm.shape[0], 4), dtype=torch.int32, device=pcm.device)
+        hip.noise_mix(pcm, num_samples, bank.bank, bank.clip_offsets, augment.next_noise_seed(),
+                      snr_lo, snr_hi, permille, out=pcm, draws=noise_draws)
     feats, lengths = hip.features(pcm, num_samples, feature_type,
                                   feature_normalization, FLAGS.features_drop_every_second_frame,
                                   FLAGS.sampling_rate)
@@ -285,7 +322,7 @@ def _make_batch(items, device, staged=None, augment=None):
         hip.spec_augment(feats, lengths, augment.next_seed(), n_freq, freq_width, n_time,
                          time_width, permille)
     return Batch(feats, lengths, staged.texts, staged.labels, staged.seconds,
-                 staged.packed_labels, pcm, num_samples)
+                 staged.packed_labels, pcm, num_samples, noise_draws)
 
 
 def _example_stream(csv_path, shuffle, rng):
@@ -387,7 +424,9 @@ def input_fn_generator(target, device='cuda', rank=0, world_size=1, seed=None, p
 
     ``--spec_augment`` / ``--speed_perturb`` act on the two training targets only: 'dev' and
     'test' batches are the same with the flags on and off.  Buckets are formed on the source
-    lengths; an utterance slowed or sped up stays in its bucket.
+    lengths; an utterance slowed or sped up stays in its bucket.  ``--noise_csv`` mixes noise into
+    the training targets; 'dev' and 'test' get it only under ``--eval_noise_snr_db``, and then the
+    same noise at every call of ``input_fn``.
     """
     if target == 'train_bucket':
         csv_path, use_buckets = FLAGS.train_csv, True
@@ -405,10 +444,16 @@ def input_fn_generator(target, device='cuda', rank=0, world_size=1, seed=None, p
 
     def input_fn():
         assert os.path.exists(csv_path) and os.path.isfile(csv_path)
+        dev = torch.device(device)
+        if dev.index is None:
+            dev = torch.device('cuda', torch.cuda.current_device())
         augment = None
-        if training and (FLAGS.spec_augment or FLAGS.speed_perturb):
+        if training and (FLAGS.spec_augment or FLAGS.speed_perturb or FLAGS.noise_csv):
             # (seeded like the epoch where it has a seed; otherwise like its shuffle: fresh)
-            augment = _Augmenter(seed if seed is not None else random.getrandbits(63), rank)
+            augment = _Augmenter(seed if seed is not None else random.getrandbits(63), rank,
+                                 device=dev)
+        elif not training and FLAGS.eval_noise_snr_db:
+            augment = _Augmenter(EVAL_NOISE_SEED, rank, training=False, device=dev)
 
         def host_side():
             if augment is None or not augment.percents:
@@ -418,17 +463,12 @@ def input_fn_generator(target, device='cuda', rank=0, world_size=1, seed=None, p
 
         if prefetch <= 0:
             for items in host_side():
-                yield _make_batch(items, torch.device(device) if torch.device(device).index
-                                  is not None else torch.device('cuda', torch.cuda.current_device()),
-                                  augment=augment)
+                yield _make_batch(items, dev, augment=augment)
             return
         # WAV reading, label packing and the uploads run ahead on a host thread (the reference's
         # prefetch(64)): pinned staging buffers, asynchronous copies on an upload stream
         pending = queue.Queue(maxsize=prefetch)
         done = object()
-        dev = torch.device(device)
-        if dev.index is None:
-            dev = torch.device('cuda', torch.cuda.current_device())
         upload = torch.cuda.Stream(dev)
         # (queue + producer + consumer; kept across epochs: pinned allocations cost up to 80 ms)
         # (one iterator at a time per ring: an iterator that starts while another one's reader

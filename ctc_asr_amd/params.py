@@ -31,8 +31,14 @@ class FlagValues:
 
     def __init__(self):
         object.__setattr__(self, '_flags', {})
+        object.__setattr__(self, '_validators', [])
 
     # -- definition -------------------------------------------------------------------------
+    def define_validator(self, validator):
+        """``validator(flags)``: raises ValueError for a COMBINATION of values that is refused; run
+        after every `parse`, when all flags of the command line are known."""
+        self._validators.append(validator)
+
     def define(self, kind, name, default, help_text='', check=None):
         """``check(value)``: raises ValueError for a value the flag refuses - when the command line
         is parsed or the flag is assigned, not when it is first used."""
@@ -140,6 +146,8 @@ class FlagValues:
                     seen_multi.add(name)
             else:
                 flag.value = self._convert(flag, raw)
+        for validator in self._validators:
+            validator(self)
         return rest
 
 
@@ -333,6 +341,68 @@ FLAGS.define('string', 'speed_perturb', '',
              'utterance is resampled to one of them, drawn uniformly; empty: off.',
              parse_speed_perturb)
 
+# Additive noise on the device (no counterpart in the reference; off while --noise_csv is empty: a
+# batch then launches what it always did).  Training batches draw whether, which clip, where in it
+# and how many dB per row; 'dev' and 'test' batches mix only under --eval_noise_snr_db, every row at
+# that one value.  predict / align never mix.
+NOISE_SNR_DB_RANGE = (-20, 60)      # CTCASR_NOISE_MIX_MIN_SNR_DB, CTCASR_NOISE_MIX_MAX_SNR_DB
+
+
+def _snr_db(flag, part):
+    try:
+        value = int(part)
+    except ValueError:
+        raise ValueError('--{}: "{}" is not a whole number of dB.'.format(flag, part))
+    if not NOISE_SNR_DB_RANGE[0] <= value <= NOISE_SNR_DB_RANGE[1]:
+        raise ValueError('--{}: {} is outside {}..{} dB.'.format(flag, value, *NOISE_SNR_DB_RANGE))
+    return value
+
+
+def parse_noise_snr_db(text):
+    """'10,30' -> (10, 30); '15' -> (15, 15); ValueError for anything else."""
+    parts = str(text).replace(',', ' ').split()
+    if len(parts) not in (1, 2):
+        raise ValueError('--noise_snr_db: "{}" is neither "lo,hi" nor one value.'.format(text))
+    values = [_snr_db('noise_snr_db', part) for part in parts]
+    if values[0] > values[-1]:
+        raise ValueError('--noise_snr_db: {} is above {}.'.format(values[0], values[-1]))
+    return values[0], values[-1]
+
+
+def parse_eval_noise_snr_db(text):
+    """'' -> None (off); '10' -> 10; ValueError for anything else."""
+    parts = str(text).split()
+    if not parts:
+        return None
+    if len(parts) != 1:
+        raise ValueError('--eval_noise_snr_db: "{}" is not one value.'.format(text))
+    return _snr_db('eval_noise_snr_db', parts[0])
+
+
+def check_noise_flags(flags):
+    if parse_eval_noise_snr_db(flags.eval_noise_snr_db) is not None and not flags.noise_csv:
+        raise ValueError('--eval_noise_snr_db needs --noise_csv.')
+
+
+FLAGS.define('string', 'noise_csv', '',
+             'Manifest (path;label;length, labels ignored) of the noise recordings mixed into '
+             'training batches; empty: off.')
+FLAGS.define('string', 'noise_dir', '', 'Root of the noise WAVs; empty: corpus_dir.')
+FLAGS.define('string', 'noise_snr_db', '10,30',
+             'Speech-to-noise ratio of a mixed utterance in whole dB, "lo,hi" (drawn uniformly, '
+             'both ends included) or one value; -20..60.', parse_noise_snr_db)
+FLAGS.define('int', 'noise_permille', 500,
+             'Share of the training utterances that get noise, in thousandths (0..1000).',
+             _int_range('noise_permille', 0, 1000))
+FLAGS.define('int', 'noise_max_seconds', 3600,
+             'Noise kept in HBM: reading the manifest stops at this many seconds (at least 1).',
+             _int_range('noise_max_seconds', 1))
+FLAGS.define('string', 'eval_noise_snr_db', '',
+             "Mix noise into every utterance of 'dev' / 'test' batches at this many dB (-20..60), "
+             'the same draws at every evaluation; needs --noise_csv; empty: off.',
+             parse_eval_noise_snr_db)
+FLAGS.define_validator(check_noise_flags)
+
 # CTC decoder (asr/params.py:84-86).
 FLAGS.define('int', 'beam_width', 1024, 'Leaves kept by the CTC beam search (<= 1024).')
 
@@ -432,6 +502,11 @@ def get_parameters():
                         FLAGS.spec_augment, FLAGS.specaug_freq_masks, FLAGS.specaug_freq_width,
                         FLAGS.specaug_time_masks, FLAGS.specaug_time_width,
                         FLAGS.specaug_time_permille, FLAGS.speed_perturb or 'off'))
+    if FLAGS.noise_csv:
+        rows.append('\tNoise (noise_csv={}, snr_db={}, permille={}, max_seconds={:,d}, '
+                    'eval_snr_db={});'.format(
+                        FLAGS.noise_csv, FLAGS.noise_snr_db, FLAGS.noise_permille,
+                        FLAGS.noise_max_seconds, FLAGS.eval_noise_snr_db or 'off'))
     if FLAGS.lr_schedule != 'constant' or FLAGS.lr_warmup_steps > 0 or \
             FLAGS.grad_accum_steps > 1 or FLAGS.ema_decay > 0 or FLAGS.eval_ema:
         rows.append('\tSchedule (lr_schedule={}, minimum_lr={}, warmup_steps={:,d}, '

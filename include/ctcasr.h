@@ -655,7 +655,7 @@ int ctcasr_adam_step_clipped(float *param, const float *grad, float *m, float *v
                              float lr, float beta1, float beta2, float epsilon, int64_t step,
                              float grad_scale, const int32_t *skip, const float *grad_factor,
                              ctcasr_stream_t stream);
-/* ... and with the exponential moving average of the parameters (K16) in the same launch: param,
+/* ... and with the exponential moving average of the parameters in the same launch: param,
  * m and v come out as ctcasr_adam_step_clipped leaves them for the same arguments, bit for bit
  * (the same expressions in the same order), and
  *   ema[i] = ema[i] + ema_alpha * (param_new[i] - ema[i])        in fp32,
@@ -768,7 +768,7 @@ int ctcasr_features(const int16_t *pcm, const int32_t *num_samples, int B, int m
 /* ---- K15: augmentation of training batches ----------------------------------------------------
  * No counterpart in the reference (it does not augment).  Two kernels around ctcasr_features:
  * speed perturbation of the PCM before it, SpecAugment masks on the features after it.  Left out
- * on purpose: time warping, noise mixing, and any mask fill other than zero.
+ * on purpose: time warping and any mask fill other than zero.  (Additive noise: K16.)
  *
  * Counter generator (integers only, so that a host reference reproduces every draw):
  *   r24(seed, idx)      = the top 24 bits (z >> 40) of the splitmix64 finaliser over
@@ -834,6 +834,63 @@ int ctcasr_resample_num_samples(int num_samples, int percent);
 int ctcasr_speed_perturb(const int16_t *pcm, const int32_t *num_samples, const int32_t *percent,
                          int B, int max_in, int16_t *out, int max_out, int32_t *out_samples,
                          ctcasr_stream_t stream);
+
+/* ---- K16: additive noise at a drawn SNR -----------------------------------------------------
+ * No counterpart in the reference.  Mixes a run of a noise clip into every drawn row of a batch
+ * of PCM, before ctcasr_features (and after ctcasr_speed_perturb where that is on), scaled so
+ * that the row's speech-to-noise power ratio is the drawn number of dB.
+ *   pcm, out      int16 [B, max_samples]; out == pcm (in place) is allowed, any other overlap is not
+ *   num_samples   int32 [B]; n = num_samples[b]
+ *   bank          int16: all noise clips back to back
+ *   clip_offsets  DEVICE int64 [num_clips + 1], clip k = bank[clip_offsets[k] : clip_offsets[k + 1]]
+ *                 of length len_k.  Only 1 <= len_k <= 2^24 is served (below() then reaches every
+ *                 offset); a row that draws any other clip is copied.  The table is trusted to
+ *                 stay inside the bank.
+ * Draws of row b, all from the generator of K15:
+ *   hit = below(seed, 8 b, 1000) < prob_permille        k   = below(seed, 8 b + 1, num_clips)
+ *   o   = below(seed, 8 b + 2, len_k)                   snr = snr_lo_db + below(seed, 8 b + 3,
+ *                                                                   snr_hi_db - snr_lo_db + 1)
+ * Noise under sample i < n: v[i] = clip_k[(o + i) mod len_k] - a clip shorter than the row wraps
+ * as often as needed.
+ * Powers: Ps = sum of x[i]^2, Pn = sum of v[i]^2 over i < n, in 64-bit integers: exact (n <= 2^30,
+ * a square <= 2^30), so independent of grid shape and arrival order (integer atomics, one per
+ * workgroup and sum; no float atomics).
+ * Gain: g = f32(sqrt(Ps / Pn) * 10^(-snr / 20)) evaluated in fp64; pinned to within one fp32 ulp
+ * (relative 2^-23) of that value, NOT to a particular rounding of the device's fp64 sqrt / pow.
+ * Every workgroup of a row computes it from the same two sums, so it is one value per row.
+ * Mix: y[i] = clamp(rint(x[i] + g * v[i]), -32768, 32767) in fp32 by one fused multiply-add,
+ * rounded to nearest even.
+ * Everything that is not mixed is a bit copy (and is not stored at all when out == pcm): rows
+ * with hit false; rows whose n is outside [1, max_samples] (all max_samples columns);  rows with
+ * Ps == 0 or Pn == 0; rows whose clip has a length outside [1, 2^24]; in every row the columns at
+ * or beyond n.
+ * Optional outputs (each may be NULL):
+ *   draws   int32 [B, 4] = (status, k, o, snr).  status 1 = mixed; 0 = not drawn or a bad row, the
+ *           other three are then 0; 2 = drawn, but speech or noise is silent or the clip's length
+ *           is not served (o = 0 then): copied.
+ *   powers  int64 [B, 2] = (Ps, Pn); both 0 where status is 0 and where the clip is not served.
+ *   gain    fp32 [B]; 0 where the row is not mixed.
+ *   workspace  ctcasr_noise_mix_workspace_bytes(B) bytes, 8-byte aligned (the two sums per row).
+ * Two launches behind a memset of the workspace: the sums, then the mix.  A workgroup serves
+ * CTCASR_NOISE_MIX_CHUNK samples of one row, cut into groups of 8 by the address of the stored
+ * stream: whole groups below n whose noise does not cross the clip's end move as 16-byte
+ * accesses, all others sample by sample.
+ * Errors, before any launch: null pcm / num_samples / bank / clip_offsets / out, B < 1,
+ * max_samples < 1, num_clips < 1, snr_lo_db > snr_hi_db, either outside
+ * [CTCASR_NOISE_MIX_MIN_SNR_DB, CTCASR_NOISE_MIX_MAX_SNR_DB], prob_permille outside [0, 1000]:
+ * CTCASR_ERR_BAD_ARGUMENT; max_samples > 2^30 or num_clips > 2^24: CTCASR_ERR_UNSUPPORTED;
+ * workspace null, short or misaligned: CTCASR_ERR_WORKSPACE.
+ * prob_permille == 0 launches no kernel: a device-to-device copy when out != pcm, and the optional
+ * outputs are zeroed by memsets. */
+#define CTCASR_NOISE_MIX_CHUNK 8192
+#define CTCASR_NOISE_MIX_MIN_SNR_DB (-20)
+#define CTCASR_NOISE_MIX_MAX_SNR_DB 60
+size_t ctcasr_noise_mix_workspace_bytes(int B);
+int ctcasr_noise_mix(const int16_t *pcm, const int32_t *num_samples, int B, int max_samples,
+                     const int16_t *bank, const int64_t *clip_offsets, int num_clips,
+                     uint64_t seed, int snr_lo_db, int snr_hi_db, int prob_permille,
+                     int16_t *out, int32_t *draws, int64_t *powers, float *gain,
+                     void *workspace, size_t workspace_bytes, ctcasr_stream_t stream);
 
 #ifdef __cplusplus
 }
