@@ -48,6 +48,13 @@ __device__ __forceinline__ float relu_clip(float v, float cutoff) {
     const float c = fminf(fmaxf(v, 0.f), cutoff);
     return v != v ? v : c;
 }
+// clamp to [-bound, bound] that keeps a NaN (fmaxf(NaN, -bound) is -bound: a NaN input would
+// become a finite one, and the step guard would never see it); infinities saturate.  65504 is the
+// finite fp16 range; the GEMM operand packs take 60000, which leaves the second piece room.
+__device__ __forceinline__ float saturate_f16(float s, float bound = 65504.f) {
+    const float c = fminf(fmaxf(s, -bound), bound);
+    return s != s ? s : c;
+}
 // Gate non-linearities on the hardware transcendentals (v_exp_f32 / v_rcp_f32, ~1 ulp each) and
 // branch-free: the library expf / tanhf (range reduction, two divergent tanh paths, IEEE division)
 // cost ~250 VALU instructions per LSTM cell update inside every time step of the recurrence.

@@ -44,13 +44,6 @@ __device__ __forceinline__ unsigned f16_pieces(float s) {
            ((unsigned)__builtin_bit_cast(unsigned short, h2) << 16);
 }
 
-// clamp to the finite fp16 range that keeps a NaN (fmaxf(NaN, -65504) is -65504: a NaN input
-// would become a finite one, and the step guard would never see it)
-__device__ __forceinline__ float saturate_f16(float s) {
-    const float c = fminf(fmaxf(s, -65504.f), 65504.f);
-    return s != s ? s : c;
-}
-
 // scale that puts a magnitude with these bits into [2^14, 2^15) (1 for zero)
 __device__ __forceinline__ float scale_below_f16_max(unsigned max_bits) {
     const int e = (int)((max_bits >> 23) & 0xFF) - 127;

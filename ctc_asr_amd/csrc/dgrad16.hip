@@ -338,7 +338,7 @@ __global__ void __launch_bounds__(256) dgrad16_pack_kernel(const float *w, int64
     for (int e = 0; e < 8; ++e) {
         const int unit = 16 * P + 8 * m + 2 * q + (e >> 2), gate = e & 3;
         float v = n < N ? w[((int64_t)d * DG_GH + gate * DG_H + unit) * ldw + n] * scale : 0.f;
-        v = fminf(fmaxf(v, -60000.f), 60000.f);         // saturate, never inf
+        v = saturate_f16(v, 60000.f);                   // saturate, never inf; a NaN stays
         const _Float16 h1 = (_Float16)v;
         const _Float16 h2 = (_Float16)(v - (float)h1);
         pc[e] = (unsigned)__builtin_bit_cast(unsigned short, h1) |

@@ -19,6 +19,8 @@
 // 64 of W_hh's) - W_hh's 64 tiles alone leave half of the CUs beside a recurrence launch idle.
 #include "common.h"
 
+#include <atomic>
+
 namespace {
 
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
@@ -34,6 +36,7 @@ constexpr int WG_A_BYTES = (WG_TILE / 16) * 2 * 1024, WG_B_BYTES = WG_A_BYTES;
 constexpr int WG_STAGE_BYTES = WG_A_BYTES + WG_B_BYTES;
 constexpr size_t WG_LDS_BYTES = 2 * (size_t)WG_STAGE_BYTES;
 constexpr int WG_LOADERS = 4;
+constexpr int WG_PART_BITS = 12;                   // a turn word = launch number << 12 | part
 
 struct WgArgs {
     const char *a;          // packed dxw of the range: [stages][m_tiles][2][1 KB]
@@ -45,7 +48,9 @@ struct WgArgs {
     int m, n[2], stage0[2]; // first stage of the range inside b[k]
     int stages, m_tiles, n_tiles[2], tiles_n[2], tiles_m;
     int parts;              // row ranges one tile's sum is cut into (one workgroup each)
-    int *sync;              // [1 + tiles]: time-out word, then the part whose turn it is to add
+    int *sync;              // [1 + tiles]: time-out word, then per tile 0 (free) or the launch's
+                            // ticket | the part whose turn it is to add
+    int ticket;             // this launch's number << WG_PART_BITS, never 0
     long spin_limit;        // polls of a turn word before a part gives up
 };
 
@@ -193,10 +198,13 @@ __global__ void __launch_bounds__(WG_THREADS) wgrad16_kernel(WgArgs p) {
         }
         return;
     }
-    // The parts of a tile add in order (the same sums on every run): part q waits for the tile's
-    // word to read q - part 0 too: the word is 0 exactly when no launch is adding to this tile, so
-    // launches of two streams that share the words take turns instead of releasing each other's
-    // parts.  Part q - 1 has a lower workgroup id, was dispatched before and waits only on lower ids
+    // The parts of a tile add in order (the same sums on every run).  The tile's word is 0 exactly
+    // when no launch is adding to this tile: part 0 TAKES it (compare-and-swap 0 -> this launch's
+    // ticket; a plain "wait until it reads 0" let the parts 0 of two streams' launches pass
+    // together, after which the first to finish released the OTHER launch's part 1 beside its
+    // still adding part 0 - a lost update), part q > 0 waits for ticket | q, the last part hands
+    // the word back as 0: launches of two streams that share the words take turns at a tile.
+    // Part q - 1 has a lower workgroup id, was dispatched before and waits only on lower ids
     // itself.  dW and the word are read and written at agent scope access by access (sc1 loads /
     // write-through stores): another XCD's L2 never holds a stale or a dirty line of them, and no
     // workgroup has to write back or invalidate a whole L2 - which would cost every other
@@ -207,7 +215,16 @@ __global__ void __launch_bounds__(WG_THREADS) wgrad16_kernel(WgArgs p) {
     int *turn = p.sync + 1 + tile_id;
     if (tid == 0) {
         long spins = 0;
-        while (__hip_atomic_load(turn, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != part) {
+        const int mine = p.ticket | part;
+        for (;;) {
+            if (part == 0) {
+                int expected = 0;
+                if (__hip_atomic_compare_exchange_strong(turn, &expected, mine, __ATOMIC_RELAXED,
+                                                         __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
+                    break;
+            } else if (__hip_atomic_load(turn, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == mine) {
+                break;
+            }
             __builtin_amdgcn_s_sleep(8);
             if (++spins > p.spin_limit ||
                 ((spins & 255) == 0 &&
@@ -253,7 +270,7 @@ __global__ void __launch_bounds__(WG_THREADS) wgrad16_kernel(WgArgs p) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     if (tid == 0)
-        __hip_atomic_store(turn, part + 1 == p.parts ? 0 : part + 1, __ATOMIC_RELAXED,
+        __hip_atomic_store(turn, part + 1 == p.parts ? 0 : p.ticket | (part + 1), __ATOMIC_RELAXED,
                            __HIP_MEMORY_SCOPE_AGENT);
 }
 
@@ -274,7 +291,7 @@ __global__ void __launch_bounds__(256) wgrad16_pack_kernel(const float *x, int64
     for (int e = 0; e < 8; ++e) {
         const int64_t row = r + e;
         float v = (c < cols && row >= 0 && row < rows_total) ? x[row * ld + c] * cs : 0.f;
-        v = fminf(fmaxf(v, -60000.f), 60000.f);
+        v = saturate_f16(v, 60000.f);                   // infinities saturate, a NaN stays
         const _Float16 h1 = (_Float16)v;
         const _Float16 h2 = (_Float16)(v - (float)h1);
         pc[e] = (unsigned)__builtin_bit_cast(unsigned short, h1) |
@@ -322,7 +339,7 @@ extern "C" int ctcasr_wgrad16_gemm(const void *d_packed, int m, int stages, cons
                                    int parts, int32_t *sync, ctcasr_stream_t stream) {
     if (!d_packed || !inv_scale || !x_packed || !dw_x || m <= 0 || stages <= 0 || nx <= 0 ||
         ld_x < nx || x_stage0 < 0 || !(x_scale > 0.f) ||
-        parts < 1 || parts > stages || (parts > 1 && !sync) ||
+        parts < 1 || parts > stages || parts >= (1 << WG_PART_BITS) || (parts > 1 && !sync) ||
         (y_packed && (!dw_y || ny <= 0 || ld_y < ny || y_stage0 < 0 || !(y_scale > 0.f))))
         return CTCASR_ERR_BAD_ARGUMENT;
     static bool attr_set = false;
@@ -347,6 +364,9 @@ extern "C" int ctcasr_wgrad16_gemm(const void *d_packed, int m, int stages, cons
         a.n_tiles[1] = (ny + 15) / 16; a.tiles_n[1] = (ny + WG_TILE - 1) / WG_TILE;
     }
     a.parts = parts; a.sync = sync; a.spin_limit = g_wgrad_spin_limit;
+    // (launch numbers 1 .. 2^19 - 1, round and round: two launches in flight never share one)
+    static std::atomic<unsigned> launches{0};
+    a.ticket = (int)((launches.fetch_add(1) % ((1u << (31 - WG_PART_BITS)) - 1) + 1) << WG_PART_BITS);
     const int tiles = a.tiles_m * (a.tiles_n[0] + a.tiles_n[1]) * parts;
     wgrad16_kernel<<<tiles, WG_THREADS, WG_LDS_BYTES, (hipStream_t)stream>>>(a);
     return ctcasr_launch_status();

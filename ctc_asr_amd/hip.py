@@ -900,10 +900,19 @@ def wgrad16_pack(x, rows_total, row0, stages, scale, col_scale=None, out=None):
     if x.dim() != 2 or x.dtype != torch.float32 or not x.is_cuda or x.stride(1) != 1:
         raise CtcAsrError('wgrad16_pack: x must be an f32 matrix in HBM with unit column stride.')
     cols = x.shape[1]
+    if not 0 < int(rows_total) <= x.shape[0]:
+        raise CtcAsrError('wgrad16_pack: rows_total = {} but x holds {} rows.'
+                          .format(rows_total, x.shape[0]))
+    if col_scale is not None:
+        _expect_numel('wgrad16_pack', 'col_scale', col_scale, cols)
+        if col_scale.device != x.device:
+            raise CtcAsrError('wgrad16_pack: col_scale lives on {}, x on {}.'
+                              .format(col_scale.device, x.device))
     need = load().ctcasr_wgrad16_packed_bytes(int(stages), cols)
     if out is None:
         out = torch.empty(need, dtype=torch.uint8, device=x.device)
-    elif out.dtype != torch.uint8 or out.numel() < need or not out.is_contiguous():
+    elif out.dtype != torch.uint8 or out.numel() < need or not out.is_contiguous() or \
+            out.device != x.device:
         raise CtcAsrError('wgrad16_pack: out must be a contiguous uint8 buffer of {} bytes.'
                           .format(need))
     _check(load().ctcasr_wgrad16_pack(
@@ -919,9 +928,38 @@ def wgrad16_gemm(d_packed, m, stages, inv_scale, x_packed, x_stage0, x_scale, dw
     """dw_x [m, nx] += D^T X and (optional) dw_y [m, ny] += D^T Y over `stages` stages of 32 rows,
     from operands packed by `wgrad16_pack` (include/ctcasr.h: ctcasr_wgrad16_gemm).  `parts`
     workgroups per tile add in order through the device's zeroed sync words (one buffer per device:
-    launches of different streams / models that meet at a tile's word take turns - part 0 waits
-    for the word to read 0)."""
-    parts = max(1, min(int(parts), int(stages)))
+    launches of different streams / models that meet at a tile's word take turns - part 0 takes
+    the word by compare-and-swap from 0 to the launch's ticket, part q > 0 adds when it reads
+    ticket | q, the last part hands it back as 0; at most 4095 parts)."""
+    parts = max(1, min(int(parts), int(stages), 4095))
+    if (y_packed is None) != (dw_y is None):
+        raise CtcAsrError('wgrad16_gemm: y_packed and dw_y come together.')
+    for name, t in (('dw_x', dw_x), ('dw_y', dw_y)):
+        if t is not None and (t.dim() != 2 or t.dtype != torch.float32 or not t.is_cuda or
+                              t.stride(1) != 1 or t.shape[0] != m):
+            raise CtcAsrError('wgrad16_gemm: {} must be an f32 [m, n] view in HBM with unit '
+                              'column stride.'.format(name))
+    # the kernel reads whole stages by DMA: every packed operand has to hold what the launch
+    # will read of it, the second operands from stage 0 of their buffer on
+    for name, t, first, cols in (('d_packed', d_packed, 0, m),
+                                 ('x_packed', x_packed, x_stage0, dw_x.shape[1]),
+                                 ('y_packed', y_packed, y_stage0,
+                                  0 if dw_y is None else dw_y.shape[1])):
+        if t is None:
+            continue
+        if int(first) < 0:
+            raise CtcAsrError('wgrad16_gemm: the first stage of {} is negative.'.format(name))
+        need = load().ctcasr_wgrad16_packed_bytes(int(first) + int(stages), cols)
+        if t.dtype != torch.uint8 or not t.is_contiguous() or t.numel() < need:
+            raise CtcAsrError('wgrad16_gemm: {} must be a contiguous uint8 buffer of at least {} '
+                              'bytes (got {}).'.format(name, need, t.numel()))
+    if inv_scale is None or inv_scale.numel() < m:
+        raise CtcAsrError('wgrad16_gemm: inv_scale holds fewer than m = {} scales.'.format(m))
+    for name, t in (('d_packed', d_packed), ('x_packed', x_packed), ('inv_scale', inv_scale),
+                    ('y_packed', y_packed), ('dw_y', dw_y)):
+        if t is not None and t.device != dw_x.device:
+            raise CtcAsrError('wgrad16_gemm: {} lives on {}, dw_x on {}.'
+                              .format(name, t.device, dw_x.device))
     sync = None
     if parts > 1:
         need = load().ctcasr_wgrad16_sync_ints(int(m), dw_x.shape[1], 0 if dw_y is None else dw_y.shape[1])
@@ -929,11 +967,6 @@ def wgrad16_gemm(d_packed, m, stages, inv_scale, x_packed, x_stage0, x_scale, dw
         if sync is None or sync.numel() < need:
             sync = _WGRAD16_SYNC[dw_x.device.index] = torch.zeros(max(need, 4096), dtype=torch.int32,
                                                             device=dw_x.device)
-    for name, t in (('dw_x', dw_x), ('dw_y', dw_y)):
-        if t is not None and (t.dim() != 2 or t.dtype != torch.float32 or not t.is_cuda or
-                              t.stride(1) != 1 or t.shape[0] != m):
-            raise CtcAsrError('wgrad16_gemm: {} must be an f32 [m, n] view in HBM with unit '
-                              'column stride.'.format(name))
     _check(load().ctcasr_wgrad16_gemm(
         d_packed.data_ptr(), int(m), int(stages), _dev(inv_scale, name='inv_scale'),
         x_packed.data_ptr(), int(x_stage0), dw_x.shape[1], float(x_scale), dw_x.data_ptr(),
@@ -949,6 +982,13 @@ _WGRAD16_SYNC = {}
 def _wgrad16_sync_of(device):
     device = torch.device(device)
     return _WGRAD16_SYNC.get(torch.cuda.current_device() if device.index is None else device.index)
+
+
+def wgrad16_sync_words(device):
+    """The int32 sync words `wgrad16_gemm` launches on `device` share (word 0: the sticky
+    time-out word, then one turn word per tile; all zero between launches), or None while no
+    launch with parts > 1 has made them."""
+    return _wgrad16_sync_of(device)
 
 
 def wgrad16_gave_up_waiting(device):
@@ -1029,6 +1069,27 @@ def dgrad16_blockscaled(workspace, num_steps, batch, hidden, packed, scale, n, o
         raise CtcAsrError('dgrad16_blockscaled: out must be an f32 [T * B, n] view with unit '
                           'column stride.')
     t_lo, t_hi = (0, num_steps) if steps is None else steps
+    if not 0 <= int(t_lo) < int(t_hi) <= num_steps:
+        raise CtcAsrError('dgrad16_blockscaled: steps = ({}, {}) is no range inside [0, {}].'
+                          .format(t_lo, t_hi, num_steps))
+    if len(dirs) != 2 or not 0 <= int(dirs[0]) < int(dirs[1]) <= 2:
+        raise CtcAsrError('dgrad16_blockscaled: dirs = {} is no range inside [0, 2].'
+                          .format(tuple(dirs)))
+    if packed.device != workspace.device:
+        raise CtcAsrError('dgrad16_blockscaled: packed weights and workspace live on different '
+                          'devices.')
+    need = dgrad16_packed_bytes(n)
+    if packed.numel() * packed.element_size() < need or not packed.is_contiguous():
+        raise CtcAsrError('dgrad16_blockscaled: packed holds {} bytes, {} expected for n = {}.'
+                          .format(packed.numel() * packed.element_size(), need, n))
+    # what the recurrence publishes: the zero block and one block per step, then the inverse scales
+    x_off, s_off = dgrad16_published_offsets(num_steps, batch, hidden)
+    need = max(x_off + (num_steps + 1) * 2 * batch * 4 * hidden * 4,
+               s_off + num_steps * 2 * (hidden // 16) * 32 * 4)
+    if workspace.numel() * workspace.element_size() < need or not workspace.is_contiguous():
+        raise CtcAsrError('dgrad16_blockscaled: workspace holds {} bytes, the published operand '
+                          'of ({}, {}) ends at {}.'.format(
+                              workspace.numel() * workspace.element_size(), num_steps, batch, need))
     with _Timed('dgrad16'):
         _check(load().ctcasr_dgrad16_blockscaled(
             workspace.data_ptr(), int(num_steps), int(batch), int(hidden), packed.data_ptr(),

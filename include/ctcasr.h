@@ -569,8 +569,9 @@ int ctcasr_gemm_split_tn(const float *a, int64_t lda, const float *b, int64_t ld
  *               valid until the next persistent launch in that workspace
  *   packed      ctcasr_dgrad16_packed_bytes(n) bytes from ctcasr_dgrad16_pack_weights(W_ih [2 * 4H,
  *               n] with leading dimension ld_w, scale): fp16 pieces of W_ih * scale (saturating at
- *               +-60000: the caller keeps |w| * scale in range), K order and fragment order of the
- *               exchange buffer
+ *               +-60000: the caller keeps |w| * scale in range; infinities saturate too, a NaN
+ *               is KEPT in both pieces and makes its column of dx NaN), K order and fragment
+ *               order of the exchange buffer
  *   [t_lo, t_hi)    the time steps (rows t * B .. ) to produce;  [dir_lo, dir_hi) the directions
  *               whose gate columns enter the sum (0..2: both) - a finished direction / step range
  *               can be multiplied while the other is still running, the rest added later
@@ -598,7 +599,9 @@ int ctcasr_dgrad16_blockscaled(void *workspace, int T, int B, int hidden, const 
  * ctcasr_wgrad16_pack writes rows [row0, row0 + 32 * stages) of x [rows_total, cols] (leading
  * dimension ld_x; rows outside [0, rows_total) read as zeros - a negative / positive row0 shifts
  * an operand by time steps), each column times col_scale[c] (NULL: 1) times scale, saturating at
- * +-60000, into ctcasr_wgrad16_packed_bytes(stages, cols) bytes.  ctcasr_wgrad16_gemm multiplies
+ * +-60000 (infinities too; a NaN is KEPT in both pieces, so that it reaches dW and the gradient
+ * guard drops the step), into ctcasr_wgrad16_packed_bytes(stages, cols) bytes - every byte of
+ * them is written: columns up to the next multiple of 16 as zeros.  ctcasr_wgrad16_gemm multiplies
  * `stages` stages of the packed D (m columns, inverse column scales inv_scale[m]) into stages
  * [x_stage0, x_stage0 + stages) of the packed X (nx columns, fixed scale x_scale) and - optional -
  * of the packed Y, and ACCUMULATES into dW_x / dW_y (row-major, leading dimensions ld_*): two fp16
@@ -606,8 +609,12 @@ int ctcasr_dgrad16_blockscaled(void *workspace, int T, int B, int hidden, const 
  * outputs; `parts` >= 1 cuts every tile's row sum into that many workgroups (for launches whose
  * tiles alone do not fill the chip), which add to dW in part order through the words of `sync`
  * (ctcasr_wgrad16_sync_ints(m, nx, ny) int32, ZERO before the first launch that uses them; every
- * launch leaves them zero).  Part q adds when the tile's word reads q - part 0 too, so launches
- * of different streams that share the words take turns at a tile.  ABI v7: a part that gives up
+ * launch leaves them zero; parts < 4096).  A tile's word is 0 while no launch adds to the tile:
+ * part 0 takes it by compare-and-swap, part q > 0 adds when it reads this launch's number << 12 | q,
+ * the last part hands it back as 0, so launches of different streams that share the words take
+ * turns at a tile.  The launch number is drawn when ctcasr_wgrad16_gemm is CALLED: two launches
+ * that carry the same number must not be in flight together - a call with parts > 1 captured
+ * into a graph may be replayed one after the other, not on two streams at once.  ABI v7: a part that gives up
  * waiting (bounded; ctcasr_set_option("wgrad16_spin_limit", polls) shortens the bound for tests)
  * sets word 0 and leaves WITHOUT adding and without passing the turn on; while word 0 is set
  * every launch on these words returns at once.  The caller folds word 0 into the optimizer's skip

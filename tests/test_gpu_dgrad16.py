@@ -9,6 +9,8 @@ import numpy as np
 import pytest
 import torch
 
+from tests.gemm_reference import publish
+
 pytestmark = pytest.mark.gpu
 DEV = 'cuda'
 H = 1024
@@ -21,38 +23,6 @@ def hip():
     from ctc_asr_amd import hip as hip_mod
     hip_mod.load()
     return hip_mod
-
-
-def publish(hip, dxw, workspace=None):
-    """Write dxw [T, B, 2, 4H] into a recurrence workspace the way prnn_bwd16_kernel publishes its
-    dgates (rnn_persistent.hip): per (step, dir, producer = 16 units x 4 gates) and row the power
-    of two that puts the row's largest of the 64 values into [2^13, 2^14), two fp16 pieces,
-    [step][dir][P][half m][piece][k group q][b][e = 4 (unit & 1) + gate]; inverse scales
-    [step][dir][P][32 rows].  Step s = time s (dir 0) / T - 1 - s (dir 1)."""
-    steps, batch = dxw.shape[:2]
-    if workspace is None:
-        workspace = hip.rnn_workspace('lstm', steps, batch, H, dxw.device)
-    x_off, s_off = hip.dgrad16_published_offsets(steps, batch, H)
-    # (t, b, dir, gate, P, m, q, u1): unit = 16 P + 8 m + 2 q + u1
-    d = dxw.view(steps, batch, 2, 4, 64, 2, 4, 2)
-    top = d.abs().amax(dim=(3, 5, 6, 7))                          # (t, b, dir, P)
-    expo = (torch.frexp(top)[1] - 1).float()                     # floor(log2(top)), exactly
-    expo = torch.where(top > 0, (13 - expo).clamp(-100, 100), torch.zeros_like(expo))
-    scale = torch.exp2(expo)
-    scaled = d * scale.view(steps, batch, 2, 1, 64, 1, 1, 1)
-    h1 = scaled.half()
-    h2 = (scaled - h1.float()).half()
-    pieces = torch.stack([h1, h2], dim=0)                         # (piece, t, b, dir, gate, P, m, q, u1)
-    # -> (t, dir, P, m, piece, q, b, u1, gate)
-    pieces = pieces.permute(1, 3, 5, 6, 0, 7, 2, 8, 4).contiguous()
-    pieces[:, 1] = pieces[:, 1].flip(0)                           # dir 1: step s = T - 1 - t
-    block = 2 * batch * 4 * H * 4                                 # bytes per step
-    workspace[x_off + block:x_off + block * (steps + 1)] = pieces.view(torch.uint8).view(-1)
-    inv = torch.zeros(steps, 2, 64, 32, device=dxw.device)
-    inv[..., :batch] = (1.0 / scale).permute(0, 2, 3, 1)
-    inv[:, 1] = inv[:, 1].flip(0)
-    workspace[s_off:s_off + inv.numel() * 4] = inv.view(torch.uint8).view(-1)
-    return workspace
 
 
 def rel_errors(got, ref):
