@@ -48,6 +48,12 @@ __device__ __forceinline__ float relu_clip(float v, float cutoff) {
     const float c = fminf(fmaxf(v, 0.f), cutoff);
     return v != v ? v : c;
 }
+// max(v, 0) that keeps a NaN, for the ReLU recurrence cell: fmaxf(NaN, 0) is 0, and a NaN
+// pre-activation would become h = 0 (finite layers above, a finite loss, the step applied).
+// (-inf -> 0, +inf -> +inf; finite input: fmaxf's result bit for bit.)
+__device__ __forceinline__ float relu_keep_nan(float v) {
+    return v != v ? v : fmaxf(v, 0.f);
+}
 // clamp to [-bound, bound] that keeps a NaN (fmaxf(NaN, -bound) is -bound: a NaN input would
 // become a finite one, and the step guard would never see it); infinities saturate.  65504 is the
 // finite fp16 range; the GEMM operand packs take 60000, which leaves the second piece room.

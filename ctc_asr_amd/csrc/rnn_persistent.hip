@@ -110,7 +110,9 @@ struct PArgs {
     float *carry;          // backward, LSTM: dc [2, B, H] handed from one launch to the next
     float *rs;             // backward, reduce-scatter form: the exchange ring (prnn_rs_ring_bytes);
                            // fp16 form: the inverse scales (prnn_b16_scale_bytes)
-    unsigned *colmax;      // backward, fp16 form (optional): [2][G * H] maxima of |dxw| (bit patterns)
+    unsigned *colmax;      // backward, fp16 form (optional): [2][G * H] maxima of |dxw| (bit patterns);
+                           // reduced with fmaxf, which skips a NaN: max over nan_to_num(|dxw|, 0),
+                           // what colmax_kernel (split.hip) finds in a pass over dxw (inf stays inf)
     int prof;              // record phase timings of workgroup 0
     unsigned ticket;       // != 0: post it once every workgroup of this launch is running
     int xcd_split;         // fp16 kernels: direction 0 on XCDs 0 - 3, direction 1 on XCDs 4 - 7
@@ -676,7 +678,7 @@ __global__ void __launch_bounds__(PRNN_THREADS * CHAINS) prnn_fwd_kernel(PArgs p
                     rsv[it][0] = gr_; rsv[it][1] = gz; rsv[it][2] = gn; rsv[it][3] = q;
                 } else {
                     const float pre = xw[it][0] + rec[0];
-                    hv[it] = CELL == CTCASR_CELL_RNN_RELU ? fmaxf(pre, 0.f) : tanhf_(pre);
+                    hv[it] = CELL == CTCASR_CELL_RNN_RELU ? relu_keep_nan(pre) : tanhf_(pre);
                 }
             }
             // publish h: lanes of 4 consecutive units gather into one 16-byte sc1 store
@@ -1841,6 +1843,16 @@ __host__ __device__ inline size_t prnn_b16_scale_bytes(int T) {
 
 // MT batch tiles of 16 rows behind one barrier, NW waves (the K axis - 64 producers - is split
 // over them), a ring of D producers' A granules in flight per wave.
+// Range of the gradients (this kernel, prnn_bwd16s / 16k / 16w and prnn_relu16_kernel alike): the
+// scale of a (producer, row) is the power of two 2^(13 - exponent of its maximum), clamped to +-100
+// binades, 1 for an all-zero row - so a maximum between roughly 2^-100 and 2^100 is published with
+// fp32-grade pieces, and dxw(2^k dy) = 2^k dxw(dy) bit for bit while every maximum stays inside.
+// Below it the second fp16 piece goes subnormal (precision falls off, nothing breaks); above 2^115
+// the first piece overflows to inf.  The maximum is reduced with fmaxf, which skips a NaN: a NaN
+// keeps the scale of its finite neighbours, stays NaN in both pieces, and the consumer's MFMA
+// spreads it over that batch row only (rows are the M axis; scales, pieces and sums are per row).
+// An inf makes the scale 2^-100: its pieces are inf and NaN, the row's other values of that
+// producer vanish - the row turns non-finite, no other row is touched.
 //   MT = 1, NW = 4: 512 registers per wave, D = 10 (40 KB per wave in flight)
 //   MT = 2, NW = 8: two waves per SIMD hide each other's LDS / VALU latencies, nothing is held
 //                   twice (a wave's 8 producers: 16 B-fragment slots in LDS, 16 in 64 registers),
@@ -3981,7 +3993,7 @@ __global__ void __launch_bounds__(PRNN_THREADS) prnn_relu16_kernel(PArgs p) {
                 acc += red[((w * 2 + (iu >> 4)) * 16 + brow[it]) * 17 + (iu & 15)];
             float val;                               // what the next step multiplies
             if constexpr (BWD) val = in1[it] > 0.f ? acc : 0.f;
-            else val = fmaxf(acc, 0.f);
+            else val = relu_keep_nan(acc);
             if (!has) val = 0.f;
             // the row's scale over this workgroup's 32 values (two DPP rows of 16 lanes)
             float mx = row16_max(fabsf(val));

@@ -166,7 +166,7 @@ __global__ void __launch_bounds__(RNN_THREADS) rnn_fwd_step_kernel(StepArgs p) {
             rs[0] = gr_; rs[H] = gz; rs[2 * H] = gn; rs[3 * H] = q;
         } else {
             float pre = xv[0] + rec[0];
-            h = CELL == CTCASR_CELL_RNN_RELU ? fmaxf(pre, 0.f) : tanhf_(pre);
+            h = CELL == CTCASR_CELL_RNN_RELU ? relu_keep_nan(pre) : tanhf_(pre);
         }
         hnext[hoff] = h;
         p.y[((size_t)t * B + b) * 2 * H + dir * H + unit] = h;

@@ -605,7 +605,9 @@ def rnn_bwd(cell, dy, y, w_hh_t, reserve, seq_len=None, b_hh_n=None, dxw=None, d
     """dy,y f32[T,B,2H], w_hh_t f32[2,H,G*H] -> dxw f32[T,B,2,G*H].
 
     ``colmax`` (optional; only where `rnn_bwd_f16_supported`): int32[2*G*H] zeroed by the caller,
-    raised to the bit patterns of the largest |dxw| per column over the steps of the call.
+    raised to the bit patterns of the largest |dxw| per column over the steps of the call - a
+    NaN is skipped (fmaxf), an inf kept: ``nan_to_num(|dxw|, nan=0).amax`` over rows and steps, what
+    `colmax_scale`'s own pass over dxw finds.
 
     ``steps=(begin, end)`` runs that range of recurrence steps only (`ctcasr_rnn_bwd_steps`): cut
     a pass into calls covering T..0 in descending order, passing the same ``dxw`` and

@@ -72,8 +72,11 @@ def recurrence(cell, xw, w_hh, b_hh_n=None, seq_len=None, xw_bias=None, rec_bias
             rec = h @ w[d].t()
             if rb[d] is not None:
                 rec = rec + rb[d]
-            h_new, c_new = _cell(cell, xd[s], rec, h, c, b_n[d], hidden)
             m = active[s].view(-1, 1)
+            # (a frame past its row's length is never read: garbage there, a NaN included, reaches
+            # neither y nor - as 0 * NaN through the masked-out branch - any gradient)
+            h_new, c_new = _cell(cell, torch.where(m, xd[s], torch.zeros_like(xd[s])), rec, h, c,
+                                 b_n[d], hidden)
             outs.append(torch.where(m, h_new, torch.zeros_like(h_new)))
             h = torch.where(m, h_new, h)
             c = torch.where(m, c_new, c)
@@ -107,7 +110,9 @@ def relu_backward(y, dy, w_hh, seq_len=None):
     """dxw f64[T, B, 2, H] of the ReLU recurrence with the mask y > 0 taken from a GIVEN y: the
     backward kernels read the mask off the y they are handed, and where a pre-activation is
     ~1e-7 the float64 forward pass may have the other sign (an O(1) change of that entry's
-    gradient).  dpre = (dy + dpre_next W) * (y > 0), walked against each direction's order."""
+    gradient).  dpre = y > 0 ? dy + dpre_next W : 0, walked against each direction's order - a
+    select as in the kernels (and TensorFlow's ReluGrad), not a product with the mask: a NaN
+    gradient where y <= 0 (or y is NaN) gives 0, never NaN * 0."""
     num_steps, batch, _ = y.shape
     hidden = w_hh.shape[2]
     dev = y.device
@@ -121,8 +126,8 @@ def relu_backward(y, dy, w_hh, seq_len=None):
         carry = torch.zeros(batch, hidden, dtype=torch.float64, device=dev)
         # (the backward direction's step after time t is time t - 1 of the same row)
         for t in (range(num_steps - 1, -1, -1) if d == 0 else range(num_steps)):
-            live = ((y64[t, :, d] > 0) & (t < steps).view(-1, 1)).double()
-            dpre = (dy64[t, :, d] + carry) * live
+            live = (y64[t, :, d] > 0) & (t < steps).view(-1, 1)
+            dpre = torch.where(live, dy64[t, :, d] + carry, torch.zeros_like(carry))
             dxw[d][t] = dpre
             carry = dpre @ w64
     return torch.stack([torch.stack([dxw[0][t], dxw[1][t]], dim=1) for t in range(num_steps)])
@@ -142,3 +147,38 @@ def forward_backward(cell, xw, w_hh, dy, b_hh_n=None, seq_len=None, xw_bias=None
     if cell == 'gru':
         dbias = torch.cat([dbias, rec_bias.grad])
     return y.detach(), x.grad, dbias
+
+
+def _row_steps(num_steps, batch, seq_len):
+    return [num_steps] * batch if seq_len is None else [int(n) for n in seq_len]
+
+
+def nan_mask_forward(num_steps, batch, hidden, t0, row, d, unit, seq_len=None):
+    """Closed form of isnan(y) bool[T, B, 2, H] after ONE NaN in xw[t0, row, d, a gate column of
+    ``unit``]: that unit at t0, then every unit of (row, d) at the frames the direction visits
+    after t0 inside the row's length (d = 0: later frames, d = 1: earlier ones); nothing when t0
+    is past the row's length, nothing in any other row or direction."""
+    mask = torch.zeros(num_steps, batch, 2, hidden, dtype=torch.bool)
+    steps = _row_steps(num_steps, batch, seq_len)[row]
+    if t0 < steps:
+        mask[t0, row, d, unit] = True
+        later = range(t0 + 1, steps) if d == 0 else range(0, t0)
+        for t in later:
+            mask[t, row, d] = True
+    return mask
+
+
+def nan_mask_backward(num_steps, batch, hidden, gates, t0, row, d, unit, seq_len=None):
+    """Closed form of isnan(dxw) bool[T, B, 2, G*H] after ONE NaN in dy[t0, row, d * H + unit] for
+    the LSTM, GRU and tanh cells (whose derivatives multiply the incoming gradient; the ReLU
+    cell's selects on y > 0: `relu_backward`): all G gate columns of the unit at t0, then every
+    column of (row, d) at the frames the backward walk visits after t0 (d = 0: earlier frames,
+    d = 1: later ones inside the row's length)."""
+    mask = torch.zeros(num_steps, batch, 2, gates * hidden, dtype=torch.bool)
+    steps = _row_steps(num_steps, batch, seq_len)[row]
+    if t0 < steps:
+        mask[t0, row, d, unit::hidden] = True
+        later = range(0, t0) if d == 0 else range(t0 + 1, steps)
+        for t in later:
+            mask[t, row, d] = True
+    return mask

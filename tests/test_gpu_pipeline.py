@@ -221,18 +221,22 @@ def test_deferred_checks_still_raise_where_tensorflow_raises():
             torch.cuda.synchronize()
 
 
-def test_a_nan_loss_raises_what_the_reference_raises():
+@pytest.mark.parametrize('rnn_cell,units', [('lstm', 64), ('gru', 64), ('rnn_relu', 64),
+                                            ('rnn_tanh', 64), ('rnn_relu', 2048)])
+def test_a_nan_loss_raises_what_the_reference_raises(rnn_cell, units):
     """A non-finite loss stops training with `NanLossDuringTrainingError` - the reference's
     NanTensorHook (asr/model.py:368) - from the Trainer's deferred checks as well (the
     guard word used to surface as a bare FloatingPointError before `train_epoch`'s own test of the
-    loss could run); the step's update is dropped on the device."""
+    loss could run); the step's update is dropped on the device.  Every cell: the NaN has to
+    come through the recurrence (the ReLU cell's max(pre, 0) once turned it into h = 0 and the
+    step was applied); 2048 units put the ReLU cell on the persistent kernels."""
     from ctc_asr_amd import train
     from ctc_asr_amd.engine import NanLossDuringTrainingError, Trainer
     from ctc_asr_amd.model import ModelConfig
     assert train.NanLossDuringTrainingError is NanLossDuringTrainingError
     assert issubclass(NanLossDuringTrainingError, RuntimeError)
     cfg = ModelConfig(used_model='ds2', conv_filters=(4, 4), num_units_dense=32, num_layers_rnn=1,
-                      num_units_rnn=64, rnn_cell='lstm', cudnn=True, dense_dropout_rate=0.0)
+                      num_units_rnn=units, rnn_cell=rnn_cell, cudnn=True, dense_dropout_rate=0.0)
     trainer = Trainer(cfg, device='cuda', seed=3)
     rng = np.random.default_rng(5)
     feats = torch.tensor(rng.normal(size=(2, 21, 80)).astype(np.float32))
@@ -257,6 +261,34 @@ def test_a_nan_loss_raises_what_the_reference_raises():
     trainer.drain_checks()
     assert trainer.model.step_count == 2
     assert torch.isfinite(trainer.model.arena.param).all()
+
+
+@pytest.mark.parametrize('rnn_cell,units', [('lstm', 64), ('gru', 64), ('rnn_relu', 64),
+                                            ('rnn_tanh', 64), ('rnn_relu', 2048)])
+def test_a_nan_reaches_the_loss_through_the_network(rnn_cell, units):
+    """`inference_fn` marks an utterance whose FEATURES are not finite at the door, and `loss_fn`
+    adds the mark to that utterance's loss - which is all the test above sees.  A NaN that arises
+    inside the network has no door: with the mark cleared, the NaN of one feature must reach its
+    utterance's loss by itself, through the convolutions, the clipped ReLUs, the recurrence and
+    the CTC kernel - and the other utterance's loss stays finite (rows are independent)."""
+    from ctc_asr_amd import hip
+    from ctc_asr_amd.model import CTCModel, ModelConfig
+    cfg = ModelConfig(used_model='ds2', conv_filters=(4, 4), num_units_dense=32, num_layers_rnn=1,
+                      num_units_rnn=units, rnn_cell=rnn_cell, cudnn=True, dense_dropout_rate=0.0)
+    model = CTCModel(cfg, 'cuda', seed=3)
+    rng = np.random.default_rng(5)
+    feats = torch.tensor(rng.normal(size=(2, 21, 80)).astype(np.float32))
+    feats[1, 7, 3] = float('nan')
+    flen = torch.tensor([21, 21], dtype=torch.int32)
+    logits, seq_len = model.inference_fn(feats, flen, True)
+    if units == 2048:
+        assert hip.rnn_persistent_supported(rnn_cell, logits.shape[0], 2, units)
+    assert torch.isnan(model._acts['input_poison']).tolist() == [False, True]
+    model._acts['input_poison'].zero_()
+    model.loss_fn(logits, seq_len, [[1, 2, 3], [4, 5]], check=False)
+    torch.cuda.synchronize()
+    model.check_rnn_error()
+    assert torch.isnan(model.last_per_utterance_loss).tolist() == [False, True]
 
 
 def test_step_guard_words():

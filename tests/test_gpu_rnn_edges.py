@@ -150,14 +150,10 @@ def _row_err(got, ref):
     return float((err / ref.abs().amax(dim=(0, 2, 3)).clamp_min(1e-30)).max())
 
 
-def _check_pass(h, cell, hidden, c, variant, fwd_flags, bwd_flags, forms, got):
-    """y, dxw, dbias and the column maxima of one pass against the float64 reference, to the bars
-    of the existing test of each kernel family."""
-    y, dxw, dbias, colmax, reserve, ws = got
+def _check_y(h, cell, hidden, c, fwd_flags, forms, y, what):
     num_steps, batch = y.shape[:2]
     ragged = c['sl'] is not None
     ref_y = c['ref_y']
-    what = (cell, hidden, variant, num_steps, batch, ragged)
     # forward: fp32 kernels 2e-5 (test_rnn_fwd_bwd); fp16 pipe within 2e-5 and 3x the fp32
     # kernel's error + 2e-6 (test_rnn_fwd_on_the_fp16_matrix_pipe; ReLU: + 1e-6 x the scale of y,
     # test_relu_recurrence_on_the_fp16_matrix_pipe)
@@ -174,6 +170,18 @@ def _check_pass(h, cell, hidden, c, variant, fwd_flags, bwd_flags, forms, got):
             assert err < 2e-5 and err < 3 * err32 + 2e-6, (what, err, err32)
     else:
         assert err < 2e-5 * scale_y, (what, err)
+
+
+def _check_pass(h, cell, hidden, c, variant, fwd_flags, bwd_flags, forms, got, check_y=True):
+    """y, dxw, dbias and the column maxima of one pass against the float64 reference, to the bars
+    of the existing test of each kernel family.  ``check_y=False`` leaves y out (a pass whose y is
+    judged elsewhere: the backward bars alone, the ReLU cell's against the y it was handed)."""
+    y, dxw, dbias, colmax, reserve, ws = got
+    num_steps, batch = y.shape[:2]
+    ragged = c['sl'] is not None
+    what = (cell, hidden, variant, num_steps, batch, ragged)
+    if check_y:
+        _check_y(h, cell, hidden, c, fwd_flags, forms, y, what)
     # backward: the ReLU cell differentiates through the mask y > 0 of the y it is handed
     ref = c['ref_dxw'] if cell != 'rnn_relu' else \
         rnn_reference.relu_backward(y, c['dy'], c['w'], c['sl'])
