@@ -28,6 +28,10 @@ GRAD_NORM_MAX_SEGMENTS = 64
 SPEC_AUGMENT_MAX_MASKS = 16     # ctcasr_spec_augment: frequency masks, and time masks, per call
 NOISE_MIX_CHUNK = 8192          # ctcasr_noise_mix: samples of a row per workgroup
 NOISE_MIX_SNR_DB = (-20, 60)    # ... and the SNR range it takes
+REVERB_CHUNK = 2048             # ctcasr_reverb: output samples of a row per workgroup,
+REVERB_TAP_BLOCK = 32           # ... taps per round of its inner loop (a remainder 8 at a time),
+REVERB_TAP_ALIGN = 8            # ... what a response's length and offset are multiples of,
+REVERB_MAX_TAPS = 8192          # ... and the longest response it serves
 CELL_IDS = {'rnn_relu': 0, 'rnn_tanh': 1, 'lstm': 2, 'gru': 3}
 CELL_GATES = {'rnn_relu': 1, 'rnn_tanh': 1, 'lstm': 4, 'gru': 3}
 
@@ -145,6 +149,8 @@ SIGNATURES = {
     'ctcasr_noise_mix_workspace_bytes': (_c_sz, [_c_int]),
     'ctcasr_noise_mix': (_c_int, [_c_p, _c_p, _c_int, _c_int, _c_p, _c_p, _c_int, _c_u64] +
                          [_c_int] * 3 + [_c_p] * 5 + [_c_sz, _c_p]),
+    'ctcasr_reverb': (_c_int, [_c_p, _c_p, _c_int, _c_int] + [_c_p] * 4 + [_c_int, _c_u64, _c_int] +
+                      [_c_p] * 3),
     'ctcasr_adam_step': (_c_int, [_c_p] * 4 + [_c_i64] + [_c_f] * 4 + [_c_i64, _c_f, _c_p, _c_p]),
     'ctcasr_adam_step_clipped': (_c_int, [_c_p] * 4 + [_c_i64] + [_c_f] * 4 +
                                  [_c_i64, _c_f, _c_p, _c_p, _c_p]),
@@ -1777,4 +1783,56 @@ def noise_mix(pcm, num_samples, bank, clip_offsets, seed, snr_lo_db, snr_hi_db,
         int(seed) & 0xFFFFFFFFFFFFFFFF, int(snr_lo_db), int(snr_hi_db), int(prob_permille),
         out_ptr, draws_ptr, powers_ptr, gain_ptr, _dev(workspace, torch.uint8, 'workspace'),
         workspace.numel(), _stream()), 'noise_mix')
+    return out
+
+
+@_on_tensor_device
+def reverb(pcm, num_samples, taps, rir_offsets, rir_delay, rir_scale, seed, prob_permille=1000,
+           out=None, draws=None):
+    """Convolve the rows of ``pcm`` int16[B, N] (``num_samples`` int32[B]) with a drawn room
+    impulse response.  ``taps`` int16[*]: the responses back to back; ``rir_offsets`` int64[R + 1]:
+    where each starts, the last entry the bank's length; ``rir_delay`` int32[R]: the tap of the
+    direct path; ``rir_scale`` float32[R] (all device tensors; `reverb.RirBank` holds such a
+    bank).  Row b is reverberated with probability ``prob_permille`` / 1000 by a response drawn
+    from (``seed``, row) - integer functions and exact integer sums pinned in include/ctcasr.h;
+    rows that are not, and the columns behind a row's length, are bit copies.  ``out``:
+    int16[B, N], never ``pcm`` itself; a new tensor when None.  ``draws``: optional int32[B, 2]
+    (status, response).  Returns ``out``."""
+    if pcm.dim() != 2:
+        raise CtcAsrError('reverb: pcm must be [B, N] (got {} dimensions).'.format(pcm.dim()))
+    batch, max_samples = pcm.shape
+    _batch_of('reverb', 'num_samples', num_samples, batch)
+    if rir_offsets.numel() < 2:
+        raise CtcAsrError('reverb: rir_offsets holds {} offsets, at least 2 needed.'
+                          .format(rir_offsets.numel()))
+    num_rirs = rir_offsets.numel() - 1
+    if taps.numel() < 1:
+        raise CtcAsrError('reverb: the bank of impulse responses is empty.')
+    if out is None:
+        out = torch.empty_like(pcm)
+    _expect_numel('reverb', 'rir_delay', rir_delay, num_rirs)
+    _expect_numel('reverb', 'rir_scale', rir_scale, num_rirs)
+    _expect_numel('reverb', 'out', out, batch * max_samples)
+    _expect_numel('reverb', 'draws', draws, batch * 2)
+    pcm_ptr = _dev(pcm, torch.int16, 'pcm')
+    num_ptr = _dev(num_samples, torch.int32, 'num_samples')
+    taps_ptr = _dev(taps, torch.int16, 'taps')
+    off_ptr = _dev(rir_offsets, torch.int64, 'rir_offsets')
+    delay_ptr = _dev(rir_delay, torch.int32, 'rir_delay')
+    scale_ptr = _dev(rir_scale, torch.float32, 'rir_scale')
+    out_ptr = _dev(out, torch.int16, 'out')
+    draws_ptr = _dev(draws, torch.int32, 'draws')
+    for name, tensor in (('num_samples', num_samples), ('taps', taps),
+                         ('rir_offsets', rir_offsets), ('rir_delay', rir_delay),
+                         ('rir_scale', rir_scale), ('out', out), ('draws', draws)):
+        if tensor is not None and tensor.device != pcm.device:
+            raise CtcAsrError('reverb: {} lives on {}, pcm on {}.'
+                              .format(name, tensor.device, pcm.device))
+    if out_ptr == pcm_ptr:
+        raise CtcAsrError('reverb: out is pcm; the kernel reads the neighbours of a sample, so '
+                          'it cannot work in place.')
+    _check(load().ctcasr_reverb(
+        pcm_ptr, num_ptr, batch, max_samples, taps_ptr, off_ptr, delay_ptr, scale_ptr, num_rirs,
+        int(seed) & 0xFFFFFFFFFFFFFFFF, int(prob_permille), out_ptr, draws_ptr, _stream()),
+        'reverb')
     return out

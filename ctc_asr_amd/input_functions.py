@@ -228,10 +228,13 @@ class Batch:
     speed perturbation and with the noise mixed in where those are on, while ``audio_seconds``
     stays the duration of the source audio.  ``noise_draws``: int32[B, 4] device tensor, (status,
     clip, offset, snr) of every row as `hip.noise_mix` reports them, or None for a batch that
-    went through no noise mixing."""
+    went through no noise mixing.  ``reverb_draws``: int32[B, 2] device tensor, (status, impulse
+    response) of every row as `hip.reverb` reports them, or None for a batch that went through
+    no reverberation (which, where it is on, comes before the noise)."""
 
     def __init__(self, spectrogram, spectrogram_length, label_plaintext, labels, seconds,
-                 packed_labels=None, pcm=None, num_samples=None, noise_draws=None):
+                 packed_labels=None, pcm=None, num_samples=None, noise_draws=None,
+                 reverb_draws=None):
         self.features = {'spectrogram': spectrogram, 'spectrogram_length': spectrogram_length,
                          'label_plaintext': label_plaintext}
         self.labels = labels
@@ -239,6 +242,7 @@ class Batch:
         self.packed_labels = packed_labels if packed_labels is not None else labels
         self.pcm, self.num_samples = pcm, num_samples
         self.noise_draws = noise_draws
+        self.reverb_draws = reverb_draws
 
     def __iter__(self):      # (features, labels) = batch
         return iter((self.features, self.labels))
@@ -252,10 +256,12 @@ class _Augmenter:
     SpecAugment seeds: a 64-bit sequence stepped like `CTCModel._next_seed`, one value per
     batch, so that two iterators with one seed mask alike (and two ranks of one epoch do not).
     The noise has a sequence of its own, from another constant and stepped once per batch as
-    well: switching the noise on moves no mask and no speed.
+    well: switching the noise on moves no mask and no speed.  The reverberation has a third one,
+    by the same rule: it moves no mask, no speed and no noise draw.
 
-    ``training=False``: the iterator of 'dev' / 'test' - no speeds, no masks, and noise only under
-    --eval_noise_snr_db: every row, at that value, from seeds that do not depend on the epoch."""
+    ``training=False``: the iterator of 'dev' / 'test' - no speeds, no masks, no reverberation,
+    and noise only under --eval_noise_snr_db: every row, at that value, from seeds that do not
+    depend on the epoch."""
 
     def __init__(self, seed, rank=0, training=True, device='cuda'):
         self.percents = parse_speed_perturb(FLAGS.speed_perturb) if training else []
@@ -266,6 +272,12 @@ class _Augmenter:
             & 0xFFFFFFFFFFFFFFFF
         self.noise_seed = (int(seed) * 0x9E3779B1 + int(rank) * 0x85EBCA6B + 0x4E01) \
             & 0xFFFFFFFFFFFFFFFF
+        self.reverb_seed = (int(seed) * 0x9E3779B1 + int(rank) * 0x85EBCA6B + 0x2E7B) \
+            & 0xFFFFFFFFFFFFFFFF
+        self.reverb = None         # (RirBank, permille)
+        if training and FLAGS.rir_csv:
+            from ctc_asr_amd.reverb import RirBank
+            self.reverb = (RirBank.from_flags(device), FLAGS.rir_permille)
         self.noise = None          # (NoiseBank, snr_lo_db, snr_hi_db, permille)
         check_noise_flags(FLAGS)
         eval_snr = parse_eval_noise_snr_db(FLAGS.eval_noise_snr_db)
@@ -278,7 +290,8 @@ class _Augmenter:
                 self.noise = (NoiseBank.from_flags(device), eval_snr, eval_snr, 1000)
 
     def __bool__(self):
-        return bool(self.percents) or self.spec is not None or self.noise is not None
+        return bool(self.percents) or self.spec is not None or self.noise is not None or \
+            self.reverb is not None
 
     def next_seed(self):
         self.seed = (self.seed * 6364136223846793005 + 1442695040888963407) & 0xFFFFFFFFFFFFFFFF
@@ -289,12 +302,18 @@ class _Augmenter:
             & 0xFFFFFFFFFFFFFFFF
         return self.noise_seed
 
+    def next_reverb_seed(self):
+        self.reverb_seed = (self.reverb_seed * 6364136223846793005 + 1442695040888963407) \
+            & 0xFFFFFFFFFFFFFFFF
+        return self.reverb_seed
+
 
 def _make_batch(items, device, staged=None, augment=None):
     """Features of one batch on the current stream.  ``staged``: the batch's `_Staged` uploads
     (made by the reader thread); without it they are made here.  ``augment``: the `_Augmenter`
-    of the iterator - speed perturbation of the PCM, then the noise, then the features, then
-    SpecAugment, all on this stream; without it exactly the launches of a plain batch."""
+    of the iterator - speed perturbation of the PCM, then the reverberation, then the noise, then
+    the features, then SpecAugment, all on this stream; without it exactly the launches of a plain
+    batch."""
     if staged is None:
         staged = _Staged(items, device, torch.cuda.current_stream(device))
     main = torch.cuda.current_stream(device)
@@ -306,10 +325,18 @@ def _make_batch(items, device, staged=None, augment=None):
     if staged.percent is not None:
         pcm, num_samples = hip.speed_perturb(pcm, num_samples, staged.percent,
                                              staged.perturbed_width)
+    reverb_draws = None
+    if augment is not None and augment.reverb is not None:
+        # into a tensor of its own (a sample is read by its neighbours); the noise then mixes into
+        # that one in place
+        bank, permille = augment.reverb
+        reverb_draws = torch.empty((pcm.shape[0], 2), dtype=torch.int32, device=pcm.device)
+        pcm = hip.reverb(pcm, num_samples, bank.taps, bank.offsets, bank.delay, bank.scale,
+                         augment.next_reverb_seed(), permille, draws=reverb_draws)
     noise_draws = None
     if augment is not None and augment.noise is not None:
-        # in place: the PCM of this batch is a tensor of its own (the upload, or the resampler's
-        # output), and rows that draw no noise are then not stored at all
+        # in place: the PCM of this batch is a tensor of its own (the upload, the resampler's
+        # output or the reverberation's), and rows that draw no noise are then not stored at all
         bank, snr_lo, snr_hi, permille = augment.noise
         noise_draws = torch.empty((pcm.shape[0], 4), dtype=torch.int32, device=pcm.device)
         hip.noise_mix(pcm, num_samples, bank.bank, bank.clip_offsets, augment.next_noise_seed(),
@@ -322,7 +349,7 @@ def _make_batch(items, device, staged=None, augment=None):
         hip.spec_augment(feats, lengths, augment.next_seed(), n_freq, freq_width, n_time,
                          time_width, permille)
     return Batch(feats, lengths, staged.texts, staged.labels, staged.seconds,
-                 staged.packed_labels, pcm, num_samples, noise_draws)
+                 staged.packed_labels, pcm, num_samples, noise_draws, reverb_draws)
 
 
 def _example_stream(csv_path, shuffle, rng):
@@ -426,7 +453,8 @@ def input_fn_generator(target, device='cuda', rank=0, world_size=1, seed=None, p
     'test' batches are the same with the flags on and off.  Buckets are formed on the source
     lengths; an utterance slowed or sped up stays in its bucket.  ``--noise_csv`` mixes noise into
     the training targets; 'dev' and 'test' get it only under ``--eval_noise_snr_db``, and then the
-    same noise at every call of ``input_fn``.
+    same noise at every call of ``input_fn``.  ``--rir_csv`` reverberates the training targets,
+    between the speed perturbation and the noise; 'dev' and 'test' never.
     """
     if target == 'train_bucket':
         csv_path, use_buckets = FLAGS.train_csv, True
@@ -448,7 +476,8 @@ def input_fn_generator(target, device='cuda', rank=0, world_size=1, seed=None, p
         if dev.index is None:
             dev = torch.device('cuda', torch.cuda.current_device())
         augment = None
-        if training and (FLAGS.spec_augment or FLAGS.speed_perturb or FLAGS.noise_csv):
+        if training and (FLAGS.spec_augment or FLAGS.speed_perturb or FLAGS.noise_csv or
+                         FLAGS.rir_csv):
             # (seeded like the epoch where it has a seed; otherwise like its shuffle: fresh)
             augment = _Augmenter(seed if seed is not None else random.getrandbits(63), rank,
                                  device=dev)

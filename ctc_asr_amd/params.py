@@ -403,6 +403,22 @@ FLAGS.define('string', 'eval_noise_snr_db', '',
              parse_eval_noise_snr_db)
 FLAGS.define_validator(check_noise_flags)
 
+# Reverberation on the device (no counterpart in the reference; off while --rir_csv is empty: a
+# batch then launches what it always did).  Training batches draw whether and with which room
+# impulse response per row, after the speed perturbation and before the noise; 'dev' / 'test',
+# evaluate / predict / align never reverberate.
+RIR_TAPS_RANGE = (8, 8192)          # CTCASR_REVERB_TAP_ALIGN, CTCASR_REVERB_MAX_TAPS
+FLAGS.define('string', 'rir_csv', '',
+             'Manifest (path;label;length, labels ignored) of the room impulse responses that '
+             'training batches are convolved with; empty: off.')
+FLAGS.define('string', 'rir_dir', '', 'Root of the impulse response WAVs; empty: corpus_dir.')
+FLAGS.define('int', 'rir_permille', 500,
+             'Share of the training utterances that get reverberated, in thousandths (0..1000).',
+             _int_range('rir_permille', 0, 1000))
+FLAGS.define('int', 'rir_max_taps', 8192,
+             'Cap on the length of an impulse response, in samples (8..8192).',
+             _int_range('rir_max_taps', *RIR_TAPS_RANGE))
+
 # CTC decoder (asr/params.py:84-86).
 FLAGS.define('int', 'beam_width', 1024, 'Leaves kept by the CTC beam search (<= 1024).')
 
@@ -507,6 +523,9 @@ def get_parameters():
                     'eval_snr_db={});'.format(
                         FLAGS.noise_csv, FLAGS.noise_snr_db, FLAGS.noise_permille,
                         FLAGS.noise_max_seconds, FLAGS.eval_noise_snr_db or 'off'))
+    if FLAGS.rir_csv:
+        rows.append('\tReverb (rir_csv={}, permille={}, max_taps={:,d});'.format(
+            FLAGS.rir_csv, FLAGS.rir_permille, FLAGS.rir_max_taps))
     if FLAGS.lr_schedule != 'constant' or FLAGS.lr_warmup_steps > 0 or \
             FLAGS.grad_accum_steps > 1 or FLAGS.ema_decay > 0 or FLAGS.eval_ema:
         rows.append('\tSchedule (lr_schedule={}, minimum_lr={}, warmup_steps={:,d}, '

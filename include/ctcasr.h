@@ -899,6 +899,51 @@ int ctcasr_noise_mix(const int16_t *pcm, const int32_t *num_samples, int B, int 
                      int16_t *out, int32_t *draws, int64_t *powers, float *gain,
                      void *workspace, size_t workspace_bytes, ctcasr_stream_t stream);
 
+/* ---- K17: reverberation with a drawn room impulse response ----------------------------------
+ * No counterpart in the reference.  Convolves every drawn row of a batch of PCM with one response
+ * of a bank, after ctcasr_speed_perturb and before ctcasr_noise_mix.  The output has the input's
+ * length: rir_delay puts the direct path of the room on the sample it came from, and the tail
+ * beyond n is cut, so num_samples, labels and timestamps do not move.
+ *   pcm, out      int16 [B, max_samples]; out must NOT be pcm (a sample is read by its neighbours)
+ *   num_samples   int32 [B]; n = num_samples[b]
+ *   taps          int16: all responses back to back, 16-byte aligned
+ *   rir_offsets   DEVICE int64 [num_rirs + 1]; response r = taps[rir_offsets[r] : rir_offsets[r + 1]],
+ *                 K_r taps.  Trusted to stay inside `taps`.
+ *   rir_delay     DEVICE int32 [num_rirs]: the tap that holds the direct path
+ *   rir_scale     DEVICE fp32 [num_rirs]
+ * Draws of row b, from the generator of K15:
+ *   hit = below(seed, 8 b, 1000) < prob_permille        r = below(seed, 8 b + 1, num_rirs)
+ * Status of row b:
+ *   0  hit false, or n outside [1, max_samples]                                   (r reported 0)
+ *   2  drew a response that is not served: K_r outside [CTCASR_REVERB_TAP_ALIGN,
+ *      CTCASR_REVERB_MAX_TAPS], K_r or rir_offsets[r] not a multiple of CTCASR_REVERB_TAP_ALIGN
+ *      (or a negative offset), rir_delay[r] outside [0, K_r)
+ *   1  reverberated: for i < n, with h = taps + rir_offsets[r], K = K_r, d = rir_delay[r],
+ *        acc    = sum over k < K of h[k] * x[i + d - k],  x = 0 outside [0, n),
+ *                 as a 32-bit two's-complement integer (the sum mod 2^32: exact, so it depends on
+ *                 no grid, tile or order of summation; a bank with sum |h[k]| <= 65535 per
+ *                 response - ctc_asr_amd/reverb.py makes one - never wraps: |acc| <= 32768 * 65535)
+ *        out[i] = clamp(rintf((float)acc * rir_scale[r]), -32768, 32767)
+ *                 one int-to-fp32 conversion (round to nearest even), one fp32 multiply, rintf.
+ * Everything else is a bit copy of pcm: rows of status 0 and 2 (all max_samples columns), and in
+ * every row the columns at or beyond n.
+ *   draws   optional int32 [B, 2] = (status, r); may be NULL.
+ * One launch; a workgroup serves CTCASR_REVERB_CHUNK output samples of one row and walks the taps
+ * CTCASR_REVERB_TAP_BLOCK at a time (a remainder 8 at a time).
+ * Errors, before any launch: a null pcm / num_samples / taps / rir_offsets / rir_delay / rir_scale
+ * / out, out == pcm, B < 1, max_samples < 1, num_rirs < 1, prob_permille outside [0, 1000]:
+ * CTCASR_ERR_BAD_ARGUMENT; max_samples > 2^30, num_rirs > 2^24 or more than INT_MAX workgroups:
+ * CTCASR_ERR_UNSUPPORTED.
+ * prob_permille == 0 launches no kernel: a device-to-device copy, and draws zeroed by a memset. */
+#define CTCASR_REVERB_CHUNK 2048
+#define CTCASR_REVERB_TAP_BLOCK 32
+#define CTCASR_REVERB_TAP_ALIGN 8
+#define CTCASR_REVERB_MAX_TAPS 8192
+int ctcasr_reverb(const int16_t *pcm, const int32_t *num_samples, int B, int max_samples,
+                  const int16_t *taps, const int64_t *rir_offsets, const int32_t *rir_delay,
+                  const float *rir_scale, int num_rirs, uint64_t seed, int prob_permille,
+                  int16_t *out, int32_t *draws, ctcasr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
