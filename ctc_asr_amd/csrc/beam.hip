@@ -1,5 +1,6 @@
 // K10: CTC beam search on the GPU with the semantics of TensorFlow 1.12's CTCBeamSearchDecoder
-// (top path, merge_repeated=False) as called by CTCModel.decode_fn (asr/model.py:292-296).
+// (merge_repeated=False; the top path, or the top_paths best leaves of the final beam with
+// NBEST) as called by CTCModel.decode_fn (asr/model.py:292-296).
 //
 // One workgroup per utterance; the beam (<= 1024 leaves) lives in LDS.  Per frame:
 //   1. all threads: normalise the frame, copy new -> old, update every leaf from its own and its
@@ -125,6 +126,8 @@ __device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long v)
 }
 
 // ascending bitonic sort of n 64-bit keys (n padded to pow2 with ~0ull), all threads
+// (NBEST: a copy per kind of kernel, for the reason given at `beam_expand`)
+template <bool NBEST>
 __device__ void bitonic_sort(unsigned long long *keys, int n_pow2, int tid) {
     for (int k = 2; k <= n_pow2; k <<= 1) {
         for (int j = k >> 1; j > 0; j >>= 1) {
@@ -157,7 +160,9 @@ __device__ void bitonic_sort(unsigned long long *keys, int n_pow2, int tid) {
 // coalesced row load each per branch, fetched one branch ahead like the children row - and a
 // child's value is x[c] + (prev + score): TensorFlow's GetStateExpansionScore.  An edge of -inf
 // is no candidate and creates no node.
-template <int PER, bool LM>
+// NBEST changes nothing here: it gives the n-best kernels copies of their own, so that the
+// inliner sees the top-1 kernels' callees exactly as it did before there were four kernels.
+template <int PER, bool LM, bool NBEST>
 __device__ void beam_expand(typename BeamLdsOf<LM>::type &L, int lane, int W, int C, int blank,
                             int nslots, int nheap0, int *pool_parent, int *pool_label,
                             int *pool_children, int nodes_per_utt, const BeamLm &lm) {
@@ -337,13 +342,16 @@ __device__ void beam_expand(typename BeamLdsOf<LM>::type &L, int lane, int W, in
 }
 
 // LM = false is the search without a model: every use of `lm` is compiled out.
-template <bool LM>
+// NBEST = true returns the `top_paths` best leaves of the final beam instead of one (out
+// [B, top_paths, T], out_len / logp [B, top_paths], n_paths [B]); the search loop is the same, and
+// NBEST = false reads neither `top_paths` nor `n_paths` and is the kernel as it was.
+template <bool LM, bool NBEST>
 __global__ void __launch_bounds__(BEAM_THREADS)
 beam_decode_kernel(const float *__restrict__ logits, const int *__restrict__ seq_len, int T, int B,
                    int C, int blank, int W, int norm_mode, int *__restrict__ out,
                    int *__restrict__ out_len, float *__restrict__ logp, int *pool_parent,
                    int *pool_label, int *pool_slot, int *pool_children, int nodes_per_utt,
-                   BeamLm lm) {
+                   BeamLm lm, int top_paths, int *__restrict__ n_paths) {
     typedef typename BeamLdsOf<LM>::type Lds;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     Lds &L = *reinterpret_cast<Lds *>(smem);
@@ -358,7 +366,12 @@ beam_decode_kernel(const float *__restrict__ logits, const int *__restrict__ seq
 
     for (int s = tid; s < nslots; s += BEAM_THREADS) { L.alive[s] = 0; L.was_alive[s] = 0; }
     for (int c = tid; c < C; c += BEAM_THREADS) gstore(&pool_children[c], -1);
-    for (int i = tid; i < T; i += BEAM_THREADS) out[(size_t)b * T + i] = 0;
+    if constexpr (NBEST) {
+        for (int i = tid; i < top_paths * T; i += BEAM_THREADS)
+            out[(size_t)b * top_paths * T + i] = 0;
+    } else {
+        for (int i = tid; i < T; i += BEAM_THREADS) out[(size_t)b * T + i] = 0;
+    }
     __syncthreads();
     if (tid == 0) {
         L.node[0] = 0; L.label[0] = -1; L.parent[0] = -1; L.alive[0] = 1;
@@ -435,7 +448,7 @@ beam_decode_kernel(const float *__restrict__ logits, const int *__restrict__ seq
             }
         }
         __syncthreads();
-        bitonic_sort(L.sort_a, n_pow2, tid);
+        bitonic_sort<NBEST>(L.sort_a, n_pow2, tid);
         for (int i = tid; i < nheap0; i += BEAM_THREADS) {
             const int sa = (int)(L.sort_a[i] & 0x7ffu);
             L.branches[i] = sa;
@@ -447,14 +460,14 @@ beam_decode_kernel(const float *__restrict__ logits, const int *__restrict__ seq
         if (tid < 64) {
             const int per = (W + 63) / 64;
             if (per <= 1)
-                beam_expand<1, LM>(L, lane, W, C, blank, nslots, nheap0, pool_parent, pool_label,
-                               pool_children, nodes_per_utt, lm);
+                beam_expand<1, LM, NBEST>(L, lane, W, C, blank, nslots, nheap0, pool_parent,
+                                          pool_label, pool_children, nodes_per_utt, lm);
             else if (per <= 4)
-                beam_expand<4, LM>(L, lane, W, C, blank, nslots, nheap0, pool_parent, pool_label,
-                               pool_children, nodes_per_utt, lm);
+                beam_expand<4, LM, NBEST>(L, lane, W, C, blank, nslots, nheap0, pool_parent,
+                                          pool_label, pool_children, nodes_per_utt, lm);
             else
-                beam_expand<16, LM>(L, lane, W, C, blank, nslots, nheap0, pool_parent, pool_label,
-                                pool_children, nodes_per_utt, lm);
+                beam_expand<16, LM, NBEST>(L, lane, W, C, blank, nslots, nheap0, pool_parent,
+                                           pool_label, pool_children, nodes_per_utt, lm);
         }
         __syncthreads();
         // ---- beam slots of the tree nodes for the next frame -----------------------------------
@@ -475,7 +488,50 @@ beam_decode_kernel(const float *__restrict__ logits, const int *__restrict__ seq
             __syncthreads();
         }
     }
-    if (tid == 0) {
+    if constexpr (NBEST) {
+        // the final leaves in the order of the branch sort - total descending, equal totals: the
+        // older node first, so rank 0 is the leaf `worse` picks below - then one thread per rank
+        // walks its leaf's parent chain
+        const int nheap = L.misc[0];
+        int n_pow2 = 1;
+        while (n_pow2 < nheap) n_pow2 <<= 1;
+        for (int i = tid; i < n_pow2; i += BEAM_THREADS) {
+            if (i < nheap) {
+                const int s = L.heap[i];
+                const unsigned nd = min((unsigned)L.node[s], 0x1fffffu);
+                // + 0.f: -0 and +0 are one total, as they are to `worse`
+                L.sort_a[i] = ((unsigned long long)(~order_key(L.n_total[s] + 0.f)) << 32) |
+                              (nd << 11) | (unsigned)s;
+            } else {
+                L.sort_a[i] = ~0ull;
+            }
+        }
+        __syncthreads();
+        bitonic_sort<NBEST>(L.sort_a, n_pow2, tid);
+        const bool overflow = L.misc[3] != 0;     // the prefix-tree pool ran out: the row is void
+        const int found = min(top_paths, nheap);
+        if (tid == 0) n_paths[b] = overflow ? -1 : found;
+        for (int r = tid; r < top_paths; r += BEAM_THREADS) {
+            const size_t at = (size_t)b * top_paths + r;
+            if (r >= found) {
+                out_len[at] = overflow ? -1 : 0;
+                logp[at] = -INFINITY;
+                continue;
+            }
+            const int s = (int)(L.sort_a[r] & 0x7ffu);
+            int n = 0;
+            for (int node = L.node[s]; gload(&pool_parent[node]) >= 0;
+                 node = gload(&pool_parent[node]))
+                ++n;
+            n = min(n, T);      // a label needs a frame: never more than T, whatever the pool holds
+            out_len[at] = overflow ? -1 : n;
+            logp[at] = L.n_total[s];
+            int k = n;
+            for (int node = L.node[s]; k > 0 && gload(&pool_parent[node]) >= 0;
+                 node = gload(&pool_parent[node]))
+                out[at * T + --k] = gload(&pool_label[node]);
+        }
+    } else if (tid == 0) {
         const int nheap = L.misc[0];
         int best = L.heap[0];
         for (int i = 1; i < nheap; ++i)
@@ -514,10 +570,15 @@ extern "C" size_t ctcasr_ctc_beam_workspace_bytes(int T, int B, int C, int beam_
 
 namespace {
 
-// arguments, limits, workspace layout and launch of both entry points (lm: NULL without a model)
+// arguments, limits, workspace layout and launch of all entry points (lm: NULL without a model;
+// top_paths 0: the top-1 entry points, whose `logp` may be NULL and which have no `n_paths`)
 int beam_launch(const float *logits, const int32_t *seq_len, int T, int B, int C, int blank,
-                int beam_width, int norm_mode, const BeamLm *lm, int32_t *out, int32_t *out_len,
-                float *logp, void *workspace, size_t workspace_bytes, ctcasr_stream_t stream) {
+                int beam_width, int norm_mode, const BeamLm *lm, int top_paths, int32_t *out,
+                int32_t *out_len, float *logp, int32_t *n_paths, void *workspace,
+                size_t workspace_bytes, ctcasr_stream_t stream) {
+    const bool nbest = top_paths != 0 || n_paths;
+    if (nbest && (!logp || !n_paths || top_paths < 1 || top_paths > beam_width))
+        return CTCASR_ERR_BAD_ARGUMENT;
     if (!logits || !seq_len || !out || !out_len || T <= 0 || B <= 0 || C <= 1 || blank < 0 ||
         blank >= C || beam_width <= 0 || norm_mode < 0 || norm_mode > 1)
         return CTCASR_ERR_BAD_ARGUMENT;
@@ -530,20 +591,23 @@ int beam_launch(const float *logits, const int32_t *seq_len, int T, int B, int C
     int *pool_label = pool_parent + (size_t)B * n;
     int *pool_slot = pool_label + (size_t)B * n;
     int *pool_children = pool_slot + (size_t)B * n;
-    const void *kernel = lm ? reinterpret_cast<const void *>(&beam_decode_kernel<true>)
-                            : reinterpret_cast<const void *>(&beam_decode_kernel<false>);
     const size_t lds = lm ? sizeof(BeamLdsLm) : sizeof(BeamLds);
-    if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
-        hipSuccess)
-        return CTCASR_ERR_LAUNCH;
-    if (lm)
-        beam_decode_kernel<true><<<B, BEAM_THREADS, lds, (hipStream_t)stream>>>(
-            logits, seq_len, T, B, C, blank, beam_width, norm_mode, out, out_len, logp,
-            pool_parent, pool_label, pool_slot, pool_children, (int)n, *lm);
-    else
-        beam_decode_kernel<false><<<B, BEAM_THREADS, lds, (hipStream_t)stream>>>(
-            logits, seq_len, T, B, C, blank, beam_width, norm_mode, out, out_len, logp,
-            pool_parent, pool_label, pool_slot, pool_children, (int)n, BeamLm{});
+#define BEAM_LAUNCH(LM, NBEST)                                                                  \
+    do {                                                                                        \
+        if (hipFuncSetAttribute(reinterpret_cast<const void *>(&beam_decode_kernel<LM, NBEST>), \
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=        \
+            hipSuccess)                                                                         \
+            return CTCASR_ERR_LAUNCH;                                                           \
+        beam_decode_kernel<LM, NBEST><<<B, BEAM_THREADS, lds, (hipStream_t)stream>>>(           \
+            logits, seq_len, T, B, C, blank, beam_width, norm_mode, out, out_len, logp,         \
+            pool_parent, pool_label, pool_slot, pool_children, (int)n, lm ? *lm : BeamLm{},     \
+            top_paths, n_paths);                                                                \
+    } while (0)
+    if (lm && nbest) BEAM_LAUNCH(true, true);
+    else if (lm) BEAM_LAUNCH(true, false);
+    else if (nbest) BEAM_LAUNCH(false, true);
+    else BEAM_LAUNCH(false, false);
+#undef BEAM_LAUNCH
     return ctcasr_launch_status();
 }
 
@@ -553,8 +617,8 @@ extern "C" int ctcasr_ctc_beam_decode(const float *logits, const int32_t *seq_le
                                       int C, int blank, int beam_width, int norm_mode,
                                       int32_t *out, int32_t *out_len, float *logp, void *workspace,
                                       size_t workspace_bytes, ctcasr_stream_t stream) {
-    return beam_launch(logits, seq_len, T, B, C, blank, beam_width, norm_mode, nullptr, out,
-                       out_len, logp, workspace, workspace_bytes, stream);
+    return beam_launch(logits, seq_len, T, B, C, blank, beam_width, norm_mode, nullptr, 0, out,
+                       out_len, logp, nullptr, workspace, workspace_bytes, stream);
 }
 
 // A leaf's state and edge score are constants of its tree node, and the branch's rows give them
@@ -571,6 +635,25 @@ extern "C" int ctcasr_ctc_beam_decode_lm(const float *logits, const int32_t *seq
                                          int32_t *out_len, float *logp, void *workspace,
                                          size_t workspace_bytes, ctcasr_stream_t stream) {
     const BeamLm lm = {lm_next, lm_score, lm_final, lm_states};
-    return beam_launch(logits, seq_len, T, B, C, blank, beam_width, norm_mode, &lm, out, out_len,
-                       logp, workspace, workspace_bytes, stream);
+    return beam_launch(logits, seq_len, T, B, C, blank, beam_width, norm_mode, &lm, 0, out,
+                       out_len, logp, nullptr, workspace, workspace_bytes, stream);
+}
+
+// The n-best list is read off the final beam: the search and its prefix tree are the plain ones.
+extern "C" size_t ctcasr_ctc_beam_nbest_workspace_bytes(int T, int B, int C, int beam_width) {
+    return ctcasr_ctc_beam_workspace_bytes(T, B, C, beam_width);
+}
+
+extern "C" int ctcasr_ctc_beam_decode_nbest(const float *logits, const int32_t *seq_len, int T,
+                                            int B, int C, int blank, int beam_width, int norm_mode,
+                                            int top_paths, const int32_t *lm_next,
+                                            const float *lm_score, const float *lm_final,
+                                            int lm_states, int32_t *out, int32_t *out_len,
+                                            float *logp, int32_t *n_paths, void *workspace,
+                                            size_t workspace_bytes, ctcasr_stream_t stream) {
+    if (top_paths < 1 || !n_paths) return CTCASR_ERR_BAD_ARGUMENT;
+    const BeamLm lm = {lm_next, lm_score, lm_final, lm_states};
+    return beam_launch(logits, seq_len, T, B, C, blank, beam_width, norm_mode,
+                       lm_next ? &lm : nullptr, top_paths, out, out_len, logp, n_paths, workspace,
+                       workspace_bytes, stream);
 }

@@ -4,7 +4,9 @@ Counterpart of ``asr/evaluate.py:18-43``: one pass over dev.csv (``--dev``) or t
 model in evaluation mode; reports the CTC loss and the two ``eval_metric_ops`` of
 ``asr/model.py:111-118`` — mean edit distance and word error rate, each the unweighted mean over
 batches of the per-batch mean.  Decoding is the CTC beam search of width ``FLAGS.beam_width``,
-with the language model of ``--lm_path`` fused in when that flag is set.
+with the language model of ``--lm_path`` fused in when that flag is set.  ``--nbest N`` also
+reads the N best hypotheses off each final beam and reports the oracle error rates of the beam
+and, with ``--rescore_lm_path``, the rates of the re-ranked hypotheses.
 """
 
 import sys
@@ -12,14 +14,14 @@ import sys
 import numpy as np
 import torch
 
-from ctc_asr_amd import lm, storage, summaries
+from ctc_asr_amd import lm, metrics, storage, summaries
 from ctc_asr_amd.input_functions import input_fn_generator
 from ctc_asr_amd.model import CTCModel, ModelConfig
 from ctc_asr_amd.params import FLAGS
 
 
 def evaluate_dataset(model, target, rank=0, world=1, max_batches=None, report_samples=True,
-                     scorer=None):
+                     scorer=None, nbest=0, rescorer=None):
     """{'loss', 'mean_edit_distance', 'word_error_rate', 'batches'} for one pass over
     ``target`` ('dev' or 'test'); with ``world > 1`` every rank scores its shard and the
     per-batch means are averaged over ranks.  ``scorer``: a scaled `lm.LmScorer` to decode
@@ -27,7 +29,13 @@ def evaluate_dataset(model, target, rank=0, world=1, max_batches=None, report_sa
     result also holds the error breakdown summed over the set - 'label_errors' and
     'word_errors', each {'substitutions', 'deletions', 'insertions', 'reference'} - and the
     corpus-level 'corpus_label_error_rate' and 'corpus_word_error_rate': total errors over
-    total reference length."""
+    total reference length.
+    ``nbest`` > 0 decodes with `CTCModel.nbest_many` (rank 0 is the top-1 decode, so every value
+    above is what it is without it) and adds 'oracle_label_error_rate' /
+    'oracle_word_error_rate' - per utterance the fewest errors over its hypotheses, summed, over
+    the total reference length -, 'nbest_mean_paths' and, with a ``rescorer`` (a scaled
+    `lm.LmScorer` that re-ranks the lists), 'rescored_label_error_rate' /
+    'rescored_word_error_rate', the same corpus-level rates of the selected hypotheses."""
     input_fn = input_fn_generator(target, device=model.device, rank=rank, world_size=world,
                                   seed=(FLAGS.random_seed or 1) if world > 1 else None)
     losses, meds, wers = [], [], []
@@ -37,12 +45,34 @@ def evaluate_dataset(model, target, rank=0, world=1, max_batches=None, report_sa
     pending, group, samples = [], None, None
     # (S, D, I, reference length) summed over the set: labels, then words
     totals = np.zeros((2, 4), dtype=np.int64)
+    # n-best: oracle errors (labels, words), rescored errors (labels, words), reference lengths
+    # (labels, words), hypotheses, utterances
+    listed_totals = np.zeros(8, dtype=np.int64)
+
+    def score_lists(lists, labels, texts):
+        label_dist, word_dist, sizes = model.nbest_error_counts(lists, labels, texts)
+        listed_totals[0] += metrics.oracle_errors(label_dist, sizes).sum()
+        listed_totals[1] += metrics.oracle_errors(word_dist, sizes).sum()
+        picked = np.cumsum(sizes) - sizes + np.array([r['selected'] for r in lists])
+        listed_totals[2] += label_dist[picked].sum()
+        listed_totals[3] += word_dist[picked].sum()
+        truths = labels.cpu().numpy() if isinstance(labels, torch.Tensor) else labels
+        listed_totals[4] += sum(int(np.count_nonzero(np.asarray(row))) for row in truths)
+        listed_totals[5] += sum(len(text.split()) for text in texts)
+        listed_totals[6] += sizes.sum()
+        listed_totals[7] += len(sizes)
 
     def score_pending():
         nonlocal samples
-        results = model.decode_many([(logits, seq_len, originals)
-                                     for logits, seq_len, originals, _, _ in pending],
-                                    scorer=scorer)
+        batches = [(logits, seq_len, originals) for logits, seq_len, originals, _, _ in pending]
+        if nbest:
+            lists = model.nbest_many(batches, nbest, scorer=scorer, rescorer=rescorer)
+            results = [model.nbest_top(listed, originals)
+                       for listed, (_, _, originals) in zip(lists, batches)]
+            for listed, (_, _, _, labels, texts) in zip(lists, pending):
+                score_lists(listed, labels, texts)
+        else:
+            results = model.decode_many(batches, scorer=scorer)
         for (decoded, plaintext, summary), (_, _, _, labels, texts) in zip(results, pending):
             if model.gpu_metrics:
                 _, mean_ed, _, wer, label_counts, word_counts, reference = \
@@ -82,7 +112,8 @@ def evaluate_dataset(model, target, rank=0, world=1, max_batches=None, report_sa
             print('  decoded: "{}"\n  original: "{}"'.format(dec, orig))
     # (the integer sums ride in the same float64 all_reduce: exact below 2^53)
     stats = torch.tensor([np.sum(losses), np.sum(meds), np.sum(wers), len(losses)] +
-                         totals.reshape(-1).tolist(), dtype=torch.float64, device=model.device)
+                         totals.reshape(-1).tolist() + listed_totals.tolist(),
+                         dtype=torch.float64, device=model.device)
     if world > 1:
         torch.distributed.all_reduce(stats)
     count = max(float(stats[3]), 1.0)
@@ -95,6 +126,14 @@ def evaluate_dataset(model, target, rank=0, world=1, max_batches=None, report_sa
                                         'insertions': ins, 'reference': reference}
             result['corpus_{}_error_rate'.format(name)] = \
                 (subs + dels + ins) / reference if reference else float('nan')
+    if nbest:
+        listed = [int(v) for v in stats[12:20].tolist()]
+        result['oracle_label_error_rate'] = metrics.corpus_rate(listed[0], listed[4])
+        result['oracle_word_error_rate'] = metrics.corpus_rate(listed[1], listed[5])
+        result['nbest_mean_paths'] = listed[6] / listed[7] if listed[7] else float('nan')
+        if rescorer is not None:
+            result['rescored_label_error_rate'] = metrics.corpus_rate(listed[2], listed[4])
+            result['rescored_word_error_rate'] = metrics.corpus_rate(listed[3], listed[5])
     return result
 
 
@@ -109,7 +148,9 @@ def main(argv=None):
     storage.restore_checkpoint(latest, model, weights='ema' if FLAGS.eval_ema else 'param')
     target = 'dev' if FLAGS.dev else 'test'
     print('Evaluating checkpoint {} on the {} set.'.format(latest, target))
-    result = evaluate_dataset(model, target, scorer=lm.from_flags(model.cfg.num_classes))
+    result = evaluate_dataset(model, target, scorer=lm.from_flags(model.cfg.num_classes),
+                              nbest=FLAGS.nbest,
+                              rescorer=lm.rescorer_from_flags(model.cfg.num_classes))
     writer = summaries.SummaryWriter(FLAGS.train_dir, 'eval_' + target)
     for tag in ('loss', 'mean_edit_distance', 'word_error_rate'):       # eval_metric_ops + loss
         writer.scalar(tag, result[tag], model.step_count)

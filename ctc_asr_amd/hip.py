@@ -56,6 +56,12 @@ SIGNATURES = {
     'ctcasr_ctc_beam_lm_workspace_bytes': (_c_sz, [_c_int] * 4),
     'ctcasr_ctc_beam_decode_lm': (_c_int, [_c_p, _c_p] + [_c_int] * 6 + [_c_p] * 3 + [_c_int] +
                                   [_c_p] * 4 + [_c_sz, _c_p]),
+    'ctcasr_ctc_beam_nbest_workspace_bytes': (_c_sz, [_c_int] * 4),
+    'ctcasr_ctc_beam_decode_nbest': (_c_int, [_c_p, _c_p] + [_c_int] * 7 + [_c_p] * 3 + [_c_int] +
+                                     [_c_p] * 5 + [_c_sz, _c_p]),
+    'ctcasr_ctc_score_workspace_bytes': (_c_sz, [_c_int] * 5),
+    'ctcasr_ctc_score': (_c_int, [_c_p, _c_p] + [_c_int] * 4 + [_c_p] * 3 + [_c_int] * 2 +
+                         [_c_p] * 3 + [_c_sz, _c_p]),
     'ctcasr_ctc_align_workspace_bytes': (_c_sz, [_c_int] * 4),
     'ctcasr_ctc_align': (_c_int, [_c_p] * 4 + [_c_int] * 5 + [_c_p] * 5 + [_c_sz, _c_p]),
     'ctcasr_edit_distance_workspace_bytes': (_c_sz, [_c_int] * 3),
@@ -426,6 +432,94 @@ def ctc_beam_decode_lm(logits, seq_len, beam_width, scorer, blank=None, normaliz
     if bool((out_len < 0).any()):
         raise CtcAsrError('ctc_beam_decode_lm: prefix-tree pool exhausted')
     return out, out_len, logp
+
+
+def ctc_beam_nbest_workspace_bytes(num_steps, batch, classes, beam_width):
+    return load().ctcasr_ctc_beam_nbest_workspace_bytes(num_steps, batch, classes,
+                                                        int(beam_width))
+
+
+@_on_tensor_device
+def ctc_beam_decode_nbest(logits, seq_len, beam_width, top_paths, scorer=None, blank=None,
+                          normalization='max'):
+    """The ``top_paths`` best leaves of the final beam of `ctc_beam_decode` (``scorer`` None) or
+    `ctc_beam_decode_lm`.  Returns (out i32[B, N, T], out_len i32[B, N], logp f32[B, N], n_paths
+    i32[B]); rank 0 is what the top-1 search returns, ranks >= n_paths[b] are empty (out_len 0,
+    logp -inf)."""
+    num_steps, batch, classes = _decode_shape('ctc_beam_decode_nbest', logits, seq_len)
+    if scorer is not None and scorer.num_classes != classes:
+        raise CtcAsrError('ctc_beam_decode_nbest: the scorer has {} classes, the logits {}.'
+                          .format(scorer.num_classes, classes))
+    blank = classes - 1 if blank is None else blank
+    top_paths = int(top_paths)
+    dev = logits.device
+    lm_next, lm_score, lm_final = scorer.to(dev) if scorer is not None else (None, None, None)
+    rows = max(top_paths, 0)
+    out = torch.empty((batch, rows, num_steps), dtype=torch.int32, device=dev)
+    out_len = torch.empty((batch, rows), dtype=torch.int32, device=dev)
+    logp = torch.empty((batch, rows), dtype=torch.float32, device=dev)
+    n_paths = torch.empty(batch, dtype=torch.int32, device=dev)
+    workspace = _workspace(load().ctcasr_ctc_beam_nbest_workspace_bytes(
+        num_steps, batch, classes, int(beam_width)), dev)
+    _check(load().ctcasr_ctc_beam_decode_nbest(
+        _dev(logits, name='logits'), _dev(seq_len, torch.int32, 'seq_len'), num_steps, batch,
+        classes, blank, int(beam_width), {'max': 0, 'log_softmax': 1}[normalization], top_paths,
+        _dev(lm_next, torch.int32, 'lm_next'), _dev(lm_score, name='lm_score'),
+        _dev(lm_final, name='lm_final'), scorer.num_states if scorer is not None else 0,
+        _dev(out, torch.int32, 'out'), _dev(out_len, torch.int32, 'out_len'),
+        _dev(logp, name='logp'), _dev(n_paths, torch.int32, 'n_paths'),
+        _dev(workspace, torch.uint8, 'workspace'), workspace.numel(), _stream()),
+        'ctc_beam_decode_nbest')
+    if bool((n_paths < 0).any()):
+        raise CtcAsrError('ctc_beam_decode_nbest: prefix-tree pool exhausted')
+    return out, out_len, logp, n_paths
+
+
+def ctc_score_workspace_bytes(num_steps, batch, classes, hyps, max_label_len):
+    return load().ctcasr_ctc_score_workspace_bytes(num_steps, batch, classes, int(hyps),
+                                                   int(max_label_len))
+
+
+@_on_tensor_device
+def ctc_score(logits, seq_len, labels, label_offsets, utt, max_label_len=None, blank=None,
+              score=None, status=None, workspace=None):
+    """Exact CTC log-likelihood of H label sequences.  logits f32[T, B, C]; seq_len i32[B];
+    labels / label_offsets (i32[H + 1]) as `ctc_loss_fwd_bwd` takes them; utt i32[H] names the
+    utterance of each hypothesis.  Returns (score f32[H], status i32[H]).  ``max_label_len``
+    defaults to the longest row.  A non-zero status is data, not an error: the caller reads it."""
+    num_steps, batch, classes = _decode_shape('ctc_score', logits, seq_len)
+    hyps = utt.numel()
+    if label_offsets.numel() != hyps + 1:
+        raise CtcAsrError('ctc_score: label_offsets holds {} entries for {} hypotheses.'
+                          .format(label_offsets.numel(), hyps))
+    _dev(label_offsets, torch.int32, 'label_offsets')
+    # the ABI takes bare pointers: keep every row the kernel may read inside `labels`
+    off64 = label_offsets.long()
+    low, high, longest = torch.stack([off64.min(), off64.max(),
+                                      (off64[1:] - off64[:-1]).max() if hyps else
+                                      off64.new_zeros(())]).tolist()
+    if low < 0 or high > labels.numel():
+        raise CtcAsrError('ctc_score: a row lies outside `labels`.')
+    max_label_len = max(longest, 0) if max_label_len is None else int(max_label_len)
+    blank = classes - 1 if blank is None else blank
+    dev = logits.device
+    score = torch.empty(hyps, dtype=torch.float32, device=dev) if score is None else score
+    status = torch.empty(hyps, dtype=torch.int32, device=dev) if status is None else status
+    _expect_numel('ctc_score', 'score', score, hyps)
+    _expect_numel('ctc_score', 'status', status, hyps)
+    if workspace is None:
+        workspace = _workspace(ctc_score_workspace_bytes(num_steps, batch, classes, hyps,
+                                                         max_label_len), dev)
+    # an empty `labels` has no address to give: the kernel reads none of it then
+    labels_ptr = _dev(labels, torch.int32, 'labels') if labels.numel() else \
+        _dev(label_offsets, torch.int32, 'label_offsets')
+    _check(load().ctcasr_ctc_score(
+        _dev(logits, name='logits'), _dev(seq_len, torch.int32, 'seq_len'), num_steps, batch,
+        classes, blank, labels_ptr, _dev(label_offsets, torch.int32, 'label_offsets'),
+        _dev(utt, torch.int32, 'utt'), hyps, max_label_len, _dev(score, name='score'),
+        _dev(status, torch.int32, 'status'), _dev(workspace, torch.uint8, 'workspace'),
+        workspace.numel(), _stream()), 'ctc_score')
+    return score, status
 
 
 def ctc_align_workspace_bytes(num_steps, batch, classes, max_label_len):

@@ -92,6 +92,26 @@ class LmScorer:
         return LmScorer(self.next, scale(self.score, bonus),
                         None if self.final is None else scale(self.final, 0.0), self.order)
 
+    def sequence_scores(self, rows):
+        """float64 [len(rows)]: for each label row the sum of its edge scores from state 0 plus
+        ``final`` of the state it ends in - what the fused search adds to a hypothesis, and
+        what a second-pass model gives one of an n-best list.  ``-inf`` (a forbidden edge or
+        end) passes through.  Raises ``ValueError`` for a label outside [0, C)."""
+        totals = np.zeros(len(rows), dtype=np.float64)
+        for i, row in enumerate(rows):
+            state, total = 0, 0.0
+            for c in row:
+                c = int(c)
+                if not 0 <= c < self.num_classes:
+                    raise ValueError('LmScorer.sequence_scores: label {} outside [0, {}).'
+                                     .format(c, self.num_classes))
+                total += float(self.score[state, c])
+                state = int(self.next[state, c])
+            if self.final is not None:
+                total += float(self.final[state])
+            totals[i] = total
+        return totals
+
     def to(self, device):
         """(next int32 [S, C], score f32 [S, C], final f32 [S] or None) on ``device``; uploaded
         once per device and cached."""
@@ -139,6 +159,16 @@ def from_flags(num_classes):
     if not FLAGS.lm_path:
         return None
     return load(FLAGS.lm_path, num_classes).scaled(FLAGS.lm_weight, FLAGS.lm_bonus)
+
+
+def rescorer_from_flags(num_classes):
+    """The scaled scorer of ``--rescore_lm_path`` / ``--rescore_lm_weight`` /
+    ``--rescore_lm_bonus``, which re-ranks the n-best list on the host; None when unset."""
+    from ctc_asr_amd.params import FLAGS
+    if not FLAGS.rescore_lm_path:
+        return None
+    return load(FLAGS.rescore_lm_path, num_classes).scaled(FLAGS.rescore_lm_weight,
+                                                           FLAGS.rescore_lm_bonus)
 
 
 def build_char_ngram(label_rows, order, num_classes, blank=None):

@@ -184,3 +184,25 @@ def wer_batch_from_counts(distances, original_lengths):
     mean = np.array(float(np.sum(rates.astype(np.float64))) / float(len(original_lengths)),
                     dtype=NP_FLOAT)
     return rates, mean
+
+
+def oracle_errors(distances, group_sizes):
+    """The fewest errors among each utterance's hypotheses: ``distances`` holds one edit
+    distance per hypothesis, utterance after utterance, ``group_sizes`` how many each utterance
+    has.  Returns int64 ``[len(group_sizes)]``; an utterance without hypotheses raises
+    ``ValueError`` (its oracle is undefined)."""
+    distances = np.asarray(distances, dtype=np.int64).reshape(-1)
+    sizes = np.asarray(group_sizes, dtype=np.int64).reshape(-1)
+    if (sizes < 1).any():
+        raise ValueError('oracle_errors(): an utterance has no hypothesis.')
+    if int(sizes.sum()) != distances.size:
+        raise ValueError('oracle_errors(): {} distances for groups of {} in all.'
+                         .format(distances.size, int(sizes.sum())))
+    starts = np.cumsum(sizes) - sizes
+    return np.minimum.reduceat(distances, starts) if sizes.size else np.zeros(0, dtype=np.int64)
+
+
+def corpus_rate(errors, reference_length):
+    """Total errors over total reference length, the corpus-level form of
+    ``corpus_*_error_rate``; NaN for an empty reference."""
+    return int(errors) / int(reference_length) if int(reference_length) else float('nan')

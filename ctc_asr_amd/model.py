@@ -1968,6 +1968,10 @@ class CTCModel:
     @staticmethod
     def _decoded_to_text(out, out_len, originals):
         decoded = [out[b, :out_len[b]].tolist() for b in range(out.shape[0])]
+        return CTCModel._lists_to_text(decoded, originals)
+
+    @staticmethod
+    def _lists_to_text(decoded, originals):
         width = max([len(d) for d in decoded] + [0])
         dense = np.zeros((len(decoded), width), dtype=np.int32)
         for b, row in enumerate(decoded):
@@ -2018,6 +2022,142 @@ class CTCModel:
         for logits, _, originals in batches:
             stop = start + int(logits.shape[1])
             results.append(self._decoded_to_text(out[start:stop], out_len[start:stop], originals))
+            start = stop
+        return results
+
+    # ------------------------------------------------------------------ n-best / rescoring
+    @staticmethod
+    def nbest_posteriors(totals, valid=None):
+        """(posterior float64[n], selected) of one utterance's hypotheses: the softmax of
+        ``totals`` over the entries ``valid`` marks (default: all) - the others get 0 - and the
+        index of the largest valid total, ties to the lower rank; -1 when nothing is valid.  A
+        ``-inf`` total has posterior 0; if every valid total is ``-inf`` they share the mass."""
+        totals = np.asarray(totals, dtype=np.float64)
+        valid = np.ones(totals.shape, dtype=bool) if valid is None else np.asarray(valid, bool)
+        posterior = np.zeros(totals.shape, dtype=np.float64)
+        if not valid.any():
+            return posterior, -1
+        masked = np.where(valid, totals, -np.inf)
+        selected = int(np.argmax(masked))              # (the first of equal maxima)
+        peak = masked[selected]
+        if np.isneginf(peak):
+            posterior[valid] = 1.0 / valid.sum()
+            return posterior, int(np.argmax(valid))
+        weights = np.exp(masked - peak)
+        return weights / weights.sum(), selected
+
+    def _nbest_launch(self, logits, seq_len, top_paths, beam_width, scorer, rescorer):
+        """One n-best launch, one `hip.ctc_score` launch over all B * N hypotheses, one
+        read-back; returns one dict per utterance (see `nbest_fn`)."""
+        from ctc_asr_amd.labels import decode
+        beam_width = self.cfg.beam_width if beam_width is None else beam_width
+        top_paths = int(top_paths)
+        out, out_len, logp, n_paths = hip.ctc_beam_decode_nbest(logits, seq_len, beam_width,
+                                                                top_paths, scorer=scorer)
+        num_steps, batch = int(logits.shape[0]), int(logits.shape[1])
+        # every rank is a hypothesis of the scoring launch; the empty ranks beyond n_paths point
+        # at no utterance (status 2: their waves leave at once)
+        ranks = torch.arange(top_paths, device=out.device, dtype=torch.int32)
+        rows = torch.arange(batch, device=out.device, dtype=torch.int32)
+        utt = torch.where(ranks[None, :] < n_paths[:, None], rows[:, None].expand(-1, top_paths),
+                          torch.full_like(out_len, -1)).reshape(-1).contiguous()
+        lengths = out_len.reshape(-1)
+        offsets = torch.zeros(batch * top_paths + 1, dtype=torch.int32, device=out.device)
+        offsets[1:] = torch.cumsum(lengths, 0)
+        frames = torch.arange(num_steps, device=out.device, dtype=torch.int32)
+        flat = out.reshape(-1, num_steps)[frames[None, :] < lengths[:, None]].contiguous()
+        ctc, status = hip.ctc_score(logits, seq_len, flat, offsets, utt,
+                                    max_label_len=max(int(out_len.max()), 0))
+        out, out_len, logp, n_paths, ctc, status = (
+            t.cpu().numpy() for t in (out, out_len, logp, n_paths,
+                                      ctc.reshape(batch, top_paths),
+                                      status.reshape(batch, top_paths)))
+        model = rescorer if rescorer is not None else scorer
+        results = []
+        for b in range(batch):
+            count = int(n_paths[b])
+            labels = [out[b, k, :out_len[b, k]].tolist() for k in range(count)]
+            lm_logp = model.sequence_scores(labels) if model is not None else np.zeros(count)
+            ctc_logp = ctc[b, :count].astype(np.float64)
+            totals = ctc_logp + lm_logp
+            posterior, selected = self.nbest_posteriors(totals, status[b, :count] == 0)
+            results.append({'selected': max(selected, 0), 'hypotheses': [
+                {'labels': labels[k], 'plaintext': decode(labels[k]),
+                 'beam_logp': float(logp[b, k]), 'ctc_logp': float(ctc_logp[k]),
+                 'lm_logp': float(lm_logp[k]), 'total': float(totals[k]),
+                 'posterior': float(posterior[k]), 'status': int(status[b, k])}
+                for k in range(count)]})
+        return results
+
+    def nbest_fn(self, logits, seq_len, top_paths, originals=None, beam_width=None, scorer=None,
+                 rescorer=None):
+        """The ``top_paths`` best hypotheses of every utterance, scored exactly.  Returns one
+        dict per utterance: ``'hypotheses'`` in first-pass order - each with ``labels``,
+        ``plaintext``, ``beam_logp`` (the beam's total), ``ctc_logp`` (the exact ln p(y | x),
+        `hip.ctc_score`), ``lm_logp`` (the ``rescorer``'s score of the labels if one is given,
+        else the ``scorer``'s, else 0), ``total`` = ctc_logp + lm_logp in float64 and
+        ``posterior``, the softmax of the totals over the utterance's hypotheses of status 0 -
+        and ``'selected'``, the index of the largest total (ties: the lower rank).
+        ``originals`` (the transcripts, as `decode_fn` takes them) are attached as
+        ``'original'`` when given.  ``scorer`` is fused into the search as in `decode_fn`;
+        ``rescorer`` (a scaled `lm.LmScorer`) only re-ranks."""
+        results = self._nbest_launch(logits, seq_len, top_paths, beam_width, scorer, rescorer)
+        return self._with_originals(results, originals)
+
+    @staticmethod
+    def _with_originals(results, originals):
+        if originals is not None and len(originals) > 0:
+            for result, original in zip(results, originals):
+                result['original'] = original.decode('utf-8') if isinstance(original, bytes) \
+                    else str(original)
+        return results
+
+    def nbest_top(self, results, originals=None, selected=False):
+        """The `decode_fn` triple (decoded, plaintext, summary) of rank 0 of every utterance of
+        an `nbest_fn` result - with ``selected`` of the selected hypothesis instead."""
+        decoded = [r['hypotheses'][r['selected'] if selected else 0]['labels'] for r in results]
+        return self._lists_to_text(decoded, originals)
+
+    def nbest_error_counts(self, results, labels, originals):
+        """Scores every hypothesis of an `nbest_fn` result against its utterance's reference,
+        all label pairs and all word pairs in ONE launch (`metrics.error_counts`).  Returns
+        (label distances, word distances, group sizes): int64 arrays, one distance per
+        hypothesis, utterance after utterance."""
+        if isinstance(labels, torch.Tensor):
+            labels = labels.cpu().numpy()
+        truths = [[int(v) for v in row if int(v) != 0] for row in labels]
+        sizes = [len(r['hypotheses']) for r in results]
+        hyp_labels = [h['labels'] for r in results for h in r['hypotheses']]
+        hyp_texts = [h['plaintext'] for r in results for h in r['hypotheses']]
+        ref_labels = [truth for truth, n in zip(truths, sizes) for _ in range(n)]
+        ref_texts = [text for text, n in zip(originals, sizes) for _ in range(n)]
+        ref_words, hyp_words = metrics.word_ids(ref_texts, hyp_texts)
+        counts = metrics.error_counts(hyp_labels + hyp_words, ref_labels + ref_words, self.device)
+        return (counts[:len(hyp_labels), 0].astype(np.int64),
+                counts[len(hyp_labels):, 0].astype(np.int64), np.array(sizes, dtype=np.int64))
+
+    def nbest_many(self, batches, top_paths, beam_width=None, scorer=None, rescorer=None):
+        """`nbest_fn` of several batches in ONE pair of launches, as `decode_many` decodes them:
+        ``batches`` is a list of (logits, seq_len, originals or None); returns one `nbest_fn`
+        result per batch, identical to calling it batch by batch."""
+        if not batches:
+            return []
+        steps = max(int(logits.shape[0]) for logits, _, _ in batches)
+        total = sum(int(logits.shape[1]) for logits, _, _ in batches)
+        classes = int(batches[0][0].shape[2])
+        joint = torch.zeros((steps, total, classes), dtype=torch.float32, device=self.device)
+        lengths = torch.empty(total, dtype=torch.int32, device=self.device)
+        start = 0
+        for logits, seq_len, _ in batches:
+            stop = start + int(logits.shape[1])
+            joint[:logits.shape[0], start:stop] = logits
+            lengths[start:stop] = seq_len
+            start = stop
+        flat = self._nbest_launch(joint, lengths, top_paths, beam_width, scorer, rescorer)
+        results, start = [], 0
+        for logits, _, originals in batches:
+            stop = start + int(logits.shape[1])
+            results.append(self._with_originals(flat[start:stop], originals))
             start = stop
         return results
 

@@ -472,6 +472,47 @@ FLAGS.define('int', 'lm_order', 5, 'lm.py: order of the n-gram to build.')
 FLAGS.define('string', 'lm_corpus_csv', '', 'lm.py: path;label;length manifest whose transcripts '
              'the n-gram is built from.')
 
+# N-best lists and second-pass rescoring (no counterpart in the reference): evaluate.py and
+# predict.py read the --nbest best hypotheses off the final beam, score each exactly
+# (hip.ctc_score) and, with --rescore_lm_path, re-rank them under that model.
+NBEST_RANGE = (0, 1024)
+
+
+def _finite(name):
+    def check(value):
+        if not np.isfinite(value):
+            raise ValueError('--{} must be finite (got {}).'.format(name, value))
+    return check
+
+
+FLAGS.define('int', 'nbest', 0, 'Hypotheses kept per utterance (0: off; at most --beam_width).',
+             _int_range('nbest', *NBEST_RANGE))
+FLAGS.define('string', 'rescore_lm_path', '', 'Character n-gram (.npz of ctc_asr_amd.lm) that '
+             're-ranks the n-best list; needs --nbest >= 2.  Empty: no rescoring.')
+FLAGS.define('float', 'rescore_lm_weight', 1.0, 'Weight of the rescoring model.',
+             _finite('rescore_lm_weight'))
+FLAGS.define('float', 'rescore_lm_bonus', 0.0, 'Added per label by the rescoring model.',
+             _finite('rescore_lm_bonus'))
+
+
+def _validate_nbest(flags):
+    if flags.nbest > flags.beam_width:
+        raise ValueError('--nbest {} is above --beam_width {}.'.format(flags.nbest,
+                                                                       flags.beam_width))
+    if flags.nbest < 2 and (flags.rescore_lm_path or flags.rescore_lm_weight != 1.0 or
+                            flags.rescore_lm_bonus != 0.0):
+        raise ValueError('--rescore_lm_path / _weight / _bonus need --nbest >= 2 (got {}).'
+                         .format(flags.nbest))
+    if flags.rescore_lm_path:
+        from ctc_asr_amd import lm
+        try:
+            lm.load(flags.rescore_lm_path, flags.num_classes)
+        except OSError as error:
+            raise ValueError('--rescore_lm_path: {}'.format(error))
+
+
+FLAGS.define_validator(_validate_nbest)
+
 # ####### Constants (asr/params.py:138-155). #########
 NP_FLOAT = np.float32
 

@@ -143,6 +143,62 @@ int ctcasr_ctc_beam_decode_lm(const float *logits, const int32_t *seq_len, int T
                               int32_t *out, int32_t *out_len, float *logp, void *workspace,
                               size_t workspace_bytes, ctcasr_stream_t stream);
 
+/* N-best lists from both searches: tf.nn.ctc_beam_search_decoder's top_paths (the reference
+ * passes 1).  One entry point; lm_next == NULL is the plain search, otherwise the four lm_*
+ * arguments are those of ctcasr_ctc_beam_decode_lm.  The search is the same search: only what is
+ * read off the final beam differs.  Arguments, limits and status codes are those of
+ * ctcasr_ctc_beam_decode_lm, plus top_paths N with 1 <= N <= beam_width (else
+ * CTCASR_ERR_BAD_ARGUMENT); logp and n_paths may not be NULL.
+ *   out      int32 [B, N, T]: the label path of rank k of utterance b, zero-padded
+ *   out_len  int32 [B, N]
+ *   logp     float [B, N]: the beam's total of that leaf (with a model: the fused total, lm_final
+ *            included).  Under norm_mode 0 it is no log-probability, and under either mode it
+ *            sums only the alignments that survived pruning: ctcasr_ctc_score gives the exact one.
+ *   n_paths  int32 [B] = min(N, leaves in the final beam)
+ * Order (pinned): total descending; among equal totals the older tree node first (-0 and +0 are
+ * equal).  It is the order of the search's branch sort, and rank 0 is the leaf that
+ * ctcasr_ctc_beam_decode / _lm return: out[b][0], out_len[b][0], logp[b][0] are theirs bit for
+ * bit.  No two ranks of a row hold the same path (a path is one tree node).
+ * Ranks k >= n_paths[b]: out_len 0, logp -inf, out 0.  A row whose prefix-tree pool ran out has
+ * n_paths = -1 and every out_len of the row -1 (its out / logp are not to be used).  Every
+ * output element is written.  Workspace: ctcasr_ctc_beam_nbest_workspace_bytes(T, B, C,
+ * beam_width), the size of the plain search's.
+ * Left out on purpose: merge_repeated, lattice output. */
+size_t ctcasr_ctc_beam_nbest_workspace_bytes(int T, int B, int C, int beam_width);
+int ctcasr_ctc_beam_decode_nbest(const float *logits, const int32_t *seq_len, int T, int B, int C,
+                                 int blank, int beam_width, int norm_mode, int top_paths,
+                                 const int32_t *lm_next, const float *lm_score,
+                                 const float *lm_final, int lm_states, int32_t *out,
+                                 int32_t *out_len, float *logp, int32_t *n_paths, void *workspace,
+                                 size_t workspace_bytes, ctcasr_stream_t stream);
+
+/* ---- K14: CTC scoring ---------------------------------------------------------------------------
+ * Forward-only CTC log-likelihood of H label sequences against B utterances (no counterpart in
+ * the reference): the exact ln p(y | x) of every hypothesis of an n-best list, for posteriors
+ * and second-pass rescoring.  One wavefront per hypothesis, the lattice in registers; nothing
+ * but one float per hypothesis is written.
+ *   logits, seq_len  as ctcasr_ctc_loss_fwd_bwd takes them; blank is any id in [0, C)
+ *   labels         int32, the concatenated label ids of all H hypotheses
+ *   label_offsets  int32 [H + 1]
+ *   utt            int32 [H]: the utterance of hypothesis h, in [0, B); any order, and an
+ *                  utterance may have no hypothesis at all
+ *   score          [H]  ln p(labels_h | x_utt[h]) = -loss of ctcasr_ctc_loss_fwd_bwd; an empty
+ *                  label is legal (the sum of the blank's log-softmax over the frames; 0 for
+ *                  seq_len 0)
+ *   status         int32 [H]: 0 ok; 1 seq_len < L + adjacent repeats; 2 a label id out of range
+ *                  or the blank, utt[h] outside [0, B), seq_len > T or < 0, or a row longer than
+ *                  max_label_len (or of negative length).  Non-zero: score -inf.
+ * A non-finite logit in the first seq_len frames of the utterance makes the score NaN, as it
+ * makes the loss; frames beyond seq_len are never read.  A hypothesis' score does not depend on
+ * the others of the call or on their order, bit for bit.  Every output element is written.
+ * 2 * max_label_len + 1 <= 1152, C <= 64 (else CTCASR_ERR_UNSUPPORTED).  Workspace:
+ * ctcasr_ctc_score_workspace_bytes(T, B, C, H, max_label_len) (the log-softmax table). */
+size_t ctcasr_ctc_score_workspace_bytes(int T, int B, int C, int H, int max_label_len);
+int ctcasr_ctc_score(const float *logits, const int32_t *seq_len, int T, int B, int C, int blank,
+                     const int32_t *labels, const int32_t *label_offsets, const int32_t *utt,
+                     int H, int max_label_len, float *score, int32_t *status, void *workspace,
+                     size_t workspace_bytes, ctcasr_stream_t stream);
+
 /* ---- K11: CTC forced alignment ----------------------------------------------------------------
  * The Viterbi (max-sum) form of K9's alpha recursion: the single best alignment of each
  * utterance's label to its frames (no counterpart in the reference).  Inputs and status codes
