@@ -32,6 +32,9 @@ REVERB_CHUNK = 2048             # ctcasr_reverb: output samples of a row per wor
 REVERB_TAP_BLOCK = 32           # ... taps per round of its inner loop (a remainder 8 at a time),
 REVERB_TAP_ALIGN = 8            # ... what a response's length and offset are multiples of,
 REVERB_MAX_TAPS = 8192          # ... and the longest response it serves
+VAD_HOP = 160                   # ctcasr_vad_energy: samples per hop (the feature step),
+VAD_LEVELS = 160                # ... bins of its level histogram,
+VAD_CHUNK = 40960               # ... and samples per workgroup
 CELL_IDS = {'rnn_relu': 0, 'rnn_tanh': 1, 'lstm': 2, 'gru': 3}
 CELL_GATES = {'rnn_relu': 1, 'rnn_tanh': 1, 'lstm': 4, 'gru': 3}
 
@@ -157,6 +160,8 @@ SIGNATURES = {
                          [_c_int] * 3 + [_c_p] * 5 + [_c_sz, _c_p]),
     'ctcasr_reverb': (_c_int, [_c_p, _c_p, _c_int, _c_int] + [_c_p] * 4 + [_c_int, _c_u64, _c_int] +
                       [_c_p] * 3),
+    'ctcasr_vad_energy': (_c_int, [_c_p, _c_i64, _c_p, _c_p, _c_p]),
+    'ctcasr_gather_segments': (_c_int, [_c_p, _c_i64, _c_p, _c_p, _c_int, _c_int] + [_c_p] * 3),
     'ctcasr_adam_step': (_c_int, [_c_p] * 4 + [_c_i64] + [_c_f] * 4 + [_c_i64, _c_f, _c_p, _c_p]),
     'ctcasr_adam_step_clipped': (_c_int, [_c_p] * 4 + [_c_i64] + [_c_f] * 4 +
                                  [_c_i64, _c_f, _c_p, _c_p, _c_p]),
@@ -1930,3 +1935,62 @@ def reverb(pcm, num_samples, taps, rir_offsets, rir_delay, rir_scale, seed, prob
         int(seed) & 0xFFFFFFFFFFFFFFFF, int(prob_permille), out_ptr, draws_ptr, _stream()),
         'reverb')
     return out
+
+
+def _recording(what, pcm):
+    if pcm.dim() != 1:
+        raise CtcAsrError('{}: pcm must be one recording, int16[n] (got {} dimensions).'
+                          .format(what, pcm.dim()))
+    if pcm.numel() < 1:
+        raise CtcAsrError('{}: the recording is empty.'.format(what))
+    return _dev(pcm, torch.int16, 'pcm')
+
+
+@_on_tensor_device
+def vad_energy(pcm):
+    """One pass over a recording, ``pcm`` int16[n] on the device (a slice of a tensor will do: any
+    2-byte aligned start) -> (energy int64[F], hist int32[VAD_LEVELS]), F = ceil(n / VAD_HOP):
+    the sum of squares of every hop of VAD_HOP samples as an exact integer, and how many hops have
+    each level (`vad.level`).  Both device tensors; integer sums, so every run gives the same bits."""
+    ptr = _recording('vad_energy', pcm)
+    n = pcm.numel()
+    energy = torch.empty((n + VAD_HOP - 1) // VAD_HOP, dtype=torch.int64, device=pcm.device)
+    hist = torch.empty(VAD_LEVELS, dtype=torch.int32, device=pcm.device)    # (counts fit: F < 2^31)
+    _check(load().ctcasr_vad_energy(ptr, n, _dev(energy, torch.int64, 'energy'),
+                                    _dev(hist, torch.int32, 'hist'), _stream()), 'vad_energy')
+    return energy, hist
+
+
+@_on_tensor_device
+def gather_segments(pcm, seg_start, seg_len, max_samples=None, out=None, num_samples=None):
+    """Pieces of a recording as the rows of a batch: ``pcm`` int16[n], ``seg_start`` int64[B] and
+    ``seg_len`` int32[B] in samples (all device tensors) -> (int16[B, max_samples], int32[B]), the
+    input of `features`.  Row b holds ``pcm[seg_start[b] : seg_start[b] + len]`` and zeros behind
+    it, ``len`` being ``seg_len[b]`` clipped to the recording and to ``max_samples``; a row that
+    starts outside the recording or has no length is all zero with count 0.  ``max_samples``:
+    columns of the result; None reads the largest ``seg_len`` back (one synchronisation)."""
+    batch = seg_start.numel()
+    if batch < 1:
+        raise CtcAsrError('gather_segments: no segments.')
+    _batch_of('gather_segments', 'seg_len', seg_len, batch)
+    ptr = _recording('gather_segments', pcm)
+    start_ptr = _dev(seg_start, torch.int64, 'seg_start')
+    len_ptr = _dev(seg_len, torch.int32, 'seg_len')
+    if max_samples is None:
+        max_samples = int(seg_len.max())
+    max_samples = max(int(max_samples), 1)
+    if out is None:
+        out = torch.empty((batch, max_samples), dtype=torch.int16, device=pcm.device)
+    if num_samples is None:
+        num_samples = torch.empty(batch, dtype=torch.int32, device=pcm.device)
+    _expect_numel('gather_segments', 'out', out, batch * max_samples)
+    _expect_numel('gather_segments', 'num_samples', num_samples, batch)
+    for name, tensor in (('seg_start', seg_start), ('seg_len', seg_len), ('out', out),
+                         ('num_samples', num_samples)):
+        if tensor.device != pcm.device:
+            raise CtcAsrError('gather_segments: {} lives on {}, pcm on {}.'
+                              .format(name, tensor.device, pcm.device))
+    _check(load().ctcasr_gather_segments(
+        ptr, pcm.numel(), start_ptr, len_ptr, batch, max_samples, _dev(out, torch.int16, 'out'),
+        _dev(num_samples, torch.int32, 'num_samples'), _stream()), 'gather_segments')
+    return out, num_samples

@@ -513,6 +513,33 @@ def _validate_nbest(flags):
 
 FLAGS.define_validator(_validate_nbest)
 
+# Long recordings (no counterpart in the reference): `python -m ctc_asr_amd.transcribe` cuts
+# --input at its pauses (ctc_asr_amd/vad.py), batches the pieces and puts their texts back on one
+# time axis.  Nothing else reads these flags.
+FLAGS.define('int', 'vad_margin_db', 9,
+             'Speech threshold, in whole dB above the noise floor of the recording (0..60).',
+             _int_range('vad_margin_db', 0, 60))
+FLAGS.define('int', 'vad_floor_permille', 100,
+             'Percentile of the 10 ms energies taken as the noise floor, in thousandths (1..999).',
+             _int_range('vad_floor_permille', 1, 999))
+FLAGS.define('int', 'vad_min_rms', 16,
+             'Absolute lower bound of the speech threshold, as an rms of 16-bit samples '
+             '(0..32767).', _int_range('vad_min_rms', 0, 32767))
+FLAGS.define('int', 'vad_rms', 0,
+             'Fixed speech threshold as an rms (1..32767); 0: derived from the recording.',
+             _int_range('vad_rms', 0, 32767))
+FLAGS.define('int', 'vad_pad_ms', 200,
+             'Padding around speech, and half the pause that is bridged, in ms (0..2000; whole '
+             '10 ms steps, rounded down).', _int_range('vad_pad_ms', 0, 2000))
+FLAGS.define('int', 'vad_min_speech_ms', 50,
+             'Speech above the threshold a piece must hold, in ms (10..2000).',
+             _int_range('vad_min_speech_ms', 10, 2000))
+FLAGS.define('int', 'max_segment_seconds', 15,
+             'Longest piece; longer speech is cut at its quietest 10 ms (1..30).',
+             _int_range('max_segment_seconds', 1, 30))
+FLAGS.define('string', 'transcribe_output', '',
+             'transcribe.py: JSON-lines file, one line per piece; empty: print.')
+
 # ####### Constants (asr/params.py:138-155). #########
 NP_FLOAT = np.float32
 

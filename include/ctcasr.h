@@ -1000,6 +1000,51 @@ int ctcasr_reverb(const int16_t *pcm, const int32_t *num_samples, int B, int max
                   const float *rir_scale, int num_rirs, uint64_t seed, int prob_permille,
                   int16_t *out, int32_t *draws, ctcasr_stream_t stream);
 
+/* ---- K18: speech segmentation of a long recording --------------------------------------------
+ * No counterpart in the reference (it transcribes one utterance).  The device side of
+ * ctc_asr_amd/vad.py and ctc_asr_amd/transcribe.py: one pass over the PCM of a whole recording,
+ * and the gather that turns the pieces the host chose into a batch for ctcasr_features.
+ *
+ * ctcasr_vad_energy: energy and level histogram per hop of CTCASR_VAD_HOP = 160 samples (the
+ * feature step).  F = ceil(n / 160) hops.
+ *   pcm      int16 [n], any 2-byte aligned address (a slice of a tensor).  A 16-byte aligned base
+ *            is read 16 bytes per lane; any other base through aligned loads and shifts, with
+ *            the same results.  Only read.
+ *   energy   int64 [F]: energy[f] = sum of x * x over samples [160 f, min(160 f + 160, n)), exact;
+ *            at most 160 * 2^30.  The last hop may be partial.
+ *   hist     uint32 [CTCASR_VAD_LEVELS]: zeroed by the call on the stream, then hist[level(e)]
+ *            counts the hops of energy e.  Integer atomics: no grid, order or run changes it.
+ * level(e), a quarter-octave scale in integers: with b the bit length of e (0 for e = 0),
+ *   level(e) = e                                   for b <= 2
+ *            = 4 (b - 2) + ((e >> (b - 3)) & 3)    otherwise;
+ * monotone, 145 at the largest energy, one level at most a factor 1.25 in energy.  Its lower edge:
+ *   level_floor(L) = L                                   for L < 4
+ *                  = (4 + (L & 3)) << ((L >> 2) - 1)     otherwise.
+ * A workgroup serves CTCASR_VAD_CHUNK samples (256 hops).
+ * Errors, before any launch: a null pointer or n < 1: CTCASR_ERR_BAD_ARGUMENT; n > 2^31 - 1:
+ * CTCASR_ERR_UNSUPPORTED.
+ *
+ * ctcasr_gather_segments: row b of out = pcm[seg_start[b] : seg_start[b] + len), zeros behind it.
+ *   pcm          int16 [n], any 2-byte aligned address.  Only read.
+ *   seg_start    DEVICE int64 [B], in samples; any value (multiples of 8 from an aligned base keep
+ *                the reads at one 16-byte load per lane)
+ *   seg_len      DEVICE int32 [B]
+ *   out          int16 [B, max_samples], the input layout of ctcasr_features; every column written
+ *   num_samples  int32 [B]: len, that is seg_len[b] clipped so that the range stays inside [0, n)
+ *                and len <= max_samples.  A row with seg_start[b] < 0, seg_start[b] >= n or
+ *                seg_len[b] < 1 is all zero with count 0.
+ * Rows may repeat and come in any order.  One launch.
+ * Errors, before any launch: a null pointer, B < 1 or max_samples < 1: CTCASR_ERR_BAD_ARGUMENT;
+ * max_samples > 2^30 or more than INT_MAX workgroups: CTCASR_ERR_UNSUPPORTED. */
+#define CTCASR_VAD_HOP 160
+#define CTCASR_VAD_LEVELS 160
+#define CTCASR_VAD_CHUNK 40960
+int ctcasr_vad_energy(const int16_t *pcm, int64_t n, int64_t *energy, uint32_t *hist,
+                      ctcasr_stream_t stream);
+int ctcasr_gather_segments(const int16_t *pcm, int64_t n, const int64_t *seg_start,
+                           const int32_t *seg_len, int B, int max_samples, int16_t *out,
+                           int32_t *num_samples, ctcasr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
