@@ -34,12 +34,6 @@
 #define PRNN_GROUPS 8
 #endif
 #define PRNN_SPIN_LIMIT (1u << 22)
-// timing probe only (wrong results): the reduce-scatter backward kernel issues this many of its 4
-// K quarters of MFMAs - 1 prices the form's exchange pattern with the matrix work of the fp16 pipe
-// (96 short MFMAs where the fp32 kernel issues 256 long ones), profiles/r05_rnn_bwd_reduce_scatter_f16.md
-#ifndef PRNN_PROBE_RS_Q
-#define PRNN_PROBE_RS_Q 4
-#endif
 #ifndef PRNN_PROBE_HALF_LOADS
 #define PRNN_PROBE_HALF_LOADS 0
 #endif
@@ -108,15 +102,15 @@ struct PArgs {
     int chain0;            // first batch tile of this launch
     int s_lo, s_hi;        // backward: this launch runs steps s_hi-1 ... s_lo (a whole pass: 0, T)
     float *carry;          // backward, LSTM: dc [2, B, H] handed from one launch to the next
-    float *rs;             // backward, reduce-scatter form: the exchange ring (prnn_rs_ring_bytes);
-                           // fp16 form: the inverse scales (prnn_b16_scale_bytes)
+    float *rs;             // backward, fp16 form: the inverse scales (prnn_b16_scale_bytes)
     unsigned *colmax;      // backward, fp16 form (optional): [2][G * H] maxima of |dxw| (bit patterns);
                            // reduced with fmaxf, which skips a NaN: max over nan_to_num(|dxw|, 0),
                            // what colmax_kernel (split.hip) finds in a pass over dxw (inf stays inf)
     int prof;              // record phase timings of workgroup 0
     unsigned ticket;       // != 0: post it once every workgroup of this launch is running
     int xcd_split;         // fp16 kernels: direction 0 on XCDs 0 - 3, direction 1 on XCDs 4 - 7
-    unsigned *kp;          // backward, K-pair form: KPairWords + the hand-off slots (prnn_kp_bytes)
+    unsigned *kp;          // backward, K-pair form (H = 2048): KPairWords + the hand-off slots
+                           // (prnn_w16_kp_bytes)
 };
 
 __device__ __forceinline__ float4 ldg4(const float *p) {
@@ -201,40 +195,6 @@ __device__ __forceinline__ void chain_barrier(ChainSync *cs, unsigned &epoch, in
     while (lds_load(&cs->bar) < epoch) __builtin_amdgcn_s_sleep(1);
     asm volatile("" ::: "memory");          // LDS reads below stay below
 }
-
-// Two chains: the MFMA phases of the two batch tiles take turns.  Left alone the chains fall into
-// lockstep - both in their MFMA phase at once, each at half rate, then both in their exchange
-// phase with the matrix pipe idle (reduce-scatter backward: 11.9 us per step = 2 x 3.9 of MFMA
-// + 4 of exchange).  With the pipe handed over explicitly one chain's exchange round trip
-// (loads, gate math, drain, barrier) runs under the other chain's MFMAs.
-struct MfmaTurn {           // in LDS, one per workgroup
-    unsigned lock;          // 1 while a chain is in its MFMA phase
-    unsigned done[2];       // waves of chain c that have finished MFMA phases (cumulative)
-    unsigned pad;
-};
-__device__ __forceinline__ void mfma_turn_take(MfmaTurn *turn) {      // one thread per chain
-    unsigned expected = 0u;
-    while (!__hip_atomic_compare_exchange_strong(&turn->lock, &expected, 1u, __ATOMIC_RELAXED,
-                                                 __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) {
-        expected = 0u;
-        __builtin_amdgcn_s_sleep(1);
-    }
-}
-// every wave of the chain, after its MFMAs: the last of the four hands the pipe over
-__device__ __forceinline__ void mfma_turn_give(MfmaTurn *turn, int lchain, int lane) {
-    if (lane == 0) {
-        const unsigned before = __hip_atomic_fetch_add(&turn->done[lchain], 1u, __ATOMIC_RELAXED,
-                                                       __HIP_MEMORY_SCOPE_WORKGROUP);
-        if ((before & 3u) == 3u)
-            __hip_atomic_store(&turn->lock, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    }
-}
-#ifndef PRNN_RS_LOCK
-#define PRNN_RS_LOCK 1
-#endif
-#ifndef PRNN_TURN_PRIO
-#define PRNN_TURN_PRIO 2            // s_setprio of the waves that hold the matrix pipe
-#endif
 
 // Direction-wide barrier, split in two so that the arrival is posted as soon as a step's
 // published stores are out and the wait happens at the top of the next step.
@@ -418,8 +378,8 @@ __global__ void __launch_bounds__(PRNN_THREADS * CHAINS) prnn_fwd_kernel(PArgs p
     // each one's exchange round trip hides behind the other's MFMAs.
     // (Round 3: both tiles as two chains in every workgroup of a WHOLE-chip launch - 128
     // workgroups per direction, 8 units each, 1.7 us of MFMA per chain and step - with the
-    // chains' MFMA phases taking turns through an LDS lock (MfmaTurn, as in the reduce-scatter
-    // backward kernel): 7.2 us per step with the lock holder at s_setprio 2, 6.96 at equal
+    // chains' MFMA phases taking turns through an LDS lock (one holder at a time; the code is
+    // gone): 7.2 us per step with the lock holder at s_setprio 2, 6.96 at equal
     // priority, 7.14 without the lock, against 6.1 for one group of workgroups per tile - the
     // other chain's gate math (VALU, transcendentals) crawls while a chain issues MFMAs on the
     // same SIMD: reduce + gates + publish 0.56 -> 1.85 - 2.46 us.  Not kept.)
@@ -1155,7 +1115,7 @@ __global__ void __launch_bounds__(PRNN_THREADS * CHAINS) prnn_bwd_kernel(PArgs p
                         (size_t)CHAINS * RED_FLOATS * sizeof(float)) + lchain;
     unsigned bar_epoch = 0, arrivals = 0;
     // Two chains: a static priority for chain 0 (left alone they start in lockstep).  Round 3
-    // tried explicit MFMA turns here as well (the LDS lock of the reduce-scatter kernel around
+    // tried explicit MFMA turns here as well (an LDS lock, one holder at a time, around
     // the loads + MFMA loop): 11.8 us per step against 11.0 without at B = 32 (GRU 10.3 / 9.7,
     // RNN-2048 11.45 / 11.40) - with the matrix pipe to itself a chain's loads + MFMA phase still
     // takes 5.8 us: this kernel is bound by the A-operand loads in flight (two batches of 16 KB
@@ -1513,255 +1473,6 @@ __global__ void __launch_bounds__(PRNN_THREADS * CHAINS) prnn_bwd_kernel(PArgs p
         for (int i = 0; i < 4; ++i) p.sync->prof[4 + i] = pt[i];
 }
 
-
-// ---------------------------------------------------------------------------------------------
-// backward, REDUCE-SCATTER form (LSTM, H = 1024, 64 workgroups per direction = half the chip).
-//
-// prnn_bwd_kernel is an all-gather: a workgroup owns 16 output units j of dh = dgates x R and so
-// needs the dgates of ALL 4H gate columns of every row - 256 KB per 16-row tile and step, pulled
-// through a per-CU load path that delivers ~50 GB/s on freshly written data (10 of the 12.7 us
-// per step at B = 32).  Here the product is cut along K instead: a workgroup
-// keeps the 64 ROWS of R that belong to the gate columns of its OWN 16 units (the same 256 KB of
-// weights, as w_hh_t[j][g*H + u0 .. u0+16) fragments), so its A operand - the dgates it has just
-// computed, [16 rows x 64] - never leaves the CU (4 KB through LDS).  It multiplies them into a
-// partial dh [16 x 1024] = 64 MFMA tiles and writes tile jt (1 KB, accumulator layout, lane
-// linear) to the slot [consumer jt][producer = this workgroup] of an exchange ring.  After ONE
-// direction barrier the workgroup that owns units 16 jt .. 16 jt + 15 reads its 64 contiguous KB
-// (one tile from each producer; wave w sums producers 16 w .. 16 w + 15 in registers, the four
-// wave sums meet in LDS) and has dh for its units.  Per step and 16-row tile a CU reads 64 KB
-// and writes 64 KB instead of reading 256 KB; nothing is read twice, so there is nothing for an
-// L2 to share and the loads bypass it (sc1), which in turn allows the buffer to be a RING of two
-// steps (33.5 MB for both directions and tiles - it lives in the Infinity Cache) instead of one
-// block per time step: a workgroup that has passed the barrier of step s knows that every
-// workgroup has finished reading the partials of step s + 1, whose slot step s - 1 overwrites.
-// Same MFMA work as prnn_bwd_kernel (K = 64 per tile: 16 MFMAs, two tiles interleaved on two
-// accumulators), same barrier, one round trip per step.
-//
-// LDS: B fragments [4 waves][32 slots][64 lanes] float4 (128 KB; the other 32 slots of a wave
-// live in 128 registers), then per chain: partial sums [4][16][17], the A operand [16][68] and
-// the chain's sync words.
-// ---------------------------------------------------------------------------------------------
-#define PRNN_RS_H 1024
-#define PRNN_RS_NWG 64                  // workgroups per direction = consumers = producers
-#define PRNN_RS_QL 32                   // B-fragment slots per wave in LDS (of 64)
-#define PRNN_RS_APITCH 68               // floats per row of the A operand in LDS
-#define PRNN_RS_TILE_BYTES 1024u        // one 16 x 16 fp32 accumulator tile
-#define PRNN_RS_SLOT_BYTES ((size_t)2 * PRNN_MAX_CHAINS * PRNN_RS_NWG * PRNN_RS_NWG * 1024)
-size_t prnn_rs_ring_bytes() { return 2 * PRNN_RS_SLOT_BYTES; }
-
-template <int CHAINS>
-__global__ void __launch_bounds__(PRNN_THREADS * CHAINS) prnn_bwd_rs_kernel(PArgs p) {
-    constexpr int H = PRNN_RS_H, GH = 4 * H, NWG = PRNN_RS_NWG, QL = PRNN_RS_QL;
-    constexpr int JW = H / 16 / 4;          // j tiles (consumers) per wave: 16
-    constexpr int QS = JW * 4;              // B-fragment slots per wave: (tile, gate) pairs
-    constexpr int REGW = QS - QL;
-    constexpr int RED_FLOATS = 4 * 16 * 17, A_FLOATS = 16 * PRNN_RS_APITCH;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    resident_signal(p.sync, p.ticket);
-    if (launch_poisoned(p.sync)) return;
-    float4 *frag = reinterpret_cast<float4 *>(smem);
-    const int chain =
-        CHAINS > 1 ? __builtin_amdgcn_readfirstlane((int)threadIdx.x / PRNN_THREADS)
-                   : p.chain0 + (int)blockIdx.x / (p.ndir * p.nwg);
-    const int lchain = CHAINS > 1 ? chain : 0;
-    const int row0 = chain * 16;
-    char *chain_mem = smem + (size_t)4 * QL * 64 * sizeof(float4) +
-                      (size_t)lchain * ((RED_FLOATS + A_FLOATS) * sizeof(float) + 16);
-    float *red = reinterpret_cast<float *>(chain_mem);
-    float *dgs = red + RED_FLOATS;
-    ChainSync *cs = reinterpret_cast<ChainSync *>(dgs + A_FLOATS);
-    MfmaTurn *turn = reinterpret_cast<MfmaTurn *>(
-        smem + (size_t)4 * QL * 64 * sizeof(float4) +
-        (size_t)CHAINS * ((RED_FLOATS + A_FLOATS) * sizeof(float) + 16));
-    unsigned bar_epoch = 0, arrivals = 0;
-    if constexpr (CHAINS > 1 && !PRNN_RS_LOCK) {
-        if (chain == 0) __builtin_amdgcn_s_setprio(PRNN_CHAIN0_PRIO);
-    }
-    const int tid = threadIdx.x % PRNN_THREADS, lane = tid & 63, wave = tid >> 6;
-    const int wg = blockIdx.x % (p.ndir * p.nwg);
-    const int dir = p.dir0 + wg / p.nwg, slice = wg % p.nwg;
-    const int group_size = p.nwg / PRNN_GROUPS, grp = slice / group_size;
-    const int B = p.B, T = p.T, BS = p.BS;
-    const int u0 = slice * 16;
-    if (CHAINS > 1 && threadIdx.x == 0) *turn = MfmaTurn{0u, {0u, 0u}, 0u};
-
-    // ---- this workgroup's 64 rows of R, as B fragments: slot (tile jl, gate q) of wave w holds
-    // R[n = q H + u0 + 4 (lane >> 4) + r][j = 16 (16 w + jl) + (lane & 15)], r = 0..3 - four
-    // consecutive floats of a row of w_hh_t
-    float4 wreg[REGW];
-    {
-        const float *wrow = p.w + ((size_t)dir * H + (size_t)wave * JW * 16 + (lane & 15)) * GH +
-                            u0 + 4 * (lane >> 4);
-        auto slot = [&](int sl) -> float4 {
-            return ldg4(wrow + (size_t)(sl >> 2) * 16 * GH + (size_t)(sl & 3) * H);
-        };
-        for (int sl = lchain; sl < QL; sl += CHAINS) frag[(wave * QL + sl) * 64 + lane] = slot(sl);
-#pragma unroll
-        for (int sl = 0; sl < REGW; ++sl) wreg[sl] = slot(QL + sl);
-    }
-    if (CHAINS > 1 && tid == 0) *cs = ChainSync{0u, 0u, 0u, 0u};
-    __syncthreads();
-
-    // exchange ring [slot = step & 1][dir][tile chain][consumer][producer][1 KB]
-    const __amdgpu_buffer_rsrc_t x_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-        p.rs, 0, (int)(2 * PRNN_RS_SLOT_BYTES), 0x00020000);
-    const unsigned x_dc = (unsigned)((dir * PRNN_MAX_CHAINS + chain) * NWG * NWG) *
-                          PRNN_RS_TILE_BYTES;
-    // read: my 64 tiles are contiguous, wave w takes producers 16 w .. 16 w + 15
-    const unsigned x_rd = x_dc + (unsigned)(slice * NWG + wave * 16) * PRNN_RS_TILE_BYTES +
-                          (unsigned)lane * 16u;
-    // write: tile of consumer 16 w + jl lands in that consumer's block at producer = slice
-    const unsigned x_wr = x_dc + (unsigned)((wave * JW) * NWG + slice) * PRNN_RS_TILE_BYTES +
-                          (unsigned)lane * 16u;
-
-    // ---- the item of this thread: row tid >> 4 of the tile, unit tid & 15 ----------------------
-    const int ib = tid >> 4, iu = tid & 15;
-    const int brow = row0 + ib, unit = u0 + iu;
-    const int steps = brow < B ? row_steps(p.seq_len, brow, T) : 0;
-    float dc_state = 0.f, dbs[4] = {0.f, 0.f, 0.f, 0.f};
-    if (p.s_hi < T && brow < B) dc_state = p.carry[((size_t)dir * B + brow) * H + unit];
-
-    unsigned long long pt[5] = {0, 0, 0, 0, 0};
-    const bool prof = p.prof && tid == 0;       // thread 0 of every chain of every workgroup
-    for (int s = p.s_hi - 1; s >= p.s_lo; --s) {
-        unsigned long long c0 = prof ? wall_clock64() : 0;
-        // everything the cell derivative needs except dh_rec: requested before the barrier
-        const bool running = s < steps;
-        const int t = running ? row_time(dir, s, steps) : 0;
-        float dyv = 0.f, gi = 0.f, gf = 0.f, gg = 0.f, go = 0.f, cv = 0.f, cpv = 0.f;
-        if (running) {
-            dyv = p.dy[((size_t)t * BS + brow) * 2 * H + dir * H + unit];
-            const float *gr = p.gates + (((size_t)t * BS + brow) * 2 + dir) * 4 * H + unit;
-            gi = gr[0]; gf = gr[H]; gg = gr[2 * H]; go = gr[3 * H];
-            cv = p.cells[(((size_t)t * BS + brow) * 2 + dir) * H + unit];
-            if (s > 0)
-                cpv = p.cells[(((size_t)row_time(dir, s - 1, steps) * BS + brow) * 2 + dir) * H +
-                              unit];
-        }
-
-        float dh = dyv;
-        if (s < T - 1) {
-            // partial dh of step s + 1 from every workgroup of this direction (the first step
-            // of a continued pass reads what the previous launch left: nothing to wait for)
-            if (s < p.s_hi - 1) {
-                dir_wait<CHAINS>(p.sync, cs, dir, chain, group_size, (unsigned)(p.s_hi - 2 - s),
-                                 tid);
-                if (s == p.s_lo && tid == 0) counters_done(p.sync, dir, chain, p.nwg);
-            }
-            if (prof) { unsigned long long c = wall_clock64(); pt[0] += c - c0; c0 = c; }
-            const unsigned rd = x_rd + (unsigned)((s + 1) & 1) * (unsigned)PRNN_RS_SLOT_BYTES;
-            float4 v[16];
-#pragma unroll
-            for (int i = 0; i < 16; ++i)
-                v[i] = load16_sc1<16>(x_rsrc, rd + (unsigned)i * PRNN_RS_TILE_BYTES);
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                v[i].x += v[i + 8].x; v[i].y += v[i + 8].y;
-                v[i].z += v[i + 8].z; v[i].w += v[i + 8].w;
-            }
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                v[i].x += v[i + 4].x; v[i].y += v[i + 4].y;
-                v[i].z += v[i + 4].z; v[i].w += v[i + 4].w;
-            }
-            const float4 sum = make_float4((v[0].x + v[2].x) + (v[1].x + v[3].x),
-                                           (v[0].y + v[2].y) + (v[1].y + v[3].y),
-                                           (v[0].z + v[2].z) + (v[1].z + v[3].z),
-                                           (v[0].w + v[2].w) + (v[1].w + v[3].w));
-            // accumulator layout: lane holds rows 4 (lane >> 4) + r of column lane & 15
-            float *rw = red + (wave * 16 + 4 * (lane >> 4)) * 17 + (lane & 15);
-            rw[0] = sum.x; rw[17] = sum.y; rw[34] = sum.z; rw[51] = sum.w;
-            if constexpr (CHAINS == 1) __syncthreads();
-            else chain_barrier(cs, bar_epoch, lane);
-            dh += (red[(0 * 16 + ib) * 17 + iu] + red[(1 * 16 + ib) * 17 + iu]) +
-                  (red[(2 * 16 + ib) * 17 + iu] + red[(3 * 16 + ib) * 17 + iu]);
-        }
-        if (prof) { unsigned long long c = wall_clock64(); pt[1] += c - c0; c0 = c; }
-
-        float dg[4] = {0.f, 0.f, 0.f, 0.f};
-        if (running) {
-            const float tc = tanhf_(cv);
-            const float dc = dc_state + dh * go * (1.f - tc * tc);
-            dg[0] = dc * gg * gi * (1.f - gi);
-            dg[1] = dc * cpv * gf * (1.f - gf);
-            dg[2] = dc * gi * (1.f - gg * gg);
-            dg[3] = dh * tc * go * (1.f - go);
-            dc_state = dc * gf;
-#pragma unroll
-            for (int g = 0; g < 4; ++g) dbs[g] += dg[g];
-        }
-        // dh of step s - 1 needs these dgates x R; step 0 has nobody to hand them to
-        if (s > 0) {
-#pragma unroll
-            for (int g = 0; g < 4; ++g) dgs[ib * PRNN_RS_APITCH + g * 16 + iu] = dg[g];
-            if constexpr (CHAINS == 1) {
-                __syncthreads();
-            } else {
-                if (PRNN_RS_LOCK && tid == 0) mfma_turn_take(turn);   // the matrix pipe is ours
-                chain_barrier(cs, bar_epoch, lane);
-                if (PRNN_RS_LOCK) __builtin_amdgcn_s_setprio(PRNN_TURN_PRIO);
-            }
-            float4 a[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-                a[q] = *reinterpret_cast<const float4 *>(
-                    dgs + (lane & 15) * PRNN_RS_APITCH + 16 * q + 4 * (lane >> 4));
-            if (prof) { unsigned long long c = wall_clock64(); pt[2] += c - c0; c0 = c; }
-            auto bfrag = [&](int sl) -> float4 {        // compile-time slot after unrolling
-                return sl < QL ? frag[(wave * QL + sl) * 64 + lane] : wreg[sl - QL];
-            };
-            const unsigned wr = x_wr + (unsigned)(s & 1) * (unsigned)PRNN_RS_SLOT_BYTES;
-#pragma unroll
-            for (int jp = 0; jp < JW; jp += 2) {
-                f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int q = 0; q < PRNN_PROBE_RS_Q; ++q)
-                    mma4x2(acc0, acc1, a[q], bfrag(jp * 4 + q), a[q], bfrag((jp + 1) * 4 + q));
-                store16_sc1(x_rsrc, wr + (unsigned)(jp * NWG) * PRNN_RS_TILE_BYTES,
-                            acc0[0], acc0[1], acc0[2], acc0[3]);
-                store16_sc1(x_rsrc, wr + (unsigned)((jp + 1) * NWG) * PRNN_RS_TILE_BYTES,
-                            acc1[0], acc1[1], acc1[2], acc1[3]);
-            }
-            if constexpr (CHAINS > 1 && PRNN_RS_LOCK) {
-                __builtin_amdgcn_s_setprio(0);
-                mfma_turn_give(turn, lchain, lane);
-            }
-            if (prof) { unsigned long long c = wall_clock64(); pt[3] += c - c0; c0 = c; }
-            if (s > p.s_lo) dir_arrive<CHAINS>(p.sync, cs, dir, chain, grp, tid, arrivals);
-        }
-        // dxw in its GEMM layout: read after the launch only
-        if (running) {
-            float *dx = p.dxw + (((size_t)t * BS + brow) * 2 + dir) * GH + unit;
-            dx[0] = dg[0]; dx[H] = dg[1]; dx[2 * H] = dg[2]; dx[3 * H] = dg[3];
-        }
-        if (prof) { unsigned long long c = wall_clock64(); pt[4] += c - c0; c0 = c; }
-    }
-    if (p.s_lo > 0 && brow < B) p.carry[((size_t)dir * B + brow) * H + unit] = dc_state;
-    if (p.dbias) {              // bias gradients: sum over the tile's 16 rows, then one atomic
-        if constexpr (CHAINS == 1) __syncthreads();
-        else chain_barrier(cs, bar_epoch, lane);
-#pragma unroll
-        for (int g = 0; g < 4; ++g) dgs[ib * PRNN_RS_APITCH + g * 16 + iu] = dbs[g];
-        if constexpr (CHAINS == 1) __syncthreads();
-        else chain_barrier(cs, bar_epoch, lane);
-        if (tid < 64) {
-            float sum = 0.f;
-            for (int r = 0; r < 16; ++r) sum += dgs[r * PRNN_RS_APITCH + tid];
-            atomicAdd(p.dbias + ((size_t)dir * 4 + (tid >> 4)) * H + u0 + (tid & 15), sum);
-        }
-    }
-    if (prof) {
-        if (blockIdx.x == 0 && lchain == 0)
-            for (int i = 0; i < 5; ++i) p.sync->prof[4 + i] = pt[i];
-        // every (workgroup, chain): wait | partial loads + sum | gates + MFMA + publish | drain
-        const int slot = (int)(blockIdx.x * CHAINS + lchain) & 255;
-        p.sync->prof_all[slot][0] = pt[0];
-        p.sync->prof_all[slot][1] = pt[1];
-        p.sync->prof_all[slot][2] = pt[2] + pt[3];
-        p.sync->prof_all[slot][3] = pt[4];
-    }
-}
-
 // ---------------------------------------------------------------------------------------------
 // backward on the fp16 matrix pipe (round 4; LSTM, H = 1024, `flags` bit CTCASR_RNN_F16).
 //
@@ -1787,7 +1498,7 @@ __global__ void __launch_bounds__(PRNN_THREADS * CHAINS) prnn_bwd_rs_kernel(PArg
 // Exchange, in the bytes of prnn_bwd_kernel's: [step][dir][producer P][gate pair m][piece]
 // [k group][b][8 halves] - k group q of (P, m) = units 8 (q & 1) .. + 7 of gate 2 m + (q >> 1) -
 // so a lane's 16-byte load is the A-fragment register quadruple of a K = 32 MFMA; behind the
-// reduce-scatter ring the inverse scales [step][dir][producer][32 rows].  B-fragment slot
+// steps' blocks the inverse scales [step][dir][producer][32 rows].  B-fragment slot
 // (P * 2 + m) * 2 + piece, the first QL of a wave in LDS.
 // Also accumulates, besides the bias gradients, the per-column maxima of |dxw| over the launch's
 // steps (`colmax`, bit patterns, atomicMax): what ctcasr_colmax_scale would find in a pass over
@@ -1827,6 +1538,8 @@ __device__ __forceinline__ void lstm_cell_bwd_pinned(float dh, float &dc_state, 
     dg[3] = ((dh * tc) * go) * (1.f - go);
     dc_state = dc * gf;
 }
+#define PRNN_B16_H 1024
+#define PRNN_B16_NWG 64                 // workgroups per direction = consumers = producers
 #define PRNN_B16_SCALE_ROWS 32          // rows per producer in the inverse-scale blocks
 #ifndef PRNN_B16_D1
 #define PRNN_B16_D1 14                  // ring depth, one tile on 4 waves
@@ -1838,12 +1551,12 @@ __device__ __forceinline__ void lstm_cell_bwd_pinned(float dh, float &dc_state, 
 #define PRNN_B16_D2 5                   // ring depth, two tiles
 #endif
 __host__ __device__ inline size_t prnn_b16_scale_bytes(int T) {
-    return (size_t)(T + 1) * 2 * (PRNN_RS_H / 16) * PRNN_B16_SCALE_ROWS * sizeof(float);
+    return (size_t)(T + 1) * 2 * (PRNN_B16_H / 16) * PRNN_B16_SCALE_ROWS * sizeof(float);
 }
 
 // MT batch tiles of 16 rows behind one barrier, NW waves (the K axis - 64 producers - is split
 // over them), a ring of D producers' A granules in flight per wave.
-// Range of the gradients (this kernel, prnn_bwd16s / 16k / 16w and prnn_relu16_kernel alike): the
+// Range of the gradients (this kernel, prnn_bwd16s / 16w and prnn_relu16_kernel alike): the
 // scale of a (producer, row) is the power of two 2^(13 - exponent of its maximum), clamped to +-100
 // binades, 1 for an all-zero row - so a maximum between roughly 2^-100 and 2^100 is published with
 // fp32-grade pieces, and dxw(2^k dy) = 2^k dxw(dy) bit for bit while every maximum stays inside.
@@ -1859,7 +1572,7 @@ __host__ __device__ inline size_t prnn_b16_scale_bytes(int T) {
 //                   one item per thread
 template <int MT, int NW, int D>
 __global__ void __launch_bounds__(64 * NW) prnn_bwd16_kernel(PArgs p) {
-    constexpr int H = PRNN_RS_H, GH = 4 * H;
+    constexpr int H = PRNN_B16_H, GH = 4 * H;
     constexpr int NTH = 64 * NW;            // threads
     constexpr int NPW = H / 16 / NW;        // producers per wave (the K split)
     constexpr int QS = NPW * 4;             // B-fragment slots per wave: (producer, half, piece)
@@ -2278,7 +1991,7 @@ __global__ void __launch_bounds__(64 * NW) prnn_bwd16_kernel(PArgs p) {
 #endif
 template <int DD, int JW, int JP, int JA, bool PROF = false>
 __global__ void __launch_bounds__(PRNN_THREADS) prnn_bwd16s_kernel(PArgs p) {
-    constexpr int H = PRNN_RS_H, GH = 4 * H;
+    constexpr int H = PRNN_B16_H, GH = 4 * H;
     constexpr int NW = 4, NTH = 256, NPW = 16, QS = NPW * 4, QL = QS / 2, REGW = QS - QL;
     constexpr int RED_FLOATS = NW * 16 * 17, IVL = 4 * NPW;
     static_assert(DD % 2 == 0 && DD <= NPW && (NPW % DD == 0 || JW == NPW / 2 - 1),
@@ -2731,582 +2444,6 @@ __global__ void __launch_bounds__(PRNN_THREADS) prnn_bwd16s_kernel(PArgs p) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// prnn_bwd16k_kernel (round 6): the staggered kernel with the K axis split over
-// PAIRS of workgroups (a 2-D decomposition of dh = dgates x W_hh^T: 32 x 2 instead of 64 x 1).
-//
-// prnn_bwd16s_kernel is bound by what a CU pulls per phase: every workgroup needs the dgates of ALL
-// 4H gate columns of a tile's rows (256 KB per tile and step; its phase timers say 5.5 of 7.5 us
-// per step is waiting for those bytes, in two exposed round trips of 8 producers each).  Here the
-// workgroups {slice, slice ^ PBIT} - the two sit on ONE XCD - share 32 hidden units: each holds ONE
-// K half (32 producers) of the weights of all 32 units (the same 256 KB: 8 producers x 2 N tiles
-// per wave, half in LDS, half in registers), reads only that half's blocks (128 KB per tile and
-// step, ALL of a wave's 8 producers in flight at once: one round trip), multiplies them into TWO
-// partial tiles [16 rows x 16 units] and hands the partner the tile of the partner's units:
-// 1 KB per tile and step, through the XCD's L2.
-//
-// The hand-off is data-tagged - no flag, no drain: every 4-byte word carries the parity of the
-// slot's write count in its lowest significand bit (the word is a partial sum of products that
-// are good to 22 bits; the bit, cleared again by the receiver, costs < 2^-23 of the partner's half
-// of dh - and the result does not depend on the count).  The count at the start
-// of a launch is kept in the workspace (KPairWords.total, advanced by the launch's last workgroup
-// to leave), so a slot's current content never looks like the next one.  The receiver cannot use
-// vector loads: vmcnt is one in-order queue, and at that point the next phase's 39 loads are in
-// flight in front of anything it could issue - it polls with SCALAR loads (s_load_dwordx16 glc:
-// lgkmcnt; measured: coherent with another CU's stores through L2, tools/pair_handoff) and spreads
-// the 64 words over its lanes (v_writelane).  One hop: 0.6 - 0.7 us against 1.2 with a flag.
-//
-// Everything a workgroup PUBLISHES (exchange blocks, inverse scales, dxw, column maxima, bias
-// gradients) is the staggered kernel's: dgrad16 / wgrad16 read it unchanged.  The sums differ in
-// their order (own K half + partner's K half instead of four K quarters), so results agree with
-// prnn_bwd16s_kernel to rounding, not bit for bit; step ranges of THIS kernel are bit-identical to
-// one launch.
-// ---------------------------------------------------------------------------------------------
-#ifndef PRNN_B16K_JW
-#define PRNN_B16K_JW 3                  // pair (of 4) at which the next phase's loads start
-#endif
-#ifndef PRNN_B16K_JP
-#define PRNN_B16K_JP 2                  // pair at which the poll loads for them are issued
-#endif
-#ifndef PRNN_B16K_JA
-#define PRNN_B16K_JA 1                  // pair at which the phase before posts its arrival
-#endif
-#ifndef PRNN_B16K_SC1
-#define PRNN_B16K_SC1 0                 // hand-off stores write-through (1) or plain (0: one L2)
-#endif
-#ifndef PRNN_B16K_PROBE
-#define PRNN_B16K_PROBE 0               // timing probes (wrong results): 1 = nobody waits for the partner
-#endif
-#ifndef PRNN_B16K_SLEEP
-#define PRNN_B16K_SLEEP 1               // s_sleep between two looks at the partner's slot
-#endif
-struct KPairWords {
-    unsigned total;         // hand-offs every slot has seen before this launch (parity = tag base)
-    unsigned pad0[15];
-    unsigned done;          // workgroups of the launch that have left
-    unsigned pad1[47];
-};
-__host__ __device__ inline size_t prnn_kp_bytes() {
-    // header, then [dir][slice][tile][256] words written by the slice's partner
-    return sizeof(KPairWords) + (size_t)2 * PRNN_RS_NWG * 2 * 256 * sizeof(unsigned);
-}
-typedef int i32x16 __attribute__((ext_vector_type(16)));
-
-template <int JW, int JP, int JA, bool PROF = false>
-__global__ void __launch_bounds__(PRNN_THREADS) prnn_bwd16k_kernel(PArgs p) {
-    constexpr int H = PRNN_RS_H, GH = 4 * H;
-    constexpr int NW = 4, NTH = 256, NPW = 8, DD = NPW;
-    constexpr int QS = NPW * 4 * 2, QL = QS / 2, REGW = QS - QL;    // slot = ((P 2 + m) 2 + piece) 2 + n
-    constexpr int RED_FLOATS = NW * 16 * 17, IVL = 4 * NPW;
-    static_assert(JW < NPW / 2 && JP <= JW && JA <= JP, "pipeline points");
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    resident_signal(p.sync, p.ticket);
-    if (launch_poisoned(p.sync)) return;
-    u32x4 *frag = reinterpret_cast<u32x4 *>(smem);
-    float *red = reinterpret_cast<float *>(smem + (size_t)NW * QL * 64 * sizeof(u32x4));   // [2 tiles][2 n]
-    float4 *invs = reinterpret_cast<float4 *>(red + 4 * RED_FLOATS);       // [2 tiles][NW][IVL]
-    float *wave_top = reinterpret_cast<float *>(invs + 2 * NW * IVL);
-    unsigned *arrived = reinterpret_cast<unsigned *>(wave_top + 4);        // [2 tiles]
-
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wg = blockIdx.x % (p.ndir * p.nwg);
-    const bool split = p.xcd_split && p.ndir == 2;
-    const int dir = p.dir0 + (split ? (wg & 7) >> 2 : wg / p.nwg);
-    const int slice = split ? (wg >> 3) * 4 + (wg & 3) : wg % p.nwg;
-    // workgroup b runs on XCD b % 8: slices that differ in this bit share an XCD
-    const int pbit = split ? 4 : 8;
-    const int partner = slice ^ pbit, kh = (slice & pbit) ? 1 : 0;
-    const int group_size = p.nwg / PRNN_GROUPS, grp = slice / group_size;
-    const int B = p.B, T = p.T, BS = p.BS;
-    const int u0 = slice * 16;
-    const int pb = 32 * kh + NPW * wave;       // this wave's first producer
-    if (tid < 2) arrived[tid] = 0u;
-    KPairWords *kpw = reinterpret_cast<KPairWords *>(p.kp);
-    unsigned *kp_slots = p.kp + sizeof(KPairWords) / sizeof(unsigned);
-    const unsigned kp_base = (unsigned)__builtin_amdgcn_readfirstlane((int)__hip_atomic_load(
-        &kpw->total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-
-    // ---- weights: the K half `kh` of R^T for this workgroup's 16 units (n = 0) and the partner's
-    // (n = 1) as scaled fp16 pieces, fragments as in prnn_bwd16_kernel ---------------------------
-    float w_scale;
-    {
-        float m = 0.f;
-#pragma unroll
-        for (int n = 0; n < 2; ++n) {
-            const float *wrow = p.w + ((size_t)dir * H + (n ? partner : slice) * 16 + (tid & 15)) * GH +
-                                512 * kh;
-            for (int g = 0; g < 4; ++g)
-                for (int x = (tid >> 4) * 4; x < 512; x += NTH / 16 * 4) {
-                    const float4 v = ldg4(wrow + (size_t)g * H + x);
-                    m = fmaxf(fmaxf(m, fmaxf(fabsf(v.x), fabsf(v.y))), fmaxf(fabsf(v.z), fabsf(v.w)));
-                }
-        }
-        m = wave_max(m);
-        if (lane == 0) wave_top[wave] = m;
-        __syncthreads();
-        m = fmaxf(fmaxf(wave_top[0], wave_top[1]), fmaxf(wave_top[2], wave_top[3]));
-        const unsigned bits = __float_as_uint(m);
-        const int e = (int)((bits >> 23) & 0xFF) - 127;
-        const int se = bits == 0u ? 0 : min(max(14 - e, -60), 60);
-        w_scale = __uint_as_float((unsigned)(se + 127) << 23);
-    }
-    const float out_scale = 1.0f / w_scale;
-    u32x4 wreg[REGW];
-    {
-        auto pieces = [&](int pm, int n, u32x4 &first, u32x4 &second) {
-            const float *wcol = p.w + ((size_t)dir * H + (n ? partner : slice) * 16 + (lane & 15)) * GH +
-                                16 * (pb + (pm >> 1)) + 8 * (pm & 1) + 2 * (lane >> 4);
-            unsigned q[8];
-#pragma unroll
-            for (int e = 0; e < 8; ++e)
-                q[e] = f16_pieces(wcol[(size_t)(e & 3) * H + (e >> 2)] * w_scale);
-            first = (u32x4){(q[0] & 0xFFFFu) | (q[1] << 16), (q[2] & 0xFFFFu) | (q[3] << 16),
-                            (q[4] & 0xFFFFu) | (q[5] << 16), (q[6] & 0xFFFFu) | (q[7] << 16)};
-            second = (u32x4){(q[0] >> 16) | (q[1] & 0xFFFF0000u), (q[2] >> 16) | (q[3] & 0xFFFF0000u),
-                             (q[4] >> 16) | (q[5] & 0xFFFF0000u), (q[6] >> 16) | (q[7] & 0xFFFF0000u)};
-        };
-        for (int pm = 0; pm < QL / 4; ++pm)
-            for (int n = 0; n < 2; ++n) {
-                u32x4 first, second;
-                pieces(pm, n, first, second);
-                frag[(wave * QL + (pm * 2 + 0) * 2 + n) * 64 + lane] = first;
-                frag[(wave * QL + (pm * 2 + 1) * 2 + n) * 64 + lane] = second;
-            }
-#pragma unroll
-        for (int pm = 0; pm < REGW / 4; ++pm)
-#pragma unroll
-            for (int n = 0; n < 2; ++n)
-                pieces(QL / 4 + pm, n, wreg[(pm * 2 + 0) * 2 + n], wreg[(pm * 2 + 1) * 2 + n]);
-    }
-    __syncthreads();
-
-    const __amdgpu_buffer_rsrc_t x_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-        p.xchg, 0, (int)((size_t)(T + 1) * 2 * B * GH * sizeof(float)), 0x00020000);
-    const size_t x_step = (size_t)2 * B * GH;
-    const size_t x_base = x_step;
-    const __amdgpu_buffer_rsrc_t s_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-        p.rs, 0, (int)prnn_b16_scale_bytes(T), 0x00020000);
-    constexpr unsigned S_STEP = 2u * (H / 16) * PRNN_B16_SCALE_ROWS * sizeof(float);
-    const int rnum = 0x7FFFFFFF;
-    const __amdgpu_buffer_rsrc_t dy_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float *>(p.dy), 0, rnum, 0x00020000);
-    const __amdgpu_buffer_rsrc_t g_rsrc = __builtin_amdgcn_make_buffer_rsrc(p.gates, 0, rnum, 0x00020000);
-    const __amdgpu_buffer_rsrc_t c_rsrc = __builtin_amdgcn_make_buffer_rsrc(p.cells, 0, rnum, 0x00020000);
-    const __amdgpu_buffer_rsrc_t dx_rsrc = __builtin_amdgcn_make_buffer_rsrc(p.dxw, 0, rnum, 0x00020000);
-    const __amdgpu_buffer_rsrc_t kp_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-        kp_slots, 0, (int)(prnn_kp_bytes() - sizeof(KPairWords)), 0x00020000);
-
-    // ---- one item per thread and tile (row x * 16 + (tid >> 4), unit tid & 15), no per-row
-    // lengths: as in prnn_bwd16s_kernel -------------------------------------------------------------
-    const int unit = u0 + (tid & 15);
-    float dc_state[2], dbs[2][4], cmx[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int x = 0; x < 2; ++x) {
-        const int brow = x * 16 + (tid >> 4);
-        dc_state[x] = 0.f;
-        if (p.s_hi < T && brow < B) dc_state[x] = p.carry[((size_t)dir * B + brow) * H + unit];
-#pragma unroll
-        for (int g = 0; g < 4; ++g) dbs[x][g] = 0.f;
-    }
-    auto ldf2 = [](__amdgpu_buffer_rsrc_t r, unsigned lane_off, unsigned uni_off) -> float {
-        return __uint_as_float(
-            __builtin_amdgcn_raw_buffer_load_b32(r, (int)lane_off, (int)uni_off, 0));
-    };
-    float c_dy[2], c_gi[2], c_gf[2], c_gg[2], c_go[2], c_cv[2], c_cp[2];
-    auto cell_prefetch = [&](int s, int x) {
-        int tq = tid;
-        asm volatile("" : "+v"(tq));
-        s = max(s, 0);                    // (behind the launch's last phase: any valid address)
-        const unsigned t = (unsigned)(dir == 0 ? s : T - 1 - s);
-        const unsigned tp = s > 0 ? (unsigned)(dir == 0 ? s - 1 : T - s) : t;
-        const unsigned unit = (unsigned)(u0 + (tq & 15));
-        const unsigned e = (unsigned)((min(x * 16 + (tq >> 4), B - 1) * 2 + dir) * H) + unit;
-        const unsigned slab = t * (unsigned)BS * 2u * H * 4u;               // bytes of [BS, 2, H] rows
-        c_dy[x] = ldf2(dy_rsrc, e * 4u, slab);
-        const unsigned ge = (e * 4u - 3u * unit) * 4u;
-        c_gi[x] = ldf2(g_rsrc, ge, slab * 4u);
-        c_gf[x] = ldf2(g_rsrc, ge + H * 4u, slab * 4u);
-        c_gg[x] = ldf2(g_rsrc, ge + 2 * H * 4u, slab * 4u);
-        c_go[x] = ldf2(g_rsrc, ge + 3 * H * 4u, slab * 4u);
-        c_cv[x] = ldf2(c_rsrc, e * 4u, slab);
-        // (step 0 has no cell state before it: the value is dropped where it is USED - a select
-        // here waits for this load, the youngest of the phase, and with it for the whole ring)
-        c_cp[x] = ldf2(c_rsrc, e * 4u, tp * (unsigned)BS * 2u * H * 4u);
-    };
-
-    unsigned ablock[2];                   // scalar: byte offset of (step, dir) in the exchange buffer
-    float4 iv_next;
-    auto lane_aoff = [&](int x) -> unsigned {
-        const int row = min(x * 16 + (lane & 15), B - 1);
-        return (unsigned)(((size_t)(lane >> 4) * B * 4 + (size_t)row * 4) * sizeof(float));
-    };
-    auto tile_addresses = [&](int s, int x) {
-        ablock[x] = (unsigned)(((s + 1 < T ? x_base + (size_t)(s + 1) * x_step : 0) +
-                                (size_t)dir * B * GH) * sizeof(float));
-        iv_next = load16_sc1<16>(s_rsrc, (unsigned)(s + 1) * S_STEP +
-                                         (unsigned)(((dir * (H / 16) + pb + ((lane >> 2) & (NPW - 1))) *
-                                                     PRNN_B16_SCALE_ROWS + x * 16 + 4 * (lane & 3)) *
-                                                    sizeof(float)));
-    };
-    u32x4 a[DD][4];                       // ALL of the wave's 8 producers of a tile in flight
-    const unsigned wave_off = (unsigned)(pb * 4) * (unsigned)B * 64u;
-    auto issue = [&](int x, int P) {
-        unsigned bstride = (unsigned)B * 64u;
-        asm volatile("" : "+s"(bstride));
-        const unsigned lo = lane_aoff(x);
-#pragma unroll
-        for (int g = 0; g < 4; ++g)       // g = half * 2 + piece
-            a[P][g] = load16u(x_rsrc, lo, ablock[x] + wave_off + (unsigned)(P * 4 + g) * bstride);
-    };
-    auto poll = [&](int x) -> unsigned {  // lanes 0 .. 7: the arrival counter of group `lane`
-        unsigned v = 0xFFFFFFFFu;
-        if (lane < PRNN_GROUPS)
-            v = __hip_atomic_load(&p.sync->group_cnt[dir][x][lane][0], __ATOMIC_RELAXED,
-                                  __HIP_MEMORY_SCOPE_AGENT);
-        return v;
-    };
-    auto bfrag = [&](int sl) -> u32x4 {   // compile-time slot after unrolling
-        return sl < QL ? frag[(wave * QL + sl) * 64 + lane] : wreg[sl - QL];
-    };
-
-    // phase timers (CTCASR_RNN_PROF, second instantiation): [0] marker wait, [1] poll wait, [2] the
-    // rest of the main loops, [3] reduce + cell derivative + publish, [5] waiting for the partner
-    unsigned long long pt[4] = {0, 0, 0, 0}, spins_total = 0, hop_total = 0;
-    unsigned long long t_issue = 0, first_wait = 0, first_lat = 0, all_lat = 0;   // (PROF) A operand
-    const bool profw = PROF && p.prof && blockIdx.x == 0 && wave == 0;
-    unsigned marker = 0u;
-
-    auto phase = [&](auto xc, int s, bool prev_arrives, bool has_next, bool next_waits) {
-        constexpr int X = decltype(xc)::value, XN = X ^ 1;
-        const int sn = X == 0 ? s : s - 1;                  // the next phase's step
-        f32x4 total[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
-        const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
-        unsigned pv = 0xFFFFFFFFu;
-        unsigned long long c0 = 0, waited = 0;
-        if constexpr (PROF) c0 = profw ? wall_clock64() : 0;
-#pragma unroll
-        for (int j = 0; j < NPW / 2; ++j) {
-            if constexpr (PROF) {
-                if (j == 0 && profw) {      // the first producer's granules: how long after their request
-                    const unsigned long long w0 = wall_clock64();
-                    asm volatile("" ::"v"(a[0][0]), "v"(a[0][3]) : "memory");
-                    const unsigned long long w1 = wall_clock64();
-                    first_wait += w1 - w0;
-                    first_lat += w1 - t_issue;
-                }
-            }
-            if (j == JA && prev_arrives) {
-                // the marker is back -> the publish stores issued in front of it are complete
-                unsigned long long w0 = 0;
-                if constexpr (PROF) w0 = profw ? wall_clock64() : 0;
-                asm volatile("" ::"v"(marker) : "memory");
-                if constexpr (PROF) {
-                    if (profw) {
-                        const unsigned long long w1 = wall_clock64(), d = w1 - w0;
-                        pt[0] += d; waited += d;
-                        all_lat += w1 - t_issue;
-                    }
-                }
-                if (lane == 0) {
-                    const unsigned before = __hip_atomic_fetch_add(
-                        &arrived[XN], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                    if ((before & 3u) == 3u)
-                        __hip_atomic_fetch_add(&p.sync->group_cnt[dir][XN][grp][0], 1u,
-                                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
-            }
-            if (j == JP && has_next && next_waits) pv = poll(XN);
-            const int P0 = 2 * j, P1 = 2 * j + 1;
-            f32x4 acc[2][2];              // [producer of the pair][n]
-#pragma unroll
-            for (int m = 0; m < 2; ++m) {
-                Frag16 w1[2][2], w2[2][2], d1[2], d2[2];
-#pragma unroll
-                for (int q = 0; q < 2; ++q) {
-                    const int pm = (P0 + q) * 2 + m;
-#pragma unroll
-                    for (int n = 0; n < 2; ++n) {
-                        w1[q][n].u = bfrag((pm * 2 + 0) * 2 + n);
-                        w2[q][n].u = bfrag((pm * 2 + 1) * 2 + n);
-                    }
-                    d1[q].u = a[P0 + q][2 * m];
-                    d2[q].u = a[P0 + q][2 * m + 1];
-                }
-#pragma unroll
-                for (int q = 0; q < 2; ++q)
-#pragma unroll
-                    for (int n = 0; n < 2; ++n)
-                        acc[q][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(
-                            d1[q].h, w1[q][n].h, m == 0 ? zero : acc[q][n], 0, 0, 0);
-#pragma unroll
-                for (int q = 0; q < 2; ++q)
-#pragma unroll
-                    for (int n = 0; n < 2; ++n)
-                        acc[q][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(
-                            d1[q].h, w2[q][n].h, acc[q][n], 0, 0, 0);
-#pragma unroll
-                for (int q = 0; q < 2; ++q)
-#pragma unroll
-                    for (int n = 0; n < 2; ++n)
-                        acc[q][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(
-                            d2[q].h, w1[q][n].h, acc[q][n], 0, 0, 0);
-            }
-            // the next phase's operands into the slots that came free, as soon as everybody has
-            // published them (unconditional, see prnn_bwd16s_kernel)
-            if (j >= JW) {
-                if (j == JW) {
-                    const unsigned target = (unsigned)group_size * (unsigned)(p.s_hi - 1 - sn);
-                    unsigned long long w1 = 0;
-                    if constexpr (PROF) {
-                        w1 = profw ? wall_clock64() : 0;
-                        asm volatile("" ::"v"(pv) : "memory");
-                        if (profw) { const unsigned long long d = wall_clock64() - w1; pt[1] += d; waited += d; }
-                        w1 = profw ? wall_clock64() : 0;
-                    }
-                    if (__builtin_expect(has_next && next_waits && !__all(pv >= target), 0)) {
-                        unsigned spins = 0;
-                        for (;;) {
-                            __builtin_amdgcn_s_sleep(PRNN_POLL_SLEEP);
-                            const unsigned again = poll(XN);
-                            if constexpr (PROF) spins_total += 1;
-                            if (__all(again >= target)) break;
-                            if (++spins > PRNN_SPIN_LIMIT ||
-                                ((spins & 1023u) == 0 &&
-                                 __hip_atomic_load(&p.sync->error, __ATOMIC_RELAXED,
-                                                   __HIP_MEMORY_SCOPE_AGENT))) {
-                                if (lane == 0)
-                                    __hip_atomic_store(&p.sync->error, 1u, __ATOMIC_RELAXED,
-                                                       __HIP_MEMORY_SCOPE_AGENT);
-                                break;
-                            }
-                        }
-                        if constexpr (PROF) {
-                            if (profw) { const unsigned long long d = wall_clock64() - w1; pt[1] += d; waited += d; }
-                        }
-                    }
-                    tile_addresses(sn, XN);
-                    if constexpr (PROF) t_issue = profw ? wall_clock64() : 0;
-#pragma unroll
-                    for (int q = 0; q <= P1; ++q) issue(XN, q);
-                    cell_prefetch(sn, XN);
-                } else {
-                    issue(XN, P0);
-                    issue(XN, P1);
-                }
-            }
-#pragma unroll
-            for (int q = 0; q < 2; ++q) {
-                const float4 ivq = invs[(X * NW + wave) * IVL + 4 * (P0 + q) + (lane >> 4)];
-#pragma unroll
-                for (int n = 0; n < 2; ++n) {
-                    total[n][0] += acc[q][n][0] * ivq.x;
-                    total[n][1] += acc[q][n][1] * ivq.y;
-                    total[n][2] += acc[q][n][2] * ivq.z;
-                    total[n][3] += acc[q][n][3] * ivq.w;
-                }
-            }
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        // ---- reduce over the waves' K shares; the partner's tile goes out, ours comes in ---------
-        if constexpr (PROF) {
-            asm volatile("" ::"v"(total[0][0]));
-            if (profw) { const unsigned long long c = wall_clock64(); pt[2] += c - c0 - waited; c0 = c; }
-        }
-        int tq = tid;
-        asm volatile("" : "+v"(tq));
-        const int lq = tq & 63, iu = tq & 15, unit = u0 + iu, ib = tq >> 4;
-        float *redx = red + X * 2 * RED_FLOATS;
-#pragma unroll
-        for (int n = 0; n < 2; ++n)
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-                redx[n * RED_FLOATS + (wave * 16 + 4 * (lq >> 4) + r) * 17 + (lq & 15)] =
-                    total[n][r] * out_scale;
-        __syncthreads();
-        const unsigned tag = (kp_base + (unsigned)(p.s_hi - s)) & 1u;
-        {
-            float theirs = redx[RED_FLOATS + ib * 17 + iu];
-#pragma unroll
-            for (int w = 1; w < NW; ++w) theirs += redx[RED_FLOATS + (w * 16 + ib) * 17 + iu];
-            const unsigned lo = (unsigned)tq * 4u;
-            const unsigned uo = (unsigned)(((dir * PRNN_RS_NWG + partner) * 2 + X) * 256) * 4u;
-            __builtin_amdgcn_raw_buffer_store_b32((__float_as_uint(theirs) & ~1u) | tag, kp_rsrc,
-                                                  (int)lo, (int)uo, PRNN_B16K_SC1 ? 16 : 0);
-        }
-        float rec = redx[ib * 17 + iu];
-#pragma unroll
-        for (int w = 1; w < NW; ++w) rec += redx[(w * 16 + ib) * 17 + iu];
-        {
-            // the partner's half of our tile: 64 words per wave, scalar loads past the scalar cache
-            const unsigned *rp = kp_slots + ((dir * PRNN_RS_NWG + slice) * 2 + X) * 256 + wave * 64;
-            unsigned long long h0 = 0;
-            if constexpr (PROF) h0 = profw ? wall_clock64() : 0;
-            unsigned rv = 0u, spins = 0;
-            for (;;) {
-                i32x16 r0, r1, r2, r3;
-                asm volatile("s_load_dwordx16 %0, %4, 0x0 glc\n\ts_load_dwordx16 %1, %4, 0x40 glc\n\t"
-                             "s_load_dwordx16 %2, %4, 0x80 glc\n\ts_load_dwordx16 %3, %4, 0xc0 glc\n\t"
-                             "s_waitcnt lgkmcnt(0)"
-                             : "=&s"(r0), "=&s"(r1), "=&s"(r2), "=&s"(r3) : "s"(rp) : "memory");
-#pragma unroll
-                for (int i = 0; i < 16; ++i) {
-                    asm volatile("v_writelane_b32 %0, %1, %2" : "+v"(rv) : "s"(r0[i]), "n"(i));
-                    asm volatile("v_writelane_b32 %0, %1, %2" : "+v"(rv) : "s"(r1[i]), "n"(i + 16));
-                    asm volatile("v_writelane_b32 %0, %1, %2" : "+v"(rv) : "s"(r2[i]), "n"(i + 32));
-                    asm volatile("v_writelane_b32 %0, %1, %2" : "+v"(rv) : "s"(r3[i]), "n"(i + 48));
-                }
-                if (PRNN_B16K_PROBE == 1 || __all((rv & 1u) == tag)) break;
-                if constexpr (PROF) spins_total += 1;
-                if (++spins > PRNN_SPIN_LIMIT ||
-                    ((spins & 1023u) == 0 &&
-                     __hip_atomic_load(&p.sync->error, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))) {
-                    if (lane == 0)
-                        __hip_atomic_store(&p.sync->error, 1u, __ATOMIC_RELAXED,
-                                           __HIP_MEMORY_SCOPE_AGENT);
-                    break;
-                }
-                __builtin_amdgcn_s_sleep(PRNN_B16K_SLEEP);
-            }
-            if constexpr (PROF) {
-                if (profw) hop_total += wall_clock64() - h0;
-            }
-            rec += __uint_as_float(rv & ~1u);     // (the tag bit dropped: the same value whatever the count)
-        }
-        // ---- cell derivative, publish: prnn_bwd16s_kernel's ---------------------------------------
-        {
-            const bool has = X * 16 + ib < B;
-            float dg[4] = {0.f, 0.f, 0.f, 0.f};
-            if (has)
-                lstm_cell_bwd_pinned(c_dy[X] + rec, dc_state[X], c_gi[X], c_gf[X], c_gg[X], c_go[X],
-                                     c_cv[X], s == 0 ? 0.f : c_cp[X], dg);
-            float mx = fmaxf(fmaxf(fabsf(dg[0]), fabsf(dg[1])), fmaxf(fabsf(dg[2]), fabsf(dg[3])));
-            mx = row16_max(mx);
-            const unsigned mbits = __float_as_uint(mx);
-            const int me = (int)((mbits >> 23) & 0xFF) - 127;
-            const int mse = mbits == 0u ? 0 : min(max(13 - me, -100), 100);
-            const float rscale = __uint_as_float((unsigned)(mse + 127) << 23);
-            const float rinv = __uint_as_float((unsigned)(127 - mse) << 23);
-            unsigned q[4];
-#pragma unroll
-            for (int g = 0; g < 4; ++g) q[g] = f16_pieces(dg[g] * rscale);
-            const bool odd = (tq & 1) != 0;
-            const unsigned f01 = (q[0] & 0xFFFFu) | (q[1] << 16), f23 = (q[2] & 0xFFFFu) | (q[3] << 16);
-            const unsigned s01 = (q[0] >> 16) | (q[1] & 0xFFFF0000u),
-                           s23 = (q[2] >> 16) | (q[3] & 0xFFFF0000u);
-            const unsigned give01 = odd ? f01 : s01, give23 = odd ? f23 : s23;
-            const unsigned got01 = dpp_u32<0xB1>(give01), got23 = dpp_u32<0xB1>(give23);
-            const u32x4 v = odd ? (u32x4){got01, got23, s01, s23} : (u32x4){f01, f23, got01, got23};
-            if (has) {
-                const unsigned lo = (unsigned)(
-                    ((size_t)((slice * 2 + (iu >> 3)) * 2 + (odd ? 1 : 0)) * B * 16 +
-                     (size_t)((iu >> 1) & 3) * B * 4 + (size_t)(X * 16 + ib) * 4) * sizeof(float));
-                const unsigned uo = (unsigned)((x_base + (size_t)s * x_step + (size_t)dir * B * GH) *
-                                               sizeof(float));
-                __builtin_amdgcn_raw_buffer_store_b128(v, x_rsrc, (int)lo, (int)uo, 16);
-            }
-            const float r0 = __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(rinv), 0));
-            const float r1 = __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(rinv), 16));
-            const float r2 = __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(rinv), 32));
-            const float r3 = __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(rinv), 48));
-            if (lq == 0)
-                store16_sc1(s_rsrc,
-                            (unsigned)s * S_STEP +
-                                (unsigned)(((dir * (H / 16) + slice) * PRNN_B16_SCALE_ROWS + X * 16 +
-                                            ib) * sizeof(float)),
-                            r0, r1, r2, r3);
-            if (has) {      // dxw in its GEMM layout: read after the launch only
-                const unsigned t = (unsigned)(dir == 0 ? s : T - 1 - s);
-                const unsigned lo = (unsigned)(((X * 16 + ib) * 2 + dir) * GH + unit) * 4u;
-                const unsigned uo = t * (unsigned)BS * 2u * GH * 4u;
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(dg[g]), dx_rsrc,
-                                                          (int)(lo + (unsigned)g * H * 4u), (int)uo, 0);
-                    dbs[X][g] += dg[g];
-                    cmx[g] = fmaxf(cmx[g], fabsf(dg[g]));
-                }
-            }
-        }
-        asm volatile("" ::: "memory");
-        marker = (unsigned)__builtin_amdgcn_raw_buffer_load_b32(x_rsrc, 0, 0, 0);
-        if (lane < IVL) invs[(XN * NW + wave) * IVL + lane] = iv_next;
-        __builtin_amdgcn_sched_barrier(0);
-        if constexpr (PROF) {
-            if (profw) pt[3] += wall_clock64() - c0;
-        }
-    };
-
-    {
-        const int s = p.s_hi - 1;
-        tile_addresses(s, 0);
-#pragma unroll
-        for (int q = 0; q < DD; ++q) issue(0, q);
-        cell_prefetch(s, 0);
-        if (lane < IVL) invs[(0 * NW + wave) * IVL + lane] = iv_next;
-    }
-    for (int s = p.s_hi - 1; s >= p.s_lo; --s) {
-        phase(std::integral_constant<int, 0>{}, s, s < p.s_hi - 1, true, s < p.s_hi - 1);
-        phase(std::integral_constant<int, 1>{}, s, s > p.s_lo, s > p.s_lo, true);
-    }
-    __syncthreads();        // every wave is through its last poll
-    if (tid == 0) {
-        if (p.s_hi - p.s_lo >= 2) {
-            counters_done(p.sync, dir, 0, p.nwg);
-            counters_done(p.sync, dir, 1, p.nwg);
-        }
-        // the last workgroup to leave advances the slots' write count (every workgroup read it at
-        // its start, and is through its last hand-off)
-        const unsigned before = __hip_atomic_fetch_add(&kpw->done, 1u, __ATOMIC_RELAXED,
-                                                       __HIP_MEMORY_SCOPE_AGENT);
-        if (before + 1 == (unsigned)(p.ndir * p.nwg)) {
-            __hip_atomic_store(&kpw->total, kp_base + (unsigned)(p.s_hi - p.s_lo), __ATOMIC_RELAXED,
-                               __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(&kpw->done, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    }
-    if constexpr (PROF) {
-        if (profw && lane == 0) {
-            for (int i = 0; i < 4; ++i) p.sync->prof[4 + i] = pt[i];
-            p.sync->prof[8] = spins_total;
-            p.sync->prof[9] = hop_total;
-            p.sync->prof[10] = first_wait;
-            p.sync->prof[11] = first_lat;
-            p.sync->prof[12] = all_lat;
-        }
-    }
-    if (p.s_lo > 0) {
-#pragma unroll
-        for (int x = 0; x < 2; ++x) {
-            const int brow = x * 16 + (tid >> 4);
-            if (brow < B) p.carry[((size_t)dir * B + brow) * H + unit] = dc_state[x];
-        }
-    }
-    if (p.dbias || p.colmax) {
-        float *sums = red, *tops = reinterpret_cast<float *>(frag);     // (the weights are done with)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            __syncthreads();
-#pragma unroll
-            for (int x = 0; x < 2; ++x) {
-                sums[tid + x * NTH] = dbs[x][g];
-                tops[tid + x * NTH] = cmx[g];
-            }
-            __syncthreads();
-            if (tid < 16) {
-                float sum = 0.f, top = 0.f;
-                for (int r = 0; r < 32; ++r) {
-                    sum += sums[r * 16 + tid];
-                    top = fmaxf(top, tops[r * 16 + tid]);
-                }
-                if (p.dbias) atomicAdd(p.dbias + ((size_t)dir * 4 + g) * H + u0 + tid, sum);
-                if (p.colmax)
-                    atomicMax(p.colmax + ((size_t)dir * 4 + g) * H + u0 + tid, __float_as_uint(top));
-            }
-        }
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
 // The same backward recurrence on the fp16 matrix pipe for the LSTM at H = 2048 (round 5; the
 // reference's best published models are 4 - 5 x BiLSTM-2048, testruns.md): ONE direction per launch
 // on 256 workgroups of 8 units - 8 x 8192 weights as two fp16 pieces = 256 KB per workgroup, half
@@ -3331,7 +2468,17 @@ __global__ void __launch_bounds__(PRNN_THREADS) prnn_bwd16k_kernel(PArgs p) {
 __host__ __device__ inline size_t prnn_w16_scale_bytes(int T) {
     return (size_t)(T + 1) * 2 * (PRNN_W16_H / 8) * PRNN_B16_SCALE_ROWS * sizeof(float);
 }
-// K split: one KPairWords per direction, then [dir][workgroup][sending member 0 .. 3][128 words]
+// K split: the words of a direction that last from launch to launch.  Every hand-off word carries
+// the parity of its slot's write count in its lowest significand bit; the count at the start of a
+// launch is kept here (advanced by the launch's last workgroup to leave), so a slot's current
+// content never looks like the next one.
+struct KPairWords {
+    unsigned total;         // hand-offs every slot has seen before this launch (parity = tag base)
+    unsigned pad0[15];
+    unsigned done;          // workgroups of the launch that have left
+    unsigned pad1[47];
+};
+// one KPairWords per direction, then [dir][workgroup][sending member 0 .. 3][128 words]
 __host__ __device__ inline size_t prnn_w16_kp_bytes() {
     return 2 * sizeof(KPairWords) + (size_t)2 * (PRNN_W16_H / 8) * 4 * 128 * sizeof(unsigned);
 }
@@ -3746,7 +2893,7 @@ __global__ void __launch_bounds__(PRNN_THREADS) prnn_bwd16w_kernel(PArgs p) {
             p.sync->prof_all[blockIdx.x & 255][i] = pt[i];
         }
     if constexpr (KP) {
-        // the last workgroup to leave advances the direction's write count (prnn_bwd16k_kernel)
+        // the last workgroup to leave advances the direction's write count (KPairWords)
         __syncthreads();
         if (tid == 0) {
             const unsigned before = __hip_atomic_fetch_add(&kpw->done, 1u, __ATOMIC_RELAXED,
@@ -4180,15 +3327,13 @@ extern "C" int ctcasr_set_option(const char *name, int value) {
 static size_t prnn_step_exchange_bytes(int T, int B, int H, int G) {
     return ctcasr_align_up((size_t)(T + 1) * 2 * B * G * H * sizeof(float), 256);
 }
-// the per-step blocks, then (LSTM, H = 1024) the ring of the reduce-scatter backward kernel
-// ... and the inverse scales of the fp16 backward kernel.  Everything here is written by a pass
+// the per-step blocks, then the inverse scales of the fp16 backward kernels.  Everything here is written by a pass
 // before that pass reads it - except the all-zero block in front of the steps (rnn_step.hip) - so
 // it may sit at offsets that move with T; the K-pair hand-off words, which last from launch to
 // launch, are not part of it (prnn_kp_region_bytes).
 size_t prnn_exchange_bytes(int T, int B, int H, int G) {
     return prnn_step_exchange_bytes(T, B, H, G) +
-           (G == 4 && H == PRNN_RS_H
-                ? prnn_rs_ring_bytes() + ctcasr_align_up(prnn_b16_scale_bytes(T), 256) : 0) +
+           (G == 4 && H == PRNN_B16_H ? ctcasr_align_up(prnn_b16_scale_bytes(T), 256) : 0) +
            (G == 4 && H == PRNN_W16_H ? ctcasr_align_up(prnn_w16_scale_bytes(T), 256) : 0) +
            (G == 1 && H == PRNN_R16_H ? prnn_r16_scale_bytes(T) : 0);
 }
@@ -4427,41 +3572,29 @@ int prnn_bwd(int cell, const float *dy, const float *y, const float *w_hh_t,
             }
         return CTCASR_OK;
     }
-    if (cell == CTCASR_CELL_LSTM && H == PRNN_RS_H && (flags & CTCASR_RNN_F16)) {
+    if (cell == CTCASR_CELL_LSTM && H == PRNN_B16_H && (flags & CTCASR_RNN_F16)) {
         // fp16 matrix pipe: 64 workgroups per direction, ONE chain of 4 waves; B > 16 on half of
         // the chip: both 16-row tiles in every workgroup (one barrier); on the whole chip: each
         // tile as its own group of workgroups
-        p.nwg = PRNN_RS_NWG;
+        p.nwg = PRNN_B16_NWG;
         p.colmax = colmax;
         p.rs = reinterpret_cast<float *>(reinterpret_cast<char *>(p.xchg) +
-                                         prnn_step_exchange_bytes(T, B, H, 4) +
-                                         prnn_rs_ring_bytes());
+                                         prnn_step_exchange_bytes(T, B, H, 4));
         auto lds = [](int tiles, int waves) {
             return (size_t)128 * 1024 + (size_t)waves * tiles * 16 * 17 * 4 +
                    (size_t)tiles * 256 * 16 + 64;      // (inverse scales: 4 float4 per producer)
         };
-        // The kernels that stagger the two tiles publish tile 1's rows of a step AFTER tile 0's
-        // rows of that step have been read: the two must not share a cache line, or the reader's
-        // L1 / L2 keeps tile 1's bytes as they were when the line came in for tile 0 (round 6,
-        // tools/r06_stale_probe.py: the K-pair kernel at B = 17 .. 20 read the pass before; the
-        // staggered kernel was never caught, but nothing but the volume of its other loads
-        // protects it).  A k group's rows are B x 16 bytes in the exchange buffer: tile 1 starts on
-        // a 128-byte line when B is a multiple of 8 - other batches keep the one-barrier kernel.
+        // The staggered kernel publishes tile 1's rows of a step AFTER tile 0's rows of that step
+        // have been read: the two must not share a cache line, or the reader's L1 / L2 keeps tile
+        // 1's bytes as they were when the line came in for tile 0 (round 6: a K-pair form of this
+        // kernel, since removed, read the pass before at B = 17 .. 20; the staggered kernel was
+        // never caught, but nothing but the volume of its other loads protects it).  A k group's
+        // rows are B x 16 bytes in the exchange buffer: tile 1 starts on a 128-byte line when B is
+        // a multiple of 8 - other batches keep the one-barrier kernel.
         // (The inverse scales of a producer share ONE line for both tiles at every B: the
-        // staggered kernels read them past the caches.)
+        // staggered kernel reads them past the caches.)
+        // CTCASR_RNN_KPAIR has no form at this H and is ignored.
         const bool tiles_apart = B % 8 == 0;
-        if (mt == 2 && half_chip && (flags & CTCASR_RNN_KPAIR) && !seq_len && tiles_apart) {
-            // K-pair form of the staggered kernel: weights 128 KB, partial tiles [2 tiles][2 n],
-            // inverse scales [2 tiles][4 waves][32] float4
-            p.kp = reinterpret_cast<unsigned *>(kp);
-            const size_t kp_lds = (size_t)128 * 1024 + (size_t)4 * 4 * 16 * 17 * 4 +
-                                  (size_t)2 * 4 * 32 * 16 + 64;
-            if (p.prof)
-                return launch_persistent(
-                    prnn_bwd16k_kernel<PRNN_B16K_JW, PRNN_B16K_JP, PRNN_B16K_JA, true>, p, kp_lds, s);
-            return launch_persistent(
-                prnn_bwd16k_kernel<PRNN_B16K_JW, PRNN_B16K_JP, PRNN_B16K_JA>, p, kp_lds, s);
-        }
         if (mt == 2 && half_chip && (flags & CTCASR_RNN_STAGGER) && !seq_len && tiles_apart) {
             if (p.prof)
                 return launch_persistent(
@@ -4474,16 +3607,6 @@ int prnn_bwd(int cell, const float *dy, const float *y, const float *w_hh_t,
         if (mt == 2 && half_chip)
             return launch_persistent(prnn_bwd16_kernel<2, PRNN_B16_NW2, PRNN_B16_D2>, p, lds(2, PRNN_B16_NW2), s, PRNN_B16_NW2 / 4);
         return launch_persistent(prnn_bwd16_kernel<1, 4, PRNN_B16_D1>, p, lds(1, 4), s, 1, mt);
-    }
-    if (cell == CTCASR_CELL_LSTM && H == PRNN_RS_H && (flags & CTCASR_RNN_REDUCE_SCATTER)) {
-        // reduce-scatter form: 64 workgroups per direction, two chains per workgroup for B > 16
-        p.nwg = PRNN_RS_NWG;
-        p.rs = reinterpret_cast<float *>(reinterpret_cast<char *>(p.xchg) +
-                                         prnn_step_exchange_bytes(T, B, H, 4));
-        const size_t per_chain = (size_t)(4 * 16 * 17 + 16 * PRNN_RS_APITCH) * 4 + 16;
-        const size_t lds = (size_t)4 * PRNN_RS_QL * 64 * 16 + 16;     // + MfmaTurn
-        if (mt == 2) return launch_persistent(prnn_bwd_rs_kernel<2>, p, lds + 2 * per_chain, s, 2);
-        return launch_persistent(prnn_bwd_rs_kernel<1>, p, lds + per_chain, s, 1);
     }
     if (cell == CTCASR_CELL_LSTM) {
         if (chains && !half_chip) {
@@ -4535,12 +3658,11 @@ int prnn_bwd(int cell, const float *dy, const float *y, const float *w_hh_t,
 // rnn_workspace_xchg_block0)
 int prnn_b16_published(const void *exchange, int T, int B, int H, const char **xchg,
                        const float **scales) {
-    if (!exchange || H != PRNN_RS_H || B < 1 || B > PRNN_BLOCK_ROWS || T < 1)
+    if (!exchange || H != PRNN_B16_H || B < 1 || B > PRNN_BLOCK_ROWS || T < 1)
         return CTCASR_ERR_BAD_ARGUMENT;
     const char *x = reinterpret_cast<const char *>(exchange);
     *xchg = x;
-    *scales = reinterpret_cast<const float *>(x + prnn_step_exchange_bytes(T, B, H, 4) +
-                                              prnn_rs_ring_bytes());
+    *scales = reinterpret_cast<const float *>(x + prnn_step_exchange_bytes(T, B, H, 4));
     return CTCASR_OK;
 }
 
@@ -4553,7 +3675,6 @@ size_t prnn_error_offset() { return offsetof(SyncWords, error); }
 // with the barrier words.
 size_t prnn_kp_region_bytes(int H, int G) {
     if (G == 4 && H == PRNN_W16_H) return prnn_w16_kp_bytes();
-    if (G == 4 && H == PRNN_RS_H) return prnn_kp_bytes();
     return 0;
 }
 
@@ -4567,12 +3688,11 @@ int prnn_resident_gate(void *sync, unsigned ticket, int max_wait_us, hipStream_t
 unsigned dgrad16_build_flags();     // (dgrad16.hip)
 extern "C" unsigned ctcasr_build_flags(void) {
     unsigned flags = dgrad16_build_flags();
-    if (PRNN_PROBE_HALF_LOADS || PRNN_PROBE_RS_Q != 4 || PRNN_B16K_PROBE) flags |= CTCASR_BUILD_PROBE_WRONG_RESULTS;
+    if (PRNN_PROBE_HALF_LOADS) flags |= CTCASR_BUILD_PROBE_WRONG_RESULTS;
     if (PRNN_GROUPS != 8 || PRNN_XCD_AWARE != 0 || PRNN_CHAIN_LB != 4 || PRNN_CHAIN_REGW != 32 ||
-        PRNN_CHAIN0_PRIO != 1 || PRNN_POLL_SLEEP != 1 || PRNN_RS_LOCK != 1 || PRNN_TURN_PRIO != 2 ||
+        PRNN_CHAIN0_PRIO != 1 || PRNN_POLL_SLEEP != 1 ||
         PRNN_XCD_TILE_PAIRS != 1 || PRNN_B16S_D != 8 || PRNN_B16S_JW != 7 || PRNN_B16S_JP != 5 ||
-        PRNN_B16S_JA != 1 || PRNN_B16S_XCD_EXCL != 0 || PRNN_B16K_JW != 3 || PRNN_B16K_JP != 2 ||
-        PRNN_B16K_JA != 1 || PRNN_B16K_SC1 != 0 || PRNN_B16K_SLEEP != 1 || PRNN_W16_D != 12 ||
+        PRNN_B16S_JA != 1 || PRNN_B16S_XCD_EXCL != 0 || PRNN_W16_D != 12 ||
         PRNN_W16_KD != 12 || PRNN_W16_KS != 2)
         flags |= CTCASR_BUILD_NONDEFAULT_TUNING;
     return flags;

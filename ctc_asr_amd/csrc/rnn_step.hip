@@ -313,10 +313,10 @@ static size_t rnn_state_bytes(int B, int H) {
 // Layout of a workspace of the persistent kernels:
 //   [state ping-pong + carry]                                   rnn_state_bytes(B, H)
 //   [control header: per row block, its barrier words (SyncWords: arrival counters, the sticky
-//    time-out word, the residency words), then its K-pair hand-off words]
+//    time-out word, the residency words), then (LSTM, H = 2048) its K-pair hand-off words]
 //                                                               prnn_blocks(B) * prnn_ctl_bytes
-//   [exchange regions: per row block, the all-zero block, the per-step blocks, the reduce-scatter
-//    ring, the inverse scales]                                  prnn_blocks(B) * prnn_exchange_bytes
+//   [exchange regions: per row block, the all-zero block, the per-step blocks, the inverse
+//    scales]                                                    prnn_blocks(B) * prnn_exchange_bytes
 // What must last from launch to launch, or be zero at a launch, sits in the header at offsets
 // that depend on (cell, B, H) only - one workspace serves every T up to the one it was sized for.
 // The exchange regions follow and move with T: a pass writes them before it reads them, except
@@ -415,8 +415,8 @@ extern "C" int ctcasr_rnn_fwd_steps(int cell, const float *xw, const float *xw_b
     if (y_pieces && (seq_len || !ctcasr_rnn_fwd_f16_supported(cell, T, B, H, flags)))
         return CTCASR_ERR_UNSUPPORTED;
     if (flags & 0xFF & ~(CTCASR_RNN_HALF_CHIP | CTCASR_RNN_WHOLE_CHIP | CTCASR_RNN_ONE_BARRIER |
-                         CTCASR_RNN_REDUCE_SCATTER | CTCASR_RNN_F16 | CTCASR_RNN_XCD_SPLIT |
-                         CTCASR_RNN_STAGGER | CTCASR_RNN_KPAIR))
+                         CTCASR_RNN_F16 | CTCASR_RNN_XCD_SPLIT | CTCASR_RNN_STAGGER |
+                         CTCASR_RNN_KPAIR))
         return CTCASR_ERR_BAD_ARGUMENT;
     if (!xw || !w_hh || !y || !reserve) return CTCASR_ERR_BAD_ARGUMENT;
     if (step_begin < 0 || step_end > T || step_begin >= step_end) return CTCASR_ERR_BAD_ARGUMENT;
@@ -518,8 +518,8 @@ extern "C" int ctcasr_rnn_bwd_steps(int cell, const float *dy, const float *y,
     int rc = rnn_check(cell, T, B, H);
     if (rc != CTCASR_OK) return rc;
     if (flags & 0xFF & ~(CTCASR_RNN_HALF_CHIP | CTCASR_RNN_WHOLE_CHIP | CTCASR_RNN_ONE_BARRIER |
-                         CTCASR_RNN_REDUCE_SCATTER | CTCASR_RNN_F16 | CTCASR_RNN_XCD_SPLIT |
-                         CTCASR_RNN_STAGGER | CTCASR_RNN_KPAIR))
+                         CTCASR_RNN_F16 | CTCASR_RNN_XCD_SPLIT | CTCASR_RNN_STAGGER |
+                         CTCASR_RNN_KPAIR))
         return CTCASR_ERR_BAD_ARGUMENT;
     if (!dy || !y || !w_hh_t || !reserve || !dxw) return CTCASR_ERR_BAD_ARGUMENT;
     if (step_begin < 0 || step_end > T || step_begin >= step_end) return CTCASR_ERR_BAD_ARGUMENT;
@@ -621,8 +621,7 @@ extern "C" int ctcasr_rnn_poll_error(void *workspace, size_t workspace_bytes, in
         // after a time-out the arrival counters are in an undefined state: start over with
         // clean barrier words (this also clears the time-out word)
         if (err && hipMemset(wb.sync, 0, prnn_sync_bytes()) != hipSuccess) return CTCASR_ERR_LAUNCH;
-        // ... and so are the write counts of the K-pair hand-off slots (prnn_bwd16k_kernel,
-        // prnn_bwd16w_kernel)
+        // ... and so are the write counts of the K-pair hand-off slots (prnn_bwd16w_kernel)
         const size_t kp_bytes = prnn_kp_region_bytes(H, cell_gates(cell));
         if (err && kp_bytes && hipMemset(wb.kp, 0, kp_bytes) != hipSuccess)
             return CTCASR_ERR_LAUNCH;

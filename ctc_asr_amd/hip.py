@@ -14,14 +14,13 @@ import torch
 _PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_PKG_DIR, 'libctcasr.so')
 
-ABI_VERSION = 7
+ABI_VERSION = 8
 BUILD_PROBE_WRONG_RESULTS, BUILD_NONDEFAULT_TUNING = 1, 2      # ctcasr_build_flags() bits
 RNN_DEFAULT, RNN_HALF_CHIP, RNN_WHOLE_CHIP, RNN_ONE_BARRIER = 0, 1, 2, 4   # rnn_fwd/bwd `flags`
-RNN_REDUCE_SCATTER = 8
 RNN_F16 = 16          # persistent LSTM / GRU kernels: the recurrent products as fp16x3 (ABI v5)
 RNN_XCD_SPLIT = 32    # fp16-pipe kernels: one direction per half of the XCDs
 RNN_STAGGER = 64      # fp16-pipe LSTM-1024 backward, 24 / 32 rows: tiles staggered by half a step
-RNN_KPAIR = 128       # ... and the K axis split over pairs of workgroups (ABI v7)
+RNN_KPAIR = 128       # fp16-pipe LSTM-2048 backward: the K axis split over pairs of workgroups
 # ctcasr_grad_norm: floats per chunk of a segment, and the most segments a call takes
 GRAD_NORM_CHUNK = 8192
 GRAD_NORM_MAX_SEGMENTS = 64

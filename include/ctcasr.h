@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define CTCASR_ABI_VERSION 7
+#define CTCASR_ABI_VERSION 8
 
 enum {
     CTCASR_OK = 0,
@@ -317,10 +317,8 @@ int ctcasr_rnn_fwd(int cell, const float *xw, const float *xw_bias, const float 
 /* batches of 17..32 rows: the round-1 kernels (both 16-row tiles behind ONE barrier per step)
  * instead of the default two independent chains per workgroup - for A/B measurements */
 #define CTCASR_RNN_ONE_BARRIER 4
-/* backward, LSTM with H = 1024: the reduce-scatter form of the recurrence (every workgroup
- * multiplies the dgates of its OWN units into partial dh tiles for all units, consumers sum 64
- * tiles) instead of the all-gather form (every workgroup reads the dgates of all units) */
-#define CTCASR_RNN_REDUCE_SCATTER 8
+/* (value 8: the reduce-scatter backward form of ABI v3 - v7, removed in ABI v8.  The bit is unknown
+ * now: a call that carries it returns CTCASR_ERR_BAD_ARGUMENT.) */
 /* forward, LSTM / GRU on the persistent kernels (ABI v5): the recurrent product h W_hh^T on the
  * fp16 matrix pipe - h (|h| <= 1) and the workgroup's slice of W_hh (scaled by a power of two found
  * inside the kernel from the slice's largest magnitude, so no weight can overflow) as TWO fp16
@@ -341,13 +339,14 @@ int ctcasr_rnn_fwd(int cell, const float *xw, const float *xw_bias, const float 
  * Same results bit for bit; every launch of a pass may choose freely.  Calls with per-row lengths
  * and other shapes ignore it.  (ABI v6) */
 #define CTCASR_RNN_STAGGER 64
-/* backward, same calls as CTCASR_RNN_STAGGER (and taking precedence over it): the K-pair form
- * (prnn_bwd16k_kernel, ABI v7) - pairs of workgroups on one XCD share 32 hidden units, each holds
- * one K half of their weights, reads only that half of the published dgates (128 KB instead of 256
- * per tile and step) and hands its partner a [16 x 16] partial tile through L2.  Publishes exactly
- * what the other fp16 backward kernels publish; results agree with them to rounding (the order of
- * the K sums differs; the hand-off carries a tag in the lowest significand bit of each partial
- * sum), step ranges bit-identical to one launch.  Every launch of a pass may choose freely. */
+/* backward, LSTM with H = 2048 on the fp16 pipe: the K-pair form (prnn_bwd16w_kernel with a K
+ * split, ABI v7) - pairs of workgroups on one XCD share 16 hidden units, each holds one K half of
+ * their weights, reads only that half of the published dgates and hands its partner the partial
+ * sums of the partner's units through L2.  Publishes exactly what the plain form publishes; results
+ * agree with it to rounding (the order of the K sums differs; the hand-off carries a tag in the
+ * lowest significand bit of each partial sum), step ranges bit-identical to one launch.  Every
+ * launch of a pass may choose freely.  Other shapes ignore it (ABI v8: H = 1024 too, whose K-pair
+ * form of the staggered kernel was removed). */
 #define CTCASR_RNN_KPAIR 128
 /* Residency ticket (bits 8..31 of `flags`, 0 = none): a persistent launch that carries one posts
  * it in the workspace once ALL of its workgroups are running; ctcasr_rnn_resident_gate() makes

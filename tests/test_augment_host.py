@@ -137,7 +137,7 @@ def test_header_binding_and_flags_agree_on_the_limits():
     assert limit == hip.SPEC_AUGMENT_MAX_MASKS == params.SPECAUG_MAX_MASKS == 16
     for name in ('ctcasr_spec_augment', 'ctcasr_speed_perturb', 'ctcasr_resample_num_samples'):
         assert name in hip.SIGNATURES
-    assert hip.ABI_VERSION == 7
+    assert hip.ABI_VERSION == 8
 
 
 def test_flags_parse_and_refuse_bad_values():

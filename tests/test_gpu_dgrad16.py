@@ -142,10 +142,8 @@ def test_weight_pieces_saturate_and_cover_ragged_column_counts(hip):
 @pytest.mark.parametrize('batch,frames', [(32, 399), (16, 329)])
 def test_the_model_takes_the_kernel_and_its_schedules_agree(hip, batch, frames):
     """`CTCModel.backward` with the own data-gradient kernel (the default for LSTM-1024) against
-    the library form (CTCASR_OWN_DGRAD=0) on the same weights and batch - every gradient slice -
-    and the kernel's optional schedules (`dgrad_early`: a finished direction's share of a step
-    range multiplied beside the next recurrence launch, on the side stream / a stream of its own)
-    against the plain one; T' odd in the second case (the two directions' ranges overlap by a row)."""
+    the library form (CTCASR_OWN_DGRAD=0) on the same weights and batch - every gradient slice;
+    T' odd in the second case."""
     from ctc_asr_amd.model import CTCModel, ModelConfig
     cfg = ModelConfig(used_model='ds2', conv_filters=(32, 32), num_units_dense=2048,
                       num_layers_rnn=2, num_units_rnn=H, rnn_cell='lstm', cudnn=True,
@@ -155,16 +153,16 @@ def test_the_model_takes_the_kernel_and_its_schedules_agree(hip, batch, frames):
     flen = torch.full((batch,), frames, dtype=torch.int32)
     labels = [list(rng.integers(1, 28, size=20)) for _ in range(batch)]
 
-    def grads(own, early):
+    def grads(own):
         model = CTCModel(cfg, DEV, seed=5)
-        model.own_dgrad, model.dgrad_early = own, early
+        model.own_dgrad = own
         loss = model.forward_backward(feats, flen, labels)
         torch.cuda.synchronize()
         model.check_rnn_error()
         return float(loss), model.arena.grad.clone(), model
 
-    loss_lib, grad_lib, _ = grads(False, '0')
-    loss_own, grad_own, model = grads(True, '0')
+    loss_lib, grad_lib, _ = grads(False)
+    loss_own, grad_own, model = grads(True)
     arith = model.arithmetic()
     assert arith['rnn1/data_gradient'].startswith('fp16x3 block-scaled')
     assert arith['rnn0/data_gradient'].startswith('fp16x3 block-scaled')
@@ -173,12 +171,6 @@ def test_the_model_takes_the_kernel_and_its_schedules_agree(hip, batch, frames):
         ref = grad_lib[a:b].double()
         rel = float((ref - grad_own[a:b].double()).norm() / ref.norm().clamp_min(1e-30))
         assert rel < 2e-5, (name, rel)               # both are fp32-grade forms of one product
-    for early in ('side', 'own'):
-        _, grad_e, _ = grads(True, early)
-        for name, a, b in model.arena.layer_slices:
-            ref = grad_own[a:b].double()
-            rel = float((ref - grad_e[a:b].double()).norm() / ref.norm().clamp_min(1e-30))
-            assert rel < 2e-6, (early, name, rel)    # the same products, summed in another order
 
 
 @pytest.mark.parametrize('steps', [1, 2, 3])
@@ -186,7 +178,7 @@ def test_the_model_takes_the_kernel_and_its_schedules_agree(hip, batch, frames):
 def test_behind_the_recurrence_kernel_at_the_edges(hip, steps, batch):
     """The operands the fp16-pipe backward recurrence publishes at one to three steps and batches
     of one row, of a tile and one row, and of tiles a row short of full - behind the one-barrier
-    kernel and behind the staggered / K-pair kernels (which take 24 and 32 rows) - for column
+    kernel and behind the staggered kernel (which takes 24 and 32 rows) - for column
     counts of 640, 2048 and 200 (not a multiple of 16): dx against float64 `dxw @ W_ih` within the
     bars of test_against_float64_next_to_the_fp32_gemm, whole, one step at a time (the other rows
     untouched) and one direction at a time."""
@@ -201,7 +193,7 @@ def test_behind_the_recurrence_kernel_at_the_edges(hip, steps, batch):
     weights = {n: torch.randn(8 * H, n, device=DEV, generator=gen) / np.sqrt(n)
                for n in (640, 2048, 200)}
     base = hip.RNN_F16 | hip.RNN_XCD_SPLIT
-    for flags in (hip.RNN_F16, base | hip.RNN_STAGGER, base | hip.RNN_KPAIR):
+    for flags in (hip.RNN_F16, base | hip.RNN_STAGGER):
         dxw = hip.rnn_bwd('lstm', dy, y, w_hh_t, reserve, workspace=ws, flags=flags)
         hip.rnn_poll_error('lstm', ws, steps, batch, H)
         d2 = dxw.view(steps * batch, 8 * H)

@@ -439,89 +439,6 @@ def test_rnn_bwd_staggered_tiles_equal_one_barrier(hip, xcd, dims):
     assert torch.equal(a, b)
 
 
-@pytest.mark.parametrize('xcd', [0, 1])
-@pytest.mark.parametrize('dims', [(12, 32), (7, 17), (61, 24)])
-def test_rnn_bwd_k_pairs(hip, xcd, dims):
-    """CTCASR_RNN_KPAIR (prnn_bwd16k_kernel, round 6): pairs of workgroups share 32 hidden units,
-    each multiplies ONE K half of the published dgates and hands its partner a [16 x 16] partial
-    tile through L2 (words tagged with the parity of the slot's write count).  dxw against autograd
-    through the float64 recurrence within the staggered kernel's error (the sums only differ in
-    their order); column maxima exact; step ranges of any cut - an odd number of steps flips the
-    tag parity the next launch starts from - bit-identical to one launch, repeated passes on one
-    workspace too; what it publishes is what the staggered kernel would publish from the same
-    sums (the data-gradient kernel reads it); the kernels may take turns inside a pass."""
-    num_steps, batch = dims
-    hidden, gh = 1024, 4096
-    g = torch.Generator(device=DEV).manual_seed(47)
-    xw = torch.randn(num_steps, batch, 2, gh, device=DEV, generator=g) * 0.5
-    w_hh = torch.randn(2, gh, hidden, device=DEV, generator=g) / np.sqrt(hidden)
-    dy = torch.randn(num_steps, batch, 2 * hidden, device=DEV, generator=g) * \
-        torch.logspace(-5, 0, batch, device=DEV).view(1, batch, 1)
-    xw64 = xw.double().requires_grad_(True)
-    ref_y = _recurrence_float64('lstm', xw64, w_hh, None, None)
-    (ref_y * dy.double()).sum().backward()
-    ref = xw64.grad
-    y, reserve, ws = hip.rnn_fwd('lstm', xw, w_hh)
-    w_hh_t = hip.transpose_batched(w_hh)
-    base = hip.RNN_F16 | (hip.RNN_XCD_SPLIT if xcd else 0)
-    x_off, s_off = hip.dgrad16_published_offsets(num_steps, batch, hidden)
-    x_bytes = (num_steps + 1) * 2 * batch * gh * 4
-    s_bytes = (num_steps + 1) * 2 * 64 * 32 * 4
-
-    def run(flags, cuts=None, alternate=None):
-        db = torch.zeros(2 * gh, device=DEV)
-        colmax = torch.zeros(2 * gh, dtype=torch.int32, device=DEV)
-        dxw = torch.full((num_steps, batch, 2, gh), float('nan'), device=DEV)
-        cuts = cuts or [num_steps, 0]
-        for k, (hi, lo) in enumerate(zip(cuts[:-1], cuts[1:])):
-            hip.rnn_bwd('lstm', dy, y, w_hh_t, reserve, None, dxw=dxw, dbias=db, workspace=ws,
-                        steps=(lo, hi), flags=(alternate if alternate and k % 2 else flags),
-                        colmax=colmax)
-        hip.rnn_poll_error('lstm', ws, num_steps, batch, hidden)
-        published = (ws[x_off:x_off + x_bytes].clone(), ws[s_off:s_off + s_bytes].clone())
-        return dxw, db, colmax, published
-
-    def row_err(got):
-        err = (got.double() - ref).abs().amax(dim=(0, 2, 3))
-        return float((err / ref.abs().amax(dim=(0, 2, 3)).clamp_min(1e-30)).max())
-
-    stag = run(base | hip.RNN_STAGGER)
-    want = run(base | hip.RNN_KPAIR)
-    assert torch.isfinite(want[0]).all()
-    e_pair, e_stag = row_err(want[0]), row_err(stag[0])
-    assert e_pair < 1.5 * e_stag + 2e-7, (e_pair, e_stag)
-    assert torch.equal(want[2].view(torch.float32), want[0].abs().amax(dim=(0, 1)).reshape(-1))
-    assert float((want[1] - stag[1]).abs().max()) < 1e-5 * max(1.0, float(stag[1].abs().max()))
-    for attempt in range(3):
-        got = run(base | hip.RNN_KPAIR)
-        assert torch.equal(got[0], want[0]), attempt
-        assert torch.equal(got[2], want[2])
-        assert torch.equal(got[3][0], want[3][0])
-        assert torch.equal(got[3][1], want[3][1])
-    if num_steps >= 7:
-        cuts = [num_steps, num_steps - 1, num_steps - 3, num_steps // 2, 1, 0]
-        for attempt in range(2):
-            got = run(base | hip.RNN_KPAIR, cuts)
-            assert torch.equal(got[0], want[0]), attempt
-            assert torch.equal(got[2], want[2])
-            assert torch.equal(got[3][0], want[3][0])
-            assert torch.equal(got[3][1], want[3][1])
-        # taking turns with the staggered kernel inside one pass: each reads what the other
-        # published
-        mixed = run(base | hip.RNN_KPAIR, cuts, alternate=base | hip.RNN_STAGGER)
-        assert row_err(mixed[0]) < 1.5 * e_stag + 2e-7
-        again = run(base | hip.RNN_KPAIR)
-        assert torch.equal(again[0], want[0])
-    # per-row lengths: the flag is ignored (one-barrier kernel)
-    sl = torch.randint(1, num_steps + 1, (batch,), device=DEV, generator=g).int()
-    y_l, reserve_l, ws_l = hip.rnn_fwd('lstm', xw, w_hh, sl)
-    a = hip.rnn_bwd('lstm', dy, y_l, w_hh_t, reserve_l, sl, workspace=ws_l, flags=base)
-    b = hip.rnn_bwd('lstm', dy, y_l, w_hh_t, reserve_l, sl, workspace=ws_l,
-                    flags=base | hip.RNN_KPAIR)
-    hip.rnn_poll_error('lstm', ws_l, num_steps, batch, hidden)
-    assert torch.equal(a, b)
-
-
 @pytest.mark.parametrize('use_len', [False, True])
 @pytest.mark.parametrize('dims', [(12, 16), (9, 5), (7, 27), (5, 40)])
 def test_rnn_bwd_k_pairs_at_2048(hip, use_len, dims):
@@ -593,15 +510,14 @@ def test_rnn_bwd_k_pairs_at_2048(hip, use_len, dims):
 @pytest.mark.parametrize('xcd', [0, 1])
 @pytest.mark.parametrize('batch', [17, 20, 24, 27, 32])
 def test_staggered_tiles_read_nothing_of_the_pass_before(hip, xcd, batch):
-    """Round 6: the kernels that stagger the two 16-row tiles publish tile 1's rows of a step after
-    tile 0's rows of that step have been read; where the two share a cache line the reader's L1 /
-    L2 keeps tile 1's bytes of the PASS BEFORE (same addresses) - invisible when every pass
-    computes the same thing, which is what every other test of these kernels does.  Here: a pass
+    """Round 6: the kernel that staggers the two 16-row tiles publishes tile 1's rows of a step
+    after tile 0's rows of that step have been read; where the two share a cache line the reader's
+    L1 / L2 keeps tile 1's bytes of the PASS BEFORE (same addresses) - invisible when every pass
+    computes the same thing, which is what every other test of this kernel does.  Here: a pass
     over data A, then a pass over data B on the same workspace, against data B on a fresh
-    workspace through the one-barrier kernel.  Staggered: bit for bit (batches that are not a
-    multiple of 8 keep the one-barrier kernel: `prnn_bwd`); K pairs: to rounding.  (The K-pair
-    kernel at 17 .. 20 rows failed this before the dispatch kept it to multiples of 8:
-    tools/r06_stale_probe.py.)"""
+    workspace through the one-barrier kernel, bit for bit (batches that are not a multiple of 8
+    keep the one-barrier kernel: `prnn_bwd`).  (A K-pair form of the kernel, since removed, failed
+    this at 17 .. 20 rows before the dispatch kept it to multiples of 8.)"""
     num_steps, hidden, gh = 40, 1024, 4096
     base = hip.RNN_F16 | (hip.RNN_XCD_SPLIT if xcd else 0)
 
@@ -612,22 +528,18 @@ def test_staggered_tiles_read_nothing_of_the_pass_before(hip, xcd, batch):
         dy = torch.randn(num_steps, batch, 2 * hidden, device=DEV, generator=g)
         return xw, w, hip.transpose_batched(w), dy
 
-    for extra, exact in ((hip.RNN_STAGGER, True), (hip.RNN_KPAIR, False)):
-        for rep in range(3):
-            xa, wa, wta, dya = data(100 + rep)
-            xb, wb, wtb, dyb = data(200 + rep)
-            ya, ra, ws = hip.rnn_fwd('lstm', xa, wa)
-            hip.rnn_bwd('lstm', dya, ya, wta, ra, workspace=ws, flags=base | extra)
-            yb, rb, _ = hip.rnn_fwd('lstm', xb, wb, workspace=ws)
-            got = hip.rnn_bwd('lstm', dyb, yb, wtb, rb, workspace=ws, flags=base | extra)
-            hip.rnn_poll_error('lstm', ws, num_steps, batch, hidden)
-            yf, rf, wsf = hip.rnn_fwd('lstm', xb, wb)
-            want = hip.rnn_bwd('lstm', dyb, yf, wtb, rf, workspace=wsf, flags=base)
-            hip.rnn_poll_error('lstm', wsf, num_steps, batch, hidden)
-            if exact:
-                assert torch.equal(got, want), (rep, int((got != want).sum()))
-            else:
-                assert float((got - want).abs().max()) < 2e-6 * float(want.abs().max()), rep
+    for rep in range(3):
+        xa, wa, wta, dya = data(100 + rep)
+        xb, wb, wtb, dyb = data(200 + rep)
+        ya, ra, ws = hip.rnn_fwd('lstm', xa, wa)
+        hip.rnn_bwd('lstm', dya, ya, wta, ra, workspace=ws, flags=base | hip.RNN_STAGGER)
+        yb, rb, _ = hip.rnn_fwd('lstm', xb, wb, workspace=ws)
+        got = hip.rnn_bwd('lstm', dyb, yb, wtb, rb, workspace=ws, flags=base | hip.RNN_STAGGER)
+        hip.rnn_poll_error('lstm', ws, num_steps, batch, hidden)
+        yf, rf, wsf = hip.rnn_fwd('lstm', xb, wb)
+        want = hip.rnn_bwd('lstm', dyb, yf, wtb, rf, workspace=wsf, flags=base)
+        hip.rnn_poll_error('lstm', wsf, num_steps, batch, hidden)
+        assert torch.equal(got, want), (rep, int((got != want).sum()))
 
 
 @pytest.mark.parametrize('cell,hidden', [('lstm', 1024), ('gru', 1024), ('rnn_relu', 2048),
@@ -658,8 +570,9 @@ def test_no_persistent_kernel_reads_the_pass_before(hip, cell, hidden):
 
     f16 = hip.RNN_F16 | hip.RNN_XCD_SPLIT
     variants = ((0, 0), (0, hip.RNN_WHOLE_CHIP), (hip.RNN_ONE_BARRIER, hip.RNN_ONE_BARRIER),
-                (f16, f16 | hip.RNN_STAGGER), (f16, f16 | hip.RNN_KPAIR),
-                (hip.RNN_F16 | hip.RNN_HALF_CHIP, hip.RNN_F16))
+                (f16, f16 | hip.RNN_STAGGER), (hip.RNN_F16 | hip.RNN_HALF_CHIP, hip.RNN_F16))
+    if (cell, hidden) == ('lstm', 2048):
+        variants += ((f16, f16 | hip.RNN_KPAIR),)
     for batch in (9, 17, 27, 32):
         if not hip.rnn_persistent_supported(cell, num_steps, batch, hidden):
             continue
@@ -741,9 +654,7 @@ def _changing_t_variants(h, cell, hidden):
     if (cell, hidden) == ('lstm', 1024):
         return [('fp32', 0, 0, True), ('whole chip', 0, h.RNN_WHOLE_CHIP, True),
                 ('one barrier', h.RNN_ONE_BARRIER, h.RNN_ONE_BARRIER, True),
-                ('reduce-scatter', 0, h.RNN_REDUCE_SCATTER, True), ('f16', f16, f16, True),
-                ('f16 stagger', f16, f16 | h.RNN_STAGGER, True),
-                ('f16 k-pair', f16, f16 | h.RNN_KPAIR, True),
+                ('f16', f16, f16, True), ('f16 stagger', f16, f16 | h.RNN_STAGGER, True),
                 ('f16 half-chip forward', h.RNN_F16 | h.RNN_HALF_CHIP, h.RNN_F16, True)]
     if (cell, hidden) == ('lstm', 2048):
         return [('f16', h.RNN_F16, h.RNN_F16, True),
@@ -869,7 +780,7 @@ def test_one_workspace_serves_every_shorter_pass(hip, cell, hidden):
     if (cell, hidden) == ('lstm', 2048):
         assert {('f16 k-pair', 16), ('f16 k-pair', 40)} <= ran, ran
     if (cell, hidden) == ('lstm', 1024):
-        assert {('f16 k-pair', 24), ('f16 k-pair', 32), ('f16 stagger', 40)} <= ran, ran
+        assert {('f16 stagger', 24), ('f16 stagger', 32), ('f16 stagger', 40)} <= ran, ran
     assert {('fp32', 40), ('fp32', 64)} <= ran, ran
 
 
@@ -920,7 +831,7 @@ def _anchor_float64(hip, p, got, bwd_flags):
 
 
 @pytest.mark.parametrize('cell,hidden,batch,flag_names', [
-    ('lstm', 1024, 40, ()), ('lstm', 1024, 40, ('RNN_F16', 'RNN_XCD_SPLIT', 'RNN_KPAIR')),
+    ('lstm', 1024, 40, ()), ('lstm', 1024, 40, ('RNN_F16', 'RNN_XCD_SPLIT', 'RNN_STAGGER')),
     ('lstm', 2048, 40, ('RNN_F16', 'RNN_KPAIR')), ('lstm', 2048, 16, ('RNN_F16', 'RNN_KPAIR'))])
 def test_time_out_word_of_a_shorter_pass_is_the_one_the_poll_reads(hip, cell, hidden, batch,
                                                                    flag_names):
@@ -1531,55 +1442,6 @@ def test_beam_search_random_sweep_against_the_oracle(hip):
             assert np.allclose(logp.cpu().numpy(), ref_logp, rtol=1e-5, atol=1e-3)
             cases += 1
     assert cases == 27
-
-
-@pytest.mark.parametrize('batch,lengths,num_steps', [
-    (3, False, 37), (16, True, 37), (19, True, 37), (32, False, 37), (32, True, 37),
-    (45, True, 37),            # two blocks of rows (32 + 13)
-    (19, False, 1), (19, True, 2), (33, False, 3)])    # degenerate passes; a block of ONE row
-def test_reduce_scatter_backward_equals_the_all_gather_kernels(hip, batch, lengths, num_steps):
-    """`RNN_REDUCE_SCATTER`: the LSTM-1024 backward recurrence with the product dgates x R cut
-    along K (every workgroup multiplies the dgates of its OWN units into a partial dh for all
-    units, consumers sum 64 partial tiles) against the default kernels (all-gather of dgates,
-    themselves checked against float64 autograd in `test_rnn_fwd_bwd`): same results to fp32
-    summation order, deterministic, bit-identical when cut into step ranges; one batch tile
-    (one chain) and two (two chains per workgroup), with and without per-row lengths."""
-    hidden = 1024
-    gen = torch.Generator(device=DEV).manual_seed(100 + batch)
-    xw = torch.randn(num_steps, batch, 2, 4 * hidden, device=DEV, generator=gen) * 0.5
-    w_hh = torch.randn(2, 4 * hidden, hidden, device=DEV, generator=gen) / 32
-    dy = torch.randn(num_steps, batch, 2 * hidden, device=DEV, generator=gen)
-    seq_len = None
-    if lengths:
-        seq_len = torch.randint(1, num_steps + 1, (batch,), device=DEV, generator=gen,
-                                dtype=torch.int32)
-        seq_len[0] = num_steps
-        seq_len[batch - 1] = 1
-    assert hip.rnn_persistent_supported('lstm', num_steps, batch, hidden)
-    w_hh_t = hip.transpose_batched(w_hh)
-    y, reserve, ws = hip.rnn_fwd('lstm', xw, w_hh, seq_len)
-    ref = hip.rnn_bwd('lstm', dy, y, w_hh_t, reserve, seq_len, workspace=ws)
-    dbias = torch.zeros(2 * 4 * hidden, device=DEV)
-    got = hip.rnn_bwd('lstm', dy, y, w_hh_t, reserve, seq_len, workspace=ws, dbias=dbias,
-                      flags=hip.RNN_REDUCE_SCATTER)
-    want_db = got.double().sum(dim=(0, 1)).reshape(-1)
-    assert float((dbias.double() - want_db).abs().max()) < 1e-4 * max(1.0, float(want_db.abs().max()))
-    again = hip.rnn_bwd('lstm', dy, y, w_hh_t, reserve, seq_len, workspace=ws,
-                        flags=hip.RNN_REDUCE_SCATTER)
-    hip.rnn_poll_error('lstm', ws, num_steps, batch, hidden)
-    assert torch.equal(got, again)
-    scale = max(1.0, float(ref.abs().max()))
-    assert float((got - ref).abs().max()) < 2e-5 * scale
-    if seq_len is not None:       # steps past a row's length carry no gradient
-        assert float(got[1:, batch - 1].abs().max()) == 0.0
-    cut = torch.empty_like(got)
-    marks = sorted({num_steps, num_steps * 20 // 37, num_steps * 19 // 37, num_steps * 7 // 37, 0},
-                   reverse=True)
-    for hi, lo in zip(marks[:-1], marks[1:]):
-        hip.rnn_bwd('lstm', dy, y, w_hh_t, reserve, seq_len, dxw=cut, workspace=ws,
-                    steps=(lo, hi), flags=hip.RNN_REDUCE_SCATTER)
-    hip.rnn_poll_error('lstm', ws, num_steps, batch, hidden)
-    assert torch.equal(cut, got)
 
 
 @pytest.mark.parametrize('flags', ['RNN_DEFAULT', 'RNN_F16'])

@@ -265,8 +265,7 @@ def test_two_tile_recurrences_equal_the_single_barrier_kernels_at_full_size(hip,
     assert float((reserve_new.view(torch.float32) - reserve.view(torch.float32)).abs().max()) < 1e-5
     dxw_ref = hip.rnn_bwd('lstm', dy, y_ref, w_hh_t, reserve, workspace=ws,
                           flags=hip.RNN_ONE_BARRIER)
-    for flags in (hip.RNN_DEFAULT, hip.RNN_WHOLE_CHIP, hip.RNN_WHOLE_CHIP | hip.RNN_ONE_BARRIER,
-                  hip.RNN_REDUCE_SCATTER):
+    for flags in (hip.RNN_DEFAULT, hip.RNN_WHOLE_CHIP, hip.RNN_WHOLE_CHIP | hip.RNN_ONE_BARRIER):
         dxw = hip.rnn_bwd('lstm', dy, y_ref, w_hh_t, reserve, workspace=ws, flags=flags)
         again = hip.rnn_bwd('lstm', dy, y_ref, w_hh_t, reserve, workspace=ws, flags=flags)
         assert torch.equal(dxw, again), flags

@@ -3,8 +3,8 @@ kernel goes wrong first: T = 1 (each step is the pipeline's prologue and epilogu
 prefetch guards, the all-zero h(-1) block and the stagger's half-step offset meet), T = 2 and 3
 (odd step counts against the K-pair tag parity), batches of one and two rows, a tile of one row,
 and two row blocks - where `prnn_bwd` hands each 32-row block its own rows as B and the whole batch
-as the row stride (block 1 of B = 56 and both blocks of B = 64 take the staggered / K-pair
-kernels with B != BS).  Per pass: y and dxw against the float64 recurrence and autograd
+as the row stride (block 1 of B = 56 and both blocks of B = 64 take the staggered kernel with
+B != BS).  Per pass: y and dxw against the float64 recurrence and autograd
 (tests/rnn_reference.py) inside the bars of each kernel's own test, the column maxima bit for bit,
 the bias gradients against the kernel's own dxw, which kernel form ran, a clean time-out poll;
 T = 3 cut into single-step launches; one workspace across T = 3, 1, 2, 3, 1."""
@@ -23,12 +23,14 @@ FAMILIES = [('lstm', 1024), ('gru', 1024), ('lstm', 2048), ('gru', 2048), ('rnn_
             ('rnn_tanh', 2048)]
 VARIANTS = ['fp32', 'whole chip', 'one barrier', 'f16 stagger', 'f16 k-pair',
             'f16 half-chip forward', 'stream']
+# (the K-pair form exists at H = 2048 only)
+CASES = [(cell, hidden, variant) for variant in VARIANTS for cell, hidden in FAMILIES
+         if variant != 'f16 k-pair' or hidden == 2048]
 STEPS = (1, 2, 3)
 BATCHES = {1024: (1, 2, 8, 15, 16, 17, 24, 31, 32, 33, 40, 48, 56, 64),
            2048: (1, 2, 16, 17, 32, 33, 56, 64)}
 # the batches at which a variant must take the kernel it exists for (no per-row lengths)
 MUST_RUN = {('lstm', 1024, 'f16 stagger'): ('prnn_bwd16s_kernel', {24, 32, 56, 64}),
-            ('lstm', 1024, 'f16 k-pair'): ('prnn_bwd16k_kernel', {24, 32, 56, 64}),
             ('lstm', 2048, 'f16 k-pair'): ('prnn_bwd16w_kernel<k-pair>', set(BATCHES[2048]))}
 
 
@@ -45,7 +47,7 @@ def _flags(h, variant):
 
 def _bwd_kernels(h, cell, hidden, num_steps, batch, flags, ragged):
     """The backward kernel each 32-row block runs, by the rule of `prnn_bwd`: the LSTM-1024
-    fp16-pipe call takes the K-pair / staggered kernel on half of the chip, without per-row
+    fp16-pipe call takes the staggered kernel on half of the chip, without per-row
     lengths, for a block of two 16-row tiles whose row count is a multiple of 8; at LSTM-2048
     RNN_F16 | RNN_KPAIR alone takes the K-pair kernel for every tile."""
     if not h.rnn_persistent_supported(cell, num_steps, batch, hidden):
@@ -69,8 +71,7 @@ def _bwd_kernels(h, cell, hidden, num_steps, batch, flags, ragged):
         else:
             apart = ((rows + 15) // 16 == 2 and not flags & h.RNN_WHOLE_CHIP and not ragged and
                      rows % 8 == 0)
-            forms.append('prnn_bwd16k_kernel' if apart and flags & h.RNN_KPAIR else
-                         'prnn_bwd16s_kernel' if apart and flags & h.RNN_STAGGER else
+            forms.append('prnn_bwd16s_kernel' if apart and flags & h.RNN_STAGGER else
                          'prnn_bwd16_kernel')
     return forms
 
@@ -208,8 +209,7 @@ def _check_pass(h, cell, hidden, c, variant, fwd_flags, bwd_flags, forms, got, c
             what
 
 
-@pytest.mark.parametrize('variant', VARIANTS)
-@pytest.mark.parametrize('cell,hidden', FAMILIES)
+@pytest.mark.parametrize('cell,hidden,variant', CASES)
 def test_every_variant_at_the_edge_shapes(hip, cell, hidden, variant, monkeypatch):
     fwd_flags, bwd_flags = _flags(hip, variant)
     if variant == 'stream':
@@ -231,7 +231,7 @@ def test_every_variant_at_the_edge_shapes(hip, cell, hidden, variant, monkeypatc
                 dxw = got[1]
                 # the staggered / K-pair forms against the plain fp16 kernel on the same reserve:
                 # staggered bit for bit; K pairs within 1.5x its row error + 2e-7
-                # (test_rnn_bwd_k_pairs / _at_2048); blocks that fall back are the plain kernel
+                # (test_rnn_bwd_k_pairs_at_2048); blocks that fall back are the plain kernel
                 if bwd_flags & (hip.RNN_STAGGER | hip.RNN_KPAIR) and cell == 'lstm':
                     plain = hip.rnn_bwd(cell, c['dy'], got[0], c['wt'], got[4], c['sl'],
                                         workspace=got[5],
@@ -240,7 +240,7 @@ def test_every_variant_at_the_edge_shapes(hip, cell, hidden, variant, monkeypatc
                     ref = c['ref_dxw']
                     for blk, form in enumerate(forms):
                         rows = slice(32 * blk, min(batch, 32 * blk + 32))
-                        if 'k-pair' in form or form == 'prnn_bwd16k_kernel':
+                        if 'k-pair' in form:
                             e_pair = _row_err(dxw[:, rows], ref[:, rows])
                             e_plain = _row_err(plain[:, rows], ref[:, rows])
                             assert e_pair < 1.5 * e_plain + 2e-7, \
@@ -267,13 +267,12 @@ def test_every_variant_at_the_edge_shapes(hip, cell, hidden, variant, monkeypatc
         for num_steps in STEPS:
             took = {b for f, t, b, ragged in ran if f == form and t == num_steps and not ragged}
             assert batches <= took, (variant, num_steps, sorted(took))
-        # per-row lengths: the LSTM-1024 staggered / K-pair kernels are not taken
+        # per-row lengths: the LSTM-1024 staggered kernel is not taken
         if hidden == 1024:
             assert not {r for r in ran if r[0] == form and r[3]}
 
 
-@pytest.mark.parametrize('variant', VARIANTS)
-@pytest.mark.parametrize('cell,hidden', FAMILIES)
+@pytest.mark.parametrize('cell,hidden,variant', CASES)
 def test_one_workspace_down_to_a_single_step(hip, cell, hidden, variant, monkeypatch):
     """test_one_workspace_serves_every_shorter_pass down to T = 1 and out to two full row blocks:
     passes at T = 3, 1, 2, 3, 1 on ONE workspace created for T = 3, new data each pass (the T = 2
@@ -300,3 +299,55 @@ def test_one_workspace_down_to_a_single_step(hip, cell, hidden, variant, monkeyp
             want = p.run(fresh, fwd_flags, bwd_flags)
             hip.rnn_poll_error(cell, fresh, num_steps, batch, hidden)
             _assert_same_pass(got, want, (variant, batch, num_steps))
+
+
+def test_the_retired_variant_bit_is_a_bad_argument(hip):
+    """Value 8 of `flags` selected the reduce-scatter backward form up to ABI v7.  It is an unknown
+    bit now: both recurrence calls refuse it before anything is enqueued, outputs untouched."""
+    num_steps, batch, hidden = 2, 1, 64
+    g = torch.Generator(device=DEV).manual_seed(8)
+    xw = torch.randn(num_steps, batch, 2, 4 * hidden, device=DEV, generator=g)
+    w = torch.randn(2, 4 * hidden, hidden, device=DEV, generator=g) / np.sqrt(hidden)
+    dy = torch.randn(num_steps, batch, 2 * hidden, device=DEV, generator=g)
+    y, reserve, ws = hip.rnn_fwd('lstm', xw, w)
+    wt = hip.transpose_batched(w)
+    y_out = torch.full_like(y, 7.0)
+    reserve_out = torch.full_like(reserve, 7)
+    with pytest.raises(hip.CtcAsrError, match='bad argument'):
+        hip.rnn_fwd('lstm', xw, w, y=y_out, reserve=reserve_out, workspace=ws, flags=8)
+    dxw = torch.full((num_steps, batch, 2, 4 * hidden), 7.0, device=DEV)
+    dbias = torch.full((2 * 4 * hidden,), 7.0, device=DEV)
+    with pytest.raises(hip.CtcAsrError, match='bad argument'):
+        hip.rnn_bwd('lstm', dy, y, wt, reserve, dxw=dxw, dbias=dbias, workspace=ws, flags=8)
+    torch.cuda.synchronize()
+    assert bool((y_out == 7.0).all()) and bool((reserve_out == 7).all())
+    assert bool((dxw == 7.0).all()) and bool((dbias == 7.0).all())
+    # (the calls themselves are whole: the same arguments without the bit)
+    hip.rnn_bwd('lstm', dy, y, wt, reserve, dxw=dxw, dbias=dbias, workspace=ws)
+    assert torch.isfinite(dxw).all() and not bool((dxw == 7.0).all())
+
+
+def test_the_k_pair_bit_is_ignored_at_1024(hip):
+    """LSTM-1024 has no K-pair form: RNN_KPAIR changes nothing there.  At the smallest shape that
+    took the removed kernel (two tiles, rows a multiple of 8, no lengths) the call runs the
+    staggered kernel where RNN_STAGGER is set, else the one-barrier kernel - dxw, the bias
+    gradients and the column maxima bit for bit those of the same call without the bit."""
+    num_steps, batch, hidden = 3, 24, 1024
+    c = _case(hip, 'lstm', hidden, num_steps, batch, False)
+    base = hip.RNN_F16 | hip.RNN_XCD_SPLIT
+    y, reserve, ws = hip.rnn_fwd('lstm', c['xw'], c['w'], xw_bias=c['bias'], flags=base)
+
+    def run(flags):
+        dbias = torch.zeros(2 * 4 * hidden, device=DEV)
+        colmax = torch.zeros(2 * 4 * hidden, dtype=torch.int32, device=DEV)
+        dxw = torch.full((num_steps, batch, 2, 4 * hidden), float('nan'), device=DEV)
+        hip.rnn_bwd('lstm', c['dy'], y, c['wt'], reserve, dxw=dxw, dbias=dbias, workspace=ws,
+                    flags=flags, colmax=colmax)
+        hip.rnn_poll_error('lstm', ws, num_steps, batch, hidden)
+        return dxw, dbias, colmax
+
+    for flags in (base, base | hip.RNN_STAGGER):
+        want, got = run(flags), run(flags | hip.RNN_KPAIR)
+        assert torch.isfinite(want[0]).all()
+        for name, a, b in zip(('dxw', 'dbias', 'colmax'), got, want):
+            assert torch.equal(a, b), (flags, name)

@@ -26,8 +26,6 @@ def main():
     if os.environ.get('CTCASR_ONE_BARRIER'):   # B > 16: round-1 kernels (one barrier for both tiles)
         bwd_flags |= hip.RNN_ONE_BARRIER
         fwd_flags |= hip.RNN_ONE_BARRIER
-    if os.environ.get('CTCASR_RS'):            # backward: reduce-scatter form (LSTM-1024)
-        bwd_flags |= hip.RNN_REDUCE_SCATTER
     if os.environ.get('CTCASR_F16'):           # both recurrences on the fp16 matrix pipe
         fwd_flags |= hip.RNN_F16
         bwd_flags |= hip.RNN_F16
@@ -36,7 +34,7 @@ def main():
         bwd_flags |= hip.RNN_XCD_SPLIT
     if os.environ.get('CTCASR_STAGGER'):       # fp16 LSTM-1024 backward, 17..32 rows: staggered tiles
         bwd_flags |= hip.RNN_STAGGER
-    if os.environ.get('CTCASR_KPAIR'):         # ... with the K axis split over pairs of workgroups
+    if os.environ.get('CTCASR_KPAIR'):         # fp16 LSTM-2048 backward: the K axis split over pairs
         bwd_flags |= hip.RNN_KPAIR
     g = torch.Generator(device='cuda').manual_seed(0)
     xw = torch.randn(T, B, 2, G * H, device='cuda', generator=g) * 0.5
@@ -65,17 +63,7 @@ def main():
             base = state + 9216 + 256 + (0 if name == "fwd" else 32)   # SyncWords: counters, error
             words = ws[base: base + 32].cpu().numpy().view(np.uint64)
             labels = ['wait', 'loads+mfma', 'reduce+gates+publish', 'drain+arrive']
-            if name == 'bwd' and os.environ.get('CTCASR_RS'):
-                words = ws[base: base + 40].cpu().numpy().view(np.uint64)
-                labels = ['wait', 'partial loads+sum', 'gates+A operand', 'mfma+publish',
-                          'drain+arrive+dxw']
-            if name == 'bwd' and os.environ.get('CTCASR_KPAIR') and H == 1024:
-                words = ws[base: base + 72].cpu().numpy().view(np.uint64)
-                labels = ['marker wait', 'poll wait', 'main loops (rest)',
-                          'reduce+hand-off+gates+publish', 'spins x 100', 'of which hand-off wait',
-                          'wait for the first granules', 'request -> first granules',
-                          'request -> arrival point (all landed)']
-            elif name == 'bwd' and os.environ.get('CTCASR_STAGGER'):
+            if name == 'bwd' and os.environ.get('CTCASR_STAGGER'):
                 words = ws[base: base + 40].cpu().numpy().view(np.uint64)
                 labels = ['marker wait', 'poll wait', 'main loops (rest)', 'reduce+gates+publish',
                           'spins x 100']
@@ -88,24 +76,6 @@ def main():
                     np.round(more[0:4], 2).tolist(), more[4]))
                 print('  chain 1: {}  (partials+barrier inside phase 2: {:.2f})'.format(
                     np.round(more[8:12], 2).tolist(), more[12]))
-            if name == 'bwd' and os.environ.get('CTCASR_RS'):
-                every = ws[state + 9216 + 256 + 128: state + 9216 + 256 + 128 + 256 * 32] \
-                    .cpu().numpy().view(np.uint64).reshape(256, 4).astype(np.float64) / 100.0 / T
-                chains = 2 if B > 16 else 1
-                every = every[:128 * chains]
-                for ch in range(chains):
-                    part = every[ch::chains]
-                    print('    chain {} over 128 workgroups (us/step)'.format(ch))
-                    for k, label in enumerate(['wait', 'partial loads+sum', 'gates+mfma+publish',
-                                               'drain+arrive+dxw']):
-                        col = part[:, k]
-                        print('      {:<20s} min {:.2f}  median {:.2f}  max {:.2f}'.format(
-                            label, col.min(), np.median(col), col.max()))
-                    busy = part[:, 1] + part[:, 2] + part[:, 3]
-                    print('      busy (all but wait)  min {:.2f}  median {:.2f}  max {:.2f}; '
-                          'per blockIdx % 8: {}'.format(
-                              busy.min(), np.median(busy), busy.max(),
-                              np.round([busy[i::8].mean() for i in range(8)], 2).tolist()))
             if name == 'bwd' and H == 2048 and cell == 'lstm' and os.environ.get('CTCASR_F16'):
                 # (the last launch of the pass: tile 0 / the last tile, direction 1)
                 fbase = state + 9216 + 256
