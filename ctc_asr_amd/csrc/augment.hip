@@ -151,7 +151,9 @@ extern "C" int ctcasr_spec_augment(float *features, const int32_t *lengths, int 
                                    uint64_t seed, int n_freq, int freq_width, int n_time,
                                    int time_width, int time_permille, int32_t *intervals,
                                    ctcasr_stream_t stream) {
-    if (!features || !lengths || B < 1 || out_frames < 0) return CTCASR_ERR_BAD_ARGUMENT;
+    // an empty [B, 0, 80] buffer has no address to give: no cell of it is ever stored to
+    if ((!features && out_frames != 0) || !lengths || B < 1 || out_frames < 0)
+        return CTCASR_ERR_BAD_ARGUMENT;
     if (n_freq < 0 || n_freq > SA_MAX_MASKS || n_time < 0 || n_time > SA_MAX_MASKS)
         return CTCASR_ERR_BAD_ARGUMENT;
     if (freq_width < 0 || time_width < 0 || time_permille < 0 || time_permille > 1000)

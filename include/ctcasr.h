@@ -859,9 +859,12 @@ int ctcasr_features(const int16_t *pcm, const int32_t *num_samples, int B, int m
  *   under 'local' normalisation; under 'none' and 'local_scalar' zero is written all the same.
  *   intervals  optional int32 [B, n_freq + n_time, 2]: (start, width) of every mask, the
  *              frequency masks first; all zero for a row with L == 0.  May be NULL.
- * Errors (CTCASR_ERR_BAD_ARGUMENT, before any launch): null features / lengths, B < 1,
- * out_frames < 0, n_freq or n_time outside [0, CTCASR_SPEC_AUGMENT_MAX_MASKS], a negative width,
- * time_permille outside [0, 1000]; out_frames >= 2^24: CTCASR_ERR_UNSUPPORTED.
+ *   out_frames == 0 is served: every L is 0, nothing is stored to the features (which may then be
+ *   NULL, as the address of an empty buffer is) and `intervals` is written all zero.
+ * Errors (CTCASR_ERR_BAD_ARGUMENT, before any launch): null lengths, null features with
+ * out_frames > 0, B < 1, out_frames < 0, n_freq or n_time outside
+ * [0, CTCASR_SPEC_AUGMENT_MAX_MASKS], a negative width, time_permille outside [0, 1000];
+ * out_frames >= 2^24: CTCASR_ERR_UNSUPPORTED.
  * n_freq == n_time == 0 launches nothing.
  *
  * ctcasr_speed_perturb: band-limited resampling of each row by its own factor; percent[b] = P

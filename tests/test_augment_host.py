@@ -231,3 +231,137 @@ def test_float64_resampler_reproduces_a_sine(percent, measured):
     # at 100 % the reference is a copy, and its rounding is to nearest even with saturation
     assert np.array_equal(ref.speed_perturb(np.array([5, -7, 32767], dtype=np.int16), 100),
                           [5, -7, 32767])
+
+
+# ------------------------------------------------------------------------------------------
+# the fp32 restatement of the resampler (tests/augment_reference.py: speed_perturb_f32)
+def _round_to_f32(value):
+    """A nonzero Fraction rounded to the nearest fp32, ties to even, in integers (normal range)."""
+    from fractions import Fraction
+    sign, mag = (-1, -value) if value < 0 else (1, value)
+    e = mag.numerator.bit_length() - mag.denominator.bit_length()
+    if Fraction(2) ** e > mag:
+        e -= 1
+    assert Fraction(2) ** e <= mag < Fraction(2) ** (e + 1)
+    scaled = mag / Fraction(2) ** (e - 23)                   # in [2^23, 2^24)
+    whole = scaled.numerator // scaled.denominator
+    rest = scaled - whole
+    if rest > Fraction(1, 2) or (rest == Fraction(1, 2) and whole & 1):
+        whole += 1
+    return sign * float(whole * Fraction(2) ** (e - 23))
+
+
+def test_fma_f32_rounds_once():
+    """`fma_f32` against exact rational arithmetic: random operands of the kernel's ranges, and
+    products that sit exactly on an fp32 tie with an accumulator far below the last float64 bit
+    on either side of it - where a float64 sum rounded again to fp32 goes wrong."""
+    from fractions import Fraction
+    rng = np.random.default_rng(3)
+    a = rng.integers(-32768, 32768, size=600).astype(np.float64)
+    b = (rng.normal(size=600) * 0.3).astype(np.float32).astype(np.float64)
+    acc = (rng.normal(size=600) * 10.0 ** rng.integers(-3, 6, size=600)).astype(np.float32)
+    # a = 3, b = 1 + k 2^-23 with k odd: 3 b lies halfway between two fp32 values of [2, 4)
+    k = 2 * rng.integers(0, 1 << 21, size=200) + 1
+    a = np.concatenate([a, np.full(200, 3.0)])
+    b = np.concatenate([b, 1.0 + k * 2.0 ** -23])
+    tiny = np.where(rng.integers(0, 2, size=200) == 0, -1.0, 1.0) * 2.0 ** -60
+    acc = np.concatenate([acc.astype(np.float64), tiny])
+    assert np.array_equal(b, b.astype(np.float32).astype(np.float64))
+    got = ref.fma_f32(a, b, acc)
+    twice = (a * b + acc).astype(np.float32).astype(np.float64)
+    for i in range(len(a)):
+        exact = Fraction(a[i]) * Fraction(b[i]) + Fraction(acc[i])
+        want = _round_to_f32(exact) if exact else 0.0
+        assert got[i] == want, (a[i], b[i], acc[i])
+    assert (twice[600:] != got[600:]).any()                 # the crafted ties tell the two apart
+
+
+@pytest.fixture(scope='module')
+def every_percent():
+    """One full-scale random row of 257 samples at every percent: the restatement, its
+    accumulator and the float64 result."""
+    x = np.random.default_rng(7).integers(-32768, 32768, size=257).astype(np.int16)
+    return x, {p: ref.speed_perturb_f32(x, p) + (ref.speed_perturb(x, p),) for p in range(50, 201)}
+
+
+def test_restatement_is_within_one_lsb_of_float64_at_every_percent(every_percent):
+    """The existing budget (tests/test_gpu_augment.py) holds for the header's arithmetic itself,
+    at all 151 percents.  Seen on this row: largest difference 1 LSB, 0.11 % of samples differ."""
+    x, results = every_percent
+    differing = total = 0
+    for percent, (y, acc, want) in results.items():
+        assert len(y) == len(acc) == len(want) == ref.resample_num_samples(257, percent)
+        assert y.dtype == np.int16 and acc.dtype == np.float32
+        diff = np.abs(y.astype(np.int64) - want.astype(np.int64))
+        assert diff.max() <= 1, (percent, int(diff.max()))
+        differing += int((diff > 0).sum())
+        total += len(y)
+    assert np.array_equal(results[100][0], x) and np.array_equal(results[100][1], x)
+    print('restatement: {} of {} samples differ from float64 ({:.4%})'
+          .format(differing, total, differing / total))
+    assert 0 < differing < total // 100                     # fp32 is visible, and rare
+
+
+def test_restatement_rounds_to_even_and_saturates():
+    # one sample at 50 %: out[0] = x[0] h(0) with h(0) = c = 0.95, out[1] sits at t = 0.5
+    for value in (32767, -32768, 10, -10):
+        y, acc = ref.speed_perturb_f32(np.array([value], dtype=np.int16), 50)
+        want = np.float32(value) * np.float32(0.95)
+        assert len(y) == 2 and acc[0] == want and y[0] == np.rint(want)
+    square = (32767 * np.where((np.arange(400) // 20) % 2 == 0, 1, -1)).astype(np.int16)
+    y, acc = ref.speed_perturb_f32(square, 90)
+    assert acc.max() > 32768 and acc.min() < -32769
+    assert y.max() == 32767 and y.min() == -32768
+    assert ref.tie_eligible([0.5, -2.5, 7.515, 7.52, 3.0, -0.484375]).tolist() == \
+        [True, True, True, False, False, True]
+
+
+def test_kernel_tap_window_covers_the_filter():
+    """m in [-R, R + 1] loses nothing: for every percent and every phase a row reaches (the
+    multiples of gcd(P, 100)), sum |h| over the kernel's taps equals sum |h| over the wider walk of
+    `resample_float64`.  The largest is 2.17, at P = 50: the '< 3' of the error budget in
+    tests/test_gpu_augment.py holds at all percents."""
+    import math
+    largest = (0.0, None)
+    for percent in range(50, 201):
+        g = math.gcd(percent, 100)
+        phase = np.arange(0, 100, g) / 100.0
+        c = 95.0 / max(percent, 100)
+        radius = ref.tap_radius(percent)
+        assert 2 * radius + 2 <= 52 and (100 // g) * (2 * radius + 2) <= 5200
+        reach = int(np.ceil(12.0 / c)) + 2
+        assert reach > radius + 1
+        narrow = sum(np.abs(ref.tap_weight(c, phase - m)) for m in range(-radius, radius + 2))
+        wide = sum(np.abs(ref.tap_weight(c, phase - m)) for m in range(-reach, reach + 1))
+        assert np.abs(narrow - wide).max() <= 1e-12, percent
+        largest = max(largest, (float(wide.max()), -percent))
+    # (phase 0.5 at c = 0.95: every percent up to 100 that reaches it ties with P = 50)
+    assert largest[1] == -50 and 2.16 < largest[0] < 2.18
+    assert ref.tap_radius(199) == 25 and ref.tap_radius(200) == 25 and ref.tap_radius(100) == 12
+    assert sorted({ref.tap_radius(p) for p in range(101, 201)}) == list(range(12, 26))
+
+
+def test_seeds_put_the_masks_on_the_edges():
+    """The seeds tests/test_gpu_augment_edges.py relies on give the intervals it expects."""
+    for seed, want in ref.TIME_SEAM_SEEDS.items():
+        got = ref.mask_intervals(seed, [129], 129, 0, 27, 1, 200, 1000)
+        assert tuple(got[0, 0]) == want, seed
+    for seed, want in ref.FREQ_EDGE_SEEDS.items():
+        got = ref.mask_intervals(seed, [5], 5, 1, 27, 0, 200, 1000)
+        assert tuple(got[0, 0]) == want, seed
+    assert ref.TIME_SEAM_SEEDS[74][0] == 64 and sum(ref.TIME_SEAM_SEEDS[1263]) == 64
+    assert ref.TIME_SEAM_SEEDS[125] == (0, 129) and ref.TIME_SEAM_SEEDS[46192] == (128, 1)
+    assert ref.FREQ_EDGE_SEEDS[38][0] == 0 and sum(ref.FREQ_EDGE_SEEDS[45]) == 80
+    assert ref.TIME_SEAM_SEEDS[454][1] == 0 and ref.FREQ_EDGE_SEEDS[10][1] == 0
+
+
+def test_spec_augment_takes_no_features_only_for_no_frames(lib):
+    """An empty [B, 0, 80] buffer has a null address; the header serves out_frames == 0, so a
+    null `features` is an error only where there are frames.  (With masks to draw the call
+    launches: tests/test_gpu_augment_edges.py.)"""
+    buf = ctypes.create_string_buffer(64)
+    p = ctypes.addressof(buf)
+    assert lib.ctcasr_spec_augment(None, p, 3, 0, 7, 0, 27, 0, 100, 1000, None, None) == 0
+    assert lib.ctcasr_spec_augment(None, p, 3, 1, 7, 0, 27, 0, 100, 1000, None, None) == -1
+    assert lib.ctcasr_spec_augment(None, None, 3, 0, 7, 0, 27, 0, 100, 1000, None, None) == -1
+    assert lib.ctcasr_spec_augment(None, p, 3, -1, 7, 0, 27, 0, 100, 1000, None, None) == -1
