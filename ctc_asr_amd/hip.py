@@ -21,6 +21,7 @@ RNN_F16 = 16          # persistent LSTM / GRU kernels: the recurrent products as
 RNN_XCD_SPLIT = 32    # fp16-pipe kernels: one direction per half of the XCDs
 RNN_STAGGER = 64      # fp16-pipe LSTM-1024 backward, 24 / 32 rows: tiles staggered by half a step
 RNN_KPAIR = 128       # fp16-pipe LSTM-2048 backward: the K axis split over pairs of workgroups
+RESIDENT_GATE_MAX_US = 100000   # ctcasr_rnn_resident_gate: the longest bound it takes
 # ctcasr_grad_norm: floats per chunk of a segment, and the most segments a call takes
 GRAD_NORM_CHUNK = 8192
 GRAD_NORM_MAX_SEGMENTS = 64

@@ -385,6 +385,13 @@ class CTCModel:
     ``apply_gradients`` are the explicit counterparts of ``optimizer.minimize``."""
 
     def __init__(self, cfg, device='cuda', seed=0, params=None, conv_autotune=None, ema=False):
+        # (before anything touches the device: a bound the gate refuses would otherwise surface as
+        # `bad argument` from inside the first training step)
+        side_gate_max_us = int(os.environ.get('CTCASR_SIDE_GATE_US', '300'))
+        if side_gate_max_us > hip.RESIDENT_GATE_MAX_US:
+            raise ValueError('CTCASR_SIDE_GATE_US={}: a residency gate waits {} us at the most '
+                             '(0 disables the gates).'.format(side_gate_max_us,
+                                                              hip.RESIDENT_GATE_MAX_US))
         hip.load()
         # The reference's convolution stack (1 -> 32 -> 32 [-> 96] channels) runs entirely on this
         # package's own kernels - forward, data gradient and kernel gradient, any number of
@@ -425,7 +432,7 @@ class CTCModel:
         # behind a residency gate: the launch posts a ticket once all its workgroups hold their
         # CUs, a one-lane gate kernel on the side stream waits for it (at most this long; 0
         # disables the gates)
-        self.side_gate_max_us = int(os.environ.get('CTCASR_SIDE_GATE_US', '300'))
+        self.side_gate_max_us = side_gate_max_us
         self._ticket = 0
         # launches per persistent backward recurrence: the weight-gradient GEMMs of the steps one
         # launch has finished run beside the next launch instead of queueing up behind the layer.

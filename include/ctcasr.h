@@ -380,7 +380,20 @@ int ctcasr_rnn_poll_error(void *workspace, size_t workspace_bytes, int cell, int
 /* Enqueues a one-lane gate kernel on `stream` that returns as soon as the persistent launch that
  * carries CTCASR_RNN_TICKET(ticket) on this workspace has every workgroup running (or a later
  * ticket has been posted), and after `max_wait_us` (<= 100 ms) at the latest.  No-op for shapes
- * that take the streaming kernels. */
+ * that take the streaming kernels and for `max_wait_us` = 0.
+ * The predicate, exactly: with `seen` the ticket posted last on the workspace (0 in a zero-filled
+ * one), the gate opens iff  seen != 0 && ((seen - ticket) & 0xFFFFFF) < 0x800000.
+ *  - Staleness window: "posted at or after mine" reaches 2^23 - 1 tickets back.  A gate for a
+ *    ticket 2^23 or more ahead of `seen` - a workspace whose last post lies more than 2^23 of the
+ *    caller's tickets back - opens at once.  That costs the head start, never a result.
+ *  - A launch that finds the time-out word set (ctcasr_rnn_poll_error) leaves at once, but it
+ *    still posts its ticket first: a poisoned launch does not hold the work behind its gate for
+ *    the whole bound.
+ *  - A poll after a time-out zero-fills the barrier words, the posted ticket among them: the
+ *    workspace has then posted nothing, and gates for earlier tickets wait again.
+ * CTCASR_ERR_BAD_ARGUMENT for a ticket outside 1..2^24-1 or a bound outside 0..100000 us,
+ * CTCASR_ERR_WORKSPACE for a workspace smaller than ctcasr_rnn_workspace_bytes(); neither
+ * enqueues anything. */
 int ctcasr_rnn_resident_gate(void *workspace, size_t workspace_bytes, int cell, int T, int B,
                              int H, unsigned ticket, int max_wait_us, ctcasr_stream_t stream);
 int ctcasr_rnn_bwd(int cell, const float *dy, const float *y, const float *w_hh_t,
