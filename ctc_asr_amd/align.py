@@ -6,7 +6,9 @@ Restores the latest checkpoint in ``train_dir``, runs the model in evaluation mo
 (`CTCModel.align_fn`).  The manifest is read in file order, header dropped and every other row
 kept: this is not the training reader, so it has no ``[1:-1]`` quirk that drops the last row.
 Rows go through the model ``batch_size`` at a time.  A transcript with a character outside the
-alphabet raises ``ValueError``, as training does.
+alphabet raises ``ValueError``, as training does.  ``--resample_input`` takes recordings of any
+sampling rate, channel count and sample format (`input_functions.read_audio`); word times are in
+seconds either way.
 
 Output: one JSON object per manifest row, in manifest order::
 
@@ -29,7 +31,7 @@ import torch
 
 from ctc_asr_amd import alignment, storage
 from ctc_asr_amd.csv_helper import read_csv_rows
-from ctc_asr_amd.input_functions import features_from_pcm, read_wav
+from ctc_asr_amd.input_functions import features_from_files
 from ctc_asr_amd.labels import encode
 from ctc_asr_amd.model import CTCModel, ModelConfig
 from ctc_asr_amd.params import CSV_HEADER_LABEL, CSV_HEADER_PATH, FLAGS
@@ -41,8 +43,8 @@ def align_rows(model, rows, corpus_dir, batch_size, drop_every_second_frame=Fals
     for start in range(0, len(rows), batch_size):
         chunk = rows[start:start + batch_size]
         labels = [encode(row[CSV_HEADER_LABEL]) for row in chunk]
-        pcm = [read_wav(os.path.join(corpus_dir, row[CSV_HEADER_PATH])) for row in chunk]
-        feats, lengths = features_from_pcm(pcm, model.device)
+        paths = [os.path.join(corpus_dir, row[CSV_HEADER_PATH]) for row in chunk]
+        feats, lengths = features_from_files(paths, model.device)
         logits, seq_len = model.inference_fn(feats, lengths, training=False)
         model.check_rnn_error()
         path, score, frame_logp, status = model.align_fn(logits, seq_len, labels)

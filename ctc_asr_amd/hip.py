@@ -35,6 +35,9 @@ REVERB_MAX_TAPS = 8192          # ... and the longest response it serves
 VAD_HOP = 160                   # ctcasr_vad_energy: samples per hop (the feature step),
 VAD_LEVELS = 160                # ... bins of its level histogram,
 VAD_CHUNK = 40960               # ... and samples per workgroup
+RESAMPLE_MAX_TABLE = 16640      # ctcasr_resample: the most weights (L * taps) of a served rate pair,
+RESAMPLE_RATES = (4000, 192000)  # ... the rates it takes,
+RESAMPLE_MAX_CHANNELS = 8       # ... and the most channels it mixes down
 CELL_IDS = {'rnn_relu': 0, 'rnn_tanh': 1, 'lstm': 2, 'gru': 3}
 CELL_GATES = {'rnn_relu': 1, 'rnn_tanh': 1, 'lstm': 4, 'gru': 3}
 
@@ -162,6 +165,13 @@ SIGNATURES = {
                       [_c_p] * 3),
     'ctcasr_vad_energy': (_c_int, [_c_p, _c_i64, _c_p, _c_p, _c_p]),
     'ctcasr_gather_segments': (_c_int, [_c_p, _c_i64, _c_p, _c_p, _c_int, _c_int] + [_c_p] * 3),
+    'ctcasr_resample_plan': (_c_int, [_c_int, _c_int] + [_c_p] * 4),
+    'ctcasr_resample_chunk': (_c_int, [_c_int, _c_int]),
+    'ctcasr_resample_out_samples': (_c_i64, [_c_i64, _c_int, _c_int]),
+    'ctcasr_resample_table_bytes': (_c_sz, [_c_int, _c_int]),
+    'ctcasr_resample_table': (_c_int, [_c_int, _c_int, _c_p, _c_p]),
+    'ctcasr_resample': (_c_int, [_c_p, _c_int, _c_int, _c_i64, _c_int, _c_int, _c_p, _c_p, _c_i64,
+                                 _c_p, _c_p]),
     'ctcasr_adam_step': (_c_int, [_c_p] * 4 + [_c_i64] + [_c_f] * 4 + [_c_i64, _c_f, _c_p, _c_p]),
     'ctcasr_adam_step_clipped': (_c_int, [_c_p] * 4 + [_c_i64] + [_c_f] * 4 +
                                  [_c_i64, _c_f, _c_p, _c_p, _c_p]),
@@ -1994,3 +2004,104 @@ def gather_segments(pcm, seg_start, seg_len, max_samples=None, out=None, num_sam
         ptr, pcm.numel(), start_ptr, len_ptr, batch, max_samples, _dev(out, torch.int16, 'out'),
         _dev(num_samples, torch.int32, 'num_samples'), _stream()), 'gather_segments')
     return out, num_samples
+
+
+# format codes of ctcasr_resample (CTCASR_PCM_*), by the dtype scipy.io.wavfile reads a file as
+# (24-bit files come as int32, left-justified)
+RESAMPLE_FORMATS = {torch.int16: 0, torch.uint8: 1, torch.int32: 2, torch.float32: 3}
+_RESAMPLE_TABLES = {}
+
+
+def resample_plan(rate_in, rate_out=16000):
+    """(M, L, radius, taps) of a pair of rates: ``rate_in / rate_out = M / L`` in lowest terms and
+    the filter's ``2 * radius + 2`` taps (include/ctcasr.h, K19).  Raises `CtcAsrError` for a rate
+    outside 4000..192000 and for a pair whose table of ``L * taps`` weights is not served."""
+    out = [_c_int() for _ in range(4)]
+    _check(load().ctcasr_resample_plan(int(rate_in), int(rate_out),
+                                       *[ctypes.byref(v) for v in out]),
+           'resample_plan({}, {})'.format(rate_in, rate_out))
+    return tuple(v.value for v in out)
+
+
+def resample_chunk(rate_in, rate_out=16000):
+    """Consecutive outputs one workgroup of `resample` owns; 0 for a pair that is not served.
+    Informative - a tuning detail that may change with the kernel, and that no result depends on;
+    the tests use it to put recordings across the seams."""
+    return load().ctcasr_resample_chunk(int(rate_in), int(rate_out))
+
+
+def resample_out_samples(n, rate_in, rate_out=16000):
+    """Samples that ``n`` frames at ``rate_in`` come to at ``rate_out``: max(1, n * L // M); 0 for
+    n < 1, n > 2^31 - 1 or a pair of rates that is not served."""
+    return load().ctcasr_resample_out_samples(int(n), int(rate_in), int(rate_out))
+
+
+def resample_table(rate_in, rate_out, device):
+    """The filter weights of a pair of rates, float32 [L, taps] on ``device`` (flat, padded to 16
+    bytes): computed by one launch the first time a pair is asked for on a device - on the current
+    stream, which is synchronised once, so that the table may then be read from any stream - and
+    kept."""
+    device = torch.device(device)
+    if device.type != 'cuda':
+        raise CtcAsrError('resample_table: {} is no GPU; there is no CPU path.'.format(device))
+    if device.index is None:
+        device = torch.device('cuda', torch.cuda.current_device())
+    key = (int(rate_in), int(rate_out), device.index)
+    if key not in _RESAMPLE_TABLES:
+        resample_plan(rate_in, rate_out)          # (raises for a pair that is not served)
+        nbytes = load().ctcasr_resample_table_bytes(int(rate_in), int(rate_out))
+        with torch.cuda.device(device):
+            table = torch.empty(nbytes // 4, dtype=torch.float32, device=device)
+            _check(load().ctcasr_resample_table(int(rate_in), int(rate_out),
+                                                _dev(table, name='table'), _stream()),
+                   'resample_table')
+            # later calls may read the table from any stream: finish it before it is handed out
+            # (one synchronisation per pair of rates and device)
+            torch.cuda.current_stream().synchronize()
+        _RESAMPLE_TABLES[key] = table
+    return _RESAMPLE_TABLES[key]
+
+
+@_on_tensor_device
+def resample_launch(samples, rate_in, rate_out=16000):
+    """`resample` without the read-back: (int16 [n_out], status int32 [1]), both on the device.
+    Bit 0 of the status: a float32 sample was not finite."""
+    if samples.dim() not in (1, 2):
+        raise CtcAsrError('resample: samples must be [n] or [n, channels] (got {} dimensions).'
+                          .format(samples.dim()))
+    if samples.dtype not in RESAMPLE_FORMATS:
+        raise CtcAsrError('resample: samples are {}; uint8, int16, int32 and float32 are served.'
+                          .format(samples.dtype))
+    n = samples.shape[0]
+    channels = samples.shape[1] if samples.dim() == 2 else 1
+    if n < 1:
+        raise CtcAsrError('resample: the recording is empty.')
+    if not 1 <= channels <= RESAMPLE_MAX_CHANNELS:
+        raise CtcAsrError('resample: {} channels, 1..{} are served.'
+                          .format(channels, RESAMPLE_MAX_CHANNELS))
+    ptr = _dev(samples, samples.dtype, 'samples')
+    table = resample_table(rate_in, rate_out, samples.device)
+    n_out = resample_out_samples(n, rate_in, rate_out)
+    if n_out < 1:
+        raise CtcAsrError('resample: {} frames are more than the 2^31 - 1 served.'.format(n))
+    out = torch.empty(n_out, dtype=torch.int16, device=samples.device)
+    status = torch.empty(1, dtype=torch.int32, device=samples.device)
+    _check(load().ctcasr_resample(
+        ptr, RESAMPLE_FORMATS[samples.dtype], channels, n, int(rate_in), int(rate_out),
+        _dev(table, name='table'), _dev(out, torch.int16, 'out'), n_out,
+        _dev(status, torch.int32, 'status'), _stream()), 'resample')
+    return out, status
+
+
+def resample(samples, rate_in, rate_out=16000):
+    """One recording to int16 mono at ``rate_out``.  ``samples``: device tensor [n] or
+    [n, channels] (1..8, interleaved as in the file) of uint8, int16, int32 or float32 - the
+    layouts `scipy.io.wavfile.read` returns - at ``rate_in``.  Channels are averaged, the rate is
+    converted with a Hann-windowed sinc (include/ctcasr.h, K19); equal rates apply no filter, and
+    mono int16 then comes back bit for bit.  Returns int16 [max(1, n * L // M)] on the device.
+    Reads one status word back (a synchronisation) and raises ``ValueError`` for a float32
+    recording that holds a non-finite sample."""
+    out, status = resample_launch(samples, rate_in, rate_out)
+    if int(status.item()) & 1:
+        raise ValueError('resample: the recording holds a non-finite sample (NaN or infinity).')
+    return out

@@ -14,6 +14,12 @@ Reference quirks kept on purpose: the CSV slice ``[1:-1]`
 header and the LAST example; ``train_batch`` keeps CSV order and drops the remainder; bucketed
 targets shuffle, pad to the longest utterance of the batch and keep partial final batches;
 int16 PCM is not rescaled; padding (0.0) is appended after normalisation.
+
+``--resample_input`` (no counterpart in the reference): the tools that read single recordings -
+predict, transcribe, align, the noise and impulse-response banks - take WAV files of any rate,
+channel count and sample format through `read_audio`, converted on the device
+(``ctcasr_resample``).  The corpus readers here (`probe_wav`, the reader pool, the pinned staging
+buffers) never convert: manifest lengths, bucket boundaries and staging are in 16 kHz samples.
 """
 
 import bisect
@@ -78,6 +84,69 @@ def probe_wav(file_path):
     return count
 
 
+AUDIO_DTYPES = (np.uint8, np.int16, np.int32, np.float32)     # what `hip.resample` takes
+
+
+def load_audio(file_path):
+    """Host half of `read_audio`: (sampling rate, samples as ``wavfile.read`` returns them -
+    ``[n]`` or ``[n, channels]`` of uint8, int16, int32 (24-bit files too, left-justified) or
+    float32), checked for what `hip.resample` serves.  The length is checked after the
+    conversion, by `read_audio`."""
+    if not isinstance(file_path, str):
+        file_path = str(file_path, 'utf-8')
+    if not os.path.isfile(file_path):
+        raise ValueError('"{}" does not exist.'.format(file_path))
+    sampling_rate, audio = wavfile.read(file_path)
+    if audio.dtype == np.float64:
+        raise RuntimeError('float64 WAV files are not supported: {}'.format(file_path))
+    if audio.dtype not in AUDIO_DTYPES:
+        raise RuntimeError('WAV files of {} samples are not supported: {}'
+                           .format(audio.dtype, file_path))
+    if audio.ndim == 2 and audio.shape[1] > hip.RESAMPLE_MAX_CHANNELS:
+        raise RuntimeError('More than {} channels ({}) are not supported: {}'
+                           .format(hip.RESAMPLE_MAX_CHANNELS, audio.shape[1], file_path))
+    low, high = hip.RESAMPLE_RATES
+    if not low <= sampling_rate <= high:
+        raise RuntimeError('Sampling rate is {:,d}, {:,d} to {:,d} can be converted: {}'
+                           .format(sampling_rate, low, high, file_path))
+    try:
+        hip.resample_plan(sampling_rate, FLAGS.sampling_rate)
+    except hip.CtcAsrError:
+        raise RuntimeError('Sampling rate {:,d} has no small ratio to {:,d} and cannot be '
+                           'converted: {}'.format(sampling_rate, FLAGS.sampling_rate, file_path))
+    return sampling_rate, audio
+
+
+def upload_audio(sampling_rate, audio, device, file_path=''):
+    """Device half of `read_audio`: one upload of ``audio`` in the file's own layout, then
+    `hip.resample` to ``FLAGS.sampling_rate`` -> int16 ``[n_out]`` device tensor."""
+    n_out = hip.resample_out_samples(len(audio), sampling_rate, FLAGS.sampling_rate)
+    if n_out < 401:
+        raise RuntimeError('Sample length {:,d} to short: {}'.format(n_out, file_path))
+    samples = torch.from_numpy(np.ascontiguousarray(audio)).to(device)
+    return hip.resample(samples, sampling_rate, FLAGS.sampling_rate)
+
+
+def read_audio(file_path, device='cuda'):
+    """Any WAV file ``wavfile.read`` opens, as 16 kHz (``FLAGS.sampling_rate``) mono int16 on the
+    device: what `read_wav` returns for a file that already is that - the same samples, bit for
+    bit - and the converted recording for every other (``--resample_input``).  The samples are
+    uploaded once, as they are in the file, and converted there.  Refused by name: float64
+    files, more than 8 channels, a rate outside 4..192 kHz or without a small ratio to the
+    target, a recording of fewer than 401 samples AFTER the conversion, and (``ValueError``)
+    float32 samples that are not finite."""
+    sampling_rate, audio = load_audio(file_path)
+    return upload_audio(sampling_rate, audio, device, file_path)
+
+
+def read_pcm_host(file_path, device='cuda'):
+    """int16 ndarray of one recording for the banks that are assembled on the host: `read_wav`,
+    or under ``--resample_input`` `read_audio` copied back (once per run)."""
+    if FLAGS.resample_input:
+        return read_audio(file_path, device).cpu().numpy()
+    return read_wav(file_path)
+
+
 def num_frames(num_samples, drop_every_second_frame=None):
     """Feature frames of an utterance of ``num_samples`` samples (after the optional drop)."""
     drop = FLAGS.features_drop_every_second_frame if drop_every_second_frame is None \
@@ -109,6 +178,29 @@ def features_from_pcm(pcm_list, device='cuda', feature_type=None, feature_normal
     return hip.features(torch.from_numpy(batch).to(device), torch.from_numpy(lengths).to(device),
                         feature_type, feature_normalization,
                         FLAGS.features_drop_every_second_frame, FLAGS.sampling_rate)
+
+
+def features_from_device_pcm(pcm_list, feature_type=None, feature_normalization=None):
+    """`features_from_pcm` for int16 device tensors (what `read_audio` returns): the zero-padded
+    batch is assembled on the device, the samples never come back to the host."""
+    feature_type, feature_normalization = _check_feature_args(feature_type,
+                                                              feature_normalization)
+    device = pcm_list[0].device
+    lengths = [int(p.numel()) for p in pcm_list]
+    batch = torch.zeros((len(pcm_list), max(lengths)), dtype=torch.int16, device=device)
+    for row, pcm in enumerate(pcm_list):
+        batch[row, :lengths[row]] = pcm
+    return hip.features(batch, torch.tensor(lengths, dtype=torch.int32, device=device),
+                        feature_type, feature_normalization,
+                        FLAGS.features_drop_every_second_frame, FLAGS.sampling_rate)
+
+
+def features_from_files(paths, device='cuda'):
+    """Features of a batch of WAV files for the drivers that read single recordings (predict,
+    align): `read_wav` and its refusals, or under ``--resample_input`` `read_audio`."""
+    if FLAGS.resample_input:
+        return features_from_device_pcm([read_audio(path, device) for path in paths])
+    return features_from_pcm([read_wav(path) for path in paths], device)
 
 
 _RINGS = {}      # the live staging ring per (device, depth, batch size)

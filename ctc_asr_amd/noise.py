@@ -14,15 +14,18 @@ from ctc_asr_amd.params import CSV_HEADER_PATH, FLAGS
 MAX_CLIP_SAMPLES = 1 << 24       # the longest clip ctcasr_noise_mix serves (its offset draw)
 
 
-def load_clips(csv_path, noise_dir, max_seconds):
+def load_clips(csv_path, noise_dir, max_seconds, device='cuda'):
     """(int16 ndarray of all clips back to back, int64 offsets [clips + 1]).
 
     Every row after the header is read (labels and lengths are ignored), in file order, with
     `input_functions.read_wav` and its checks (16 kHz, mono, int16); paths are relative to
-    ``noise_dir``.  A recording longer than `MAX_CLIP_SAMPLES` becomes several clips.  Reading
-    stops once ``max_seconds`` of audio are held; the recording that crosses the mark is cut at
-    it.  A manifest that yields no sample is refused."""
-    from ctc_asr_amd.input_functions import read_wav
+    ``noise_dir``.  Under ``--resample_input`` a recording of any rate, channel count and format
+    is converted on ``device`` (`input_functions.read_audio`) and copied back for the assembly
+    here, once per run; ``max_seconds`` counts converted audio.  A recording longer than
+    `MAX_CLIP_SAMPLES` becomes several clips.  Reading stops once ``max_seconds`` of audio are
+    held; the recording that crosses the mark is cut at it.  A manifest that yields no sample is
+    refused."""
+    from ctc_asr_amd.input_functions import read_pcm_host
     if max_seconds < 1:
         raise ValueError('load_clips: max_seconds is {}, at least 1 needed.'.format(max_seconds))
     budget = int(max_seconds) * int(FLAGS.sampling_rate)
@@ -30,7 +33,7 @@ def load_clips(csv_path, noise_dir, max_seconds):
     for row in read_csv_rows(csv_path)[1:]:
         if budget <= 0:
             break
-        audio = read_wav(os.path.join(noise_dir, row[CSV_HEADER_PATH]))[:budget]
+        audio = read_pcm_host(os.path.join(noise_dir, row[CSV_HEADER_PATH]), device)[:budget]
         budget -= len(audio)
         for start in range(0, len(audio), MAX_CLIP_SAMPLES):
             piece = audio[start:start + MAX_CLIP_SAMPLES]
@@ -58,7 +61,7 @@ class NoiseBank:
             device = torch.device('cuda', torch.cuda.current_device())
         key = (os.path.abspath(csv_path), os.path.abspath(noise_dir), int(max_seconds), str(device))
         if key not in _BANKS:
-            _BANKS[key] = cls(*load_clips(csv_path, noise_dir, max_seconds), device)
+            _BANKS[key] = cls(*load_clips(csv_path, noise_dir, max_seconds, device), device)
         return _BANKS[key]
 
     @classmethod

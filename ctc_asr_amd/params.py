@@ -431,6 +431,15 @@ FLAGS.define('float', 'dense_dropout_rate', 0.1, 'Drop probability after each de
 FLAGS.define('int', 'num_buckets', 96, 'Upper bound on length buckets.')
 FLAGS.define('int', 'num_classes', num_classes(), 'Alphabet size + unused id 0 + CTC blank.')
 FLAGS.define('int', 'sampling_rate', 16000, 'Expected WAV sampling rate in Hz.')
+# Any WAV for the tools that read single recordings (no counterpart in the reference, whose corpus
+# is 16 kHz mono int16; off: every reader refuses anything else, as it always did).  predict,
+# transcribe, align, the noise bank and the impulse-response bank then read through
+# `input_functions.read_audio`: rate conversion and channel downmix on the device
+# (ctcasr_resample).  The train / dev / test readers never convert.
+FLAGS.define('bool', 'resample_input', False,
+             'predict / transcribe / align / --noise_csv / --rir_csv: take WAV files of any '
+             'sampling rate (4..192 kHz), 1..8 channels, 8 / 16 / 24 / 32-bit PCM or float32, '
+             'converted to --sampling_rate mono int16 on the device.')
 
 # Performance / GPU (asr/params.py:105-112).  `cudnn=True` selects the fused recurrent kernels
 # with cuDNN semantics (no sequence lengths); False selects the length-aware tanh-RNN semantics of

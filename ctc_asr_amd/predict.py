@@ -8,7 +8,8 @@ the timestamps are then those of the text it decoded.  ``--nbest N`` adds ``'nbe
 in first-pass order (``logp``: the beam's total; ``ctc_logp``: the exact ln p(y | x)), and
 ``'confidence'``, the posterior of the printed hypothesis.  That is rank 0 - what is printed
 without the flag - unless ``--rescore_lm_path`` re-ranks the list: then the selected hypothesis
-is printed, and ``--timestamps`` aligns its text."""
+is printed, and ``--timestamps`` aligns its text.  ``--resample_input`` takes a file of any
+sampling rate, channel count and sample format (`input_functions.read_audio`)."""
 
 import os
 import sys
@@ -17,13 +18,13 @@ import numpy as np
 import torch
 
 from ctc_asr_amd import alignment, lm, storage
-from ctc_asr_amd.input_functions import features_from_pcm, read_wav
+from ctc_asr_amd.input_functions import features_from_files
 from ctc_asr_amd.model import CTCModel, ModelConfig
 from ctc_asr_amd.params import FLAGS
 
 
 def predict(model, wav_path, timestamps=False, scorer=None, nbest=0, rescorer=None):
-    feats, lengths = features_from_pcm([read_wav(wav_path)], model.device)
+    feats, lengths = features_from_files([wav_path], model.device)
     logits, seq_len = model.inference_fn(feats, lengths, training=False)
     model.check_rnn_error()
     if nbest:

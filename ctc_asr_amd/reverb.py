@@ -64,18 +64,20 @@ def quantise_rir(h, max_taps=MAX_TAPS, name='impulse response'):
     return padded, delay, scale
 
 
-def load_rirs(csv_path, rir_dir, max_taps=MAX_TAPS):
+def load_rirs(csv_path, rir_dir, max_taps=MAX_TAPS, device='cuda'):
     """(int16 taps of all responses back to back, int64 offsets [R + 1], int32 delay [R],
     float32 scale [R]).
 
     Every row after the header is read (labels and lengths are ignored), in file order, with
     `input_functions.read_wav` and its checks (16 kHz, mono, int16); paths are relative to
-    ``rir_dir``.  A manifest without a row and a silent recording are refused."""
-    from ctc_asr_amd.input_functions import read_wav
+    ``rir_dir``.  Under ``--resample_input`` a response of any rate, channel count and format is
+    converted on ``device`` (`input_functions.read_audio`) and copied back for the quantisation
+    here, once per run.  A manifest without a row and a silent recording are refused."""
+    from ctc_asr_amd.input_functions import read_pcm_host
     pieces, offsets, delays, scales = [], [0], [], []
     for row in read_csv_rows(csv_path)[1:]:
         path = os.path.join(rir_dir, row[CSV_HEADER_PATH])
-        taps, delay, scale = quantise_rir(read_wav(path), max_taps, path)
+        taps, delay, scale = quantise_rir(read_pcm_host(path, device), max_taps, path)
         pieces.append(taps)
         offsets.append(offsets[-1] + len(taps))
         delays.append(delay)
@@ -106,7 +108,7 @@ class RirBank:
             device = torch.device('cuda', torch.cuda.current_device())
         key = (os.path.abspath(csv_path), os.path.abspath(rir_dir), int(max_taps), str(device))
         if key not in _BANKS:
-            _BANKS[key] = cls(*load_rirs(csv_path, rir_dir, max_taps), device)
+            _BANKS[key] = cls(*load_rirs(csv_path, rir_dir, max_taps, device), device)
         return _BANKS[key]
 
     @classmethod

@@ -5,7 +5,9 @@
 recording is uploaded once, cut at its pauses (`vad.segment`: one pass over the PCM on the
 MI355X, the decision on the host), and the pieces go through the model in batches:
 
-1. ``read_wav``, one upload of the PCM;
+1. ``read_wav``, one upload of the PCM (under ``--resample_input``: any WAV, uploaded in its own
+   layout and converted to 16 kHz mono int16 by ``hip.resample``; every length and time below is
+   then counted on the converted recording, and times stay seconds of the recording);
 2. ``vad.segment`` -> the table of pieces ``(start, length)`` in samples, in time order;
 3. pieces ordered by length, longest first (ties in time order), ``--batch_size`` to a batch, so
    that a batch pads little;
@@ -29,7 +31,7 @@ import numpy as np
 import torch
 
 from ctc_asr_amd import alignment, hip, lm, storage, vad
-from ctc_asr_amd.input_functions import _check_feature_args, read_wav
+from ctc_asr_amd.input_functions import _check_feature_args, load_audio, read_wav, upload_audio
 from ctc_asr_amd.model import CTCModel, ModelConfig
 from ctc_asr_amd.params import FLAGS
 
@@ -95,9 +97,15 @@ def transcribe(model, wav_path, timestamps=False, scorer=None, nbest=0, settings
     settings = vad.VadSettings.from_flags(FLAGS) if settings is None else settings
     batch_size = FLAGS.batch_size if batch_size is None else int(batch_size)
     feature_type, normalization = _check_feature_args(None, None)
-    audio = read_wav(wav_path)
-    clock = _Clock(timings)
-    pcm = torch.from_numpy(np.ascontiguousarray(audio)).to(model.device)
+    if FLAGS.resample_input:
+        # the file's own layout goes up once and is converted there ('upload' holds both)
+        rate, audio = load_audio(wav_path)
+        clock = _Clock(timings)
+        pcm = upload_audio(rate, audio, model.device, wav_path)
+    else:
+        audio = read_wav(wav_path)
+        clock = _Clock(timings)
+        pcm = torch.from_numpy(np.ascontiguousarray(audio)).to(model.device)
     clock.lap('upload')
     start, length, threshold = vad.segment(pcm, settings)
     clock.lap('segmentation')
@@ -146,7 +154,7 @@ def transcribe(model, wav_path, timestamps=False, scorer=None, nbest=0, settings
         decode_pending()
     if report is not None:
         report.update(start=start, length=length, threshold=threshold, decoded=labels)
-    return assemble(start, length, texts, len(audio), words if timestamps else None,
+    return assemble(start, length, texts, int(pcm.numel()), words if timestamps else None,
                     FLAGS.sampling_rate)
 
 

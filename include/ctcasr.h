@@ -1060,6 +1060,84 @@ int ctcasr_gather_segments(const int16_t *pcm, int64_t n, const int64_t *seg_sta
                            const int32_t *seg_len, int B, int max_samples, int16_t *out,
                            int32_t *num_samples, ctcasr_stream_t stream);
 
+/* ---- K19: sampling-rate conversion and channel downmix ---------------------------------------
+ * No counterpart in the reference (its corpus is 16 kHz mono int16).  One recording of interleaved
+ * PCM in the layout of its file - any of four sample formats, 1..8 channels, rate_in - becomes
+ * int16 mono at rate_out.  The filter is that of ctcasr_speed_perturb at the ratio of the two
+ * rates; that kernel's rule is the special case L = 100, M = P.  (These entry points were added
+ * without a change of CTCASR_ABI_VERSION: they break no caller.)
+ *
+ * Plan (ctcasr_resample_plan, pure host arithmetic):
+ *   g = gcd(rate_in, rate_out), M = rate_in / g, L = rate_out / g, S = max(M, L)
+ *   c = 95 L / (100 S) in fp64                    (0.95 * min(1, L / M): the cut-off)
+ *   R = (1200 S) / (95 L) (integer division), taps = 2 R + 2
+ *   Rates within [4000, 192000] are served (else CTCASR_ERR_BAD_ARGUMENT), and of those the pairs
+ *   with L * taps <= CTCASR_RESAMPLE_MAX_TABLE (else CTCASR_ERR_UNSUPPORTED): to 16 000 Hz,
+ *     rate_in   8000  11025  12000  22050  24000  32000  44100  48000  88200  96000  192000
+ *     M            1    441      3    441      3      2    441      3    441      6      12
+ *     L            2    640      4    320      2      1    160      1     80      1       1
+ *     R           12     12     12     17     18     25     34     37     69     75     151
+ *     taps        26     26     26     36     38     52     70     76    140    152     304
+ *   16 001 -> 16 000 would need 416 000 weights and is not served.  A pair whose table and the
+ *   input span of 256 outputs do not fit a workgroup's LDS together is not served either (none of
+ *   the rates above; 192 000 -> 4000 still is).
+ * Count (ctcasr_resample_out_samples, pure host arithmetic):
+ *   n_out = max(1, n * L / M) (integer division in 64 bits); 0 for n < 1, n > 2^31 - 1 or a pair
+ *   that is not served.
+ * Weights (ctcasr_resample_table): table float [L][taps] in DEVICE memory, 16-byte aligned,
+ *   ctcasr_resample_table_bytes(rate_in, rate_out) bytes (L * taps floats rounded up to 16 bytes,
+ *   the pad zero; 0 for a pair that is not served).  Entry (p, i) = h(p / L - (i - R)) with h and
+ *   sinc exactly as in the ctcasr_speed_perturb block above (K15) and the c of the plan, evaluated
+ *   in fp64 and rounded once to fp32, in a launch of its own: once per pair of rates.  The
+ *   resampling kernel never evaluates a sine.
+ * Frame value s[k], k in [0, n): the fp32 sum over the frame's channels, in ascending channel
+ *   order (the first channel's value, then one fp32 addition per further channel), of
+ *     CTCASR_PCM_S16  int16                (float)x
+ *     CTCASR_PCM_U8   uint8                (float)((x - 128) * 256)
+ *     CTCASR_PCM_S32  int32                (float)x * 0x1p-16f    (24-bit files, left-justified
+ *                                                                   in 32 bits, are this format)
+ *     CTCASR_PCM_F32  float32              x * 32768.0f
+ *   and s[k] = 0 outside [0, n).  `in` holds n frames of `channels` samples, interleaved, at any
+ *   address aligned to one sample (a slice of a tensor); it is read through aligned 16-byte loads
+ *   whatever its alignment and frame size (6 bytes for three int16 channels), with the same
+ *   results.  Only read.
+ * Output j in [0, n_out): pos = j * M in 64 bits, t0 = pos / L, p = pos % L;
+ *   acc = +0.0f; for i = 0 .. taps - 1: acc = fmaf(s[t0 - R + i], table[p][i], acc);
+ *   out[j] = sat16(rintf(acc * gain)), gain = (float)(1.0 / channels), sat16 the clamp to
+ *   [-32768, 32767], rintf to nearest even.
+ *   M == L (rate_in == rate_out): no filter, out[j] = sat16(rintf(s[j] * gain)); mono int16 input
+ *   comes back bit for bit.  (`table` is not read then, but may not be NULL.)
+ *   Only out[0 .. n_out) is written.  n_out must be ctcasr_resample_out_samples(n, rate_in,
+ *   rate_out), else CTCASR_ERR_BAD_ARGUMENT.
+ * status int32 [1], device: cleared by a memset on the stream, then bit 0 is raised (an integer
+ *   atomic OR) when a CTCASR_PCM_F32 sample of a frame in [0, n) is not finite.  Outputs whose
+ *   taps touch such a frame are unspecified; all others are what they would be without it.
+ * One launch behind the memset.  A workgroup owns ctcasr_resample_chunk(rate_in, rate_out)
+ * consecutive outputs (2048, 1024, 512 or 256, the most that fit LDS with the table; 0 for a pair
+ * that is not served): it copies the table into LDS, downmixes its span of input once into an
+ * fp32 tile in LDS and runs the taps from there.  Every output is computed by the same operations
+ * in the same order wherever it falls: the result does not depend on the grid.  No float atomics.
+ * ctcasr_resample_chunk is INFORMATIVE, not a contract: the run per workgroup is a tuning detail
+ * that may change with the kernel, no caller needs it to size anything, and no result depends on
+ * it.  It is exported so that tests can put recordings across the seams of the kernel as built.
+ * Errors, before any launch: a null pointer, a format outside 0..3, channels outside 1..8, n < 1,
+ * a rate outside [4000, 192000], `in` / `table` / `out` / `status` not aligned to 1 sample / 16 /
+ * 2 / 4 bytes, a wrong n_out: CTCASR_ERR_BAD_ARGUMENT; a pair that is not served or n > 2^31 - 1:
+ * CTCASR_ERR_UNSUPPORTED. */
+#define CTCASR_RESAMPLE_MAX_TABLE 16640      /* 640 x 26: the table of 11 025 -> 16 000 */
+#define CTCASR_PCM_S16 0
+#define CTCASR_PCM_U8 1
+#define CTCASR_PCM_S32 2
+#define CTCASR_PCM_F32 3
+int ctcasr_resample_plan(int rate_in, int rate_out, int *M, int *L, int *radius, int *taps);
+int ctcasr_resample_chunk(int rate_in, int rate_out);
+int64_t ctcasr_resample_out_samples(int64_t n, int rate_in, int rate_out);
+size_t ctcasr_resample_table_bytes(int rate_in, int rate_out);
+int ctcasr_resample_table(int rate_in, int rate_out, float *table, ctcasr_stream_t stream);
+int ctcasr_resample(const void *in, int format, int channels, int64_t n, int rate_in, int rate_out,
+                    const float *table, int16_t *out, int64_t n_out, int32_t *status,
+                    ctcasr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
