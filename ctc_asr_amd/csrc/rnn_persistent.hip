@@ -3312,6 +3312,7 @@ size_t prnn_sync_bytes() { return sizeof(SyncWords); }
 // per-call argument (`flags` of ctcasr_rnn_fwd_steps / _bwd_steps).
 void wgrad16_set_spin_limit(long polls);      // (wgrad16.hip)
 extern int g_grad_norm_blocks;                // (grad_norm.hip)
+extern int g_seq_bn_blocks;                   // (seq_bn.hip)
 extern "C" int ctcasr_set_option(const char *name, int value) {
     if (!name) return CTCASR_ERR_BAD_ARGUMENT;
     if (strcmp(name, "rnn_kernel_events") == 0) { g_kernel_events = value ? 1 : 0; return CTCASR_OK; }
@@ -3319,6 +3320,11 @@ extern "C" int ctcasr_set_option(const char *name, int value) {
     if (strcmp(name, "grad_norm_blocks") == 0) {
         if (value < 0 || value > 65536) return CTCASR_ERR_BAD_ARGUMENT;
         g_grad_norm_blocks = value;
+        return CTCASR_OK;
+    }
+    if (strcmp(name, "seq_bn_blocks") == 0) {
+        if (value < 0 || value > 65536) return CTCASR_ERR_BAD_ARGUMENT;
+        g_seq_bn_blocks = value;
         return CTCASR_OK;
     }
     return CTCASR_ERR_BAD_ARGUMENT;

@@ -38,11 +38,13 @@ VAD_CHUNK = 40960               # ... and samples per workgroup
 RESAMPLE_MAX_TABLE = 16640      # ctcasr_resample: the most weights (L * taps) of a served rate pair,
 RESAMPLE_RATES = (4000, 192000)  # ... the rates it takes,
 RESAMPLE_MAX_CHANNELS = 8       # ... and the most channels it mixes down
+SEQ_BN_ROWS = 64                # ctcasr_seq_bn_*: consecutive rows per chunk of the pinned sums
 CELL_IDS = {'rnn_relu': 0, 'rnn_tanh': 1, 'lstm': 2, 'gru': 3}
 CELL_GATES = {'rnn_relu': 1, 'rnn_tanh': 1, 'lstm': 4, 'gru': 3}
 
 _c_int, _c_i64, _c_u64 = ctypes.c_int, ctypes.c_int64, ctypes.c_uint64
 _c_f, _c_p, _c_sz = ctypes.c_float, ctypes.c_void_p, ctypes.c_size_t
+_c_d = ctypes.c_double
 
 # name -> (restype, argtypes); doubles as the list of symbols the ABI must export
 SIGNATURES = {
@@ -180,6 +182,13 @@ SIGNATURES = {
     'ctcasr_grad_norm_workspace_bytes': (_c_sz, [_c_i64, _c_int]),
     'ctcasr_grad_norm': (_c_int, [_c_p, _c_i64, _c_p, _c_int, _c_f, _c_f] + [_c_p] * 4 +
                          [_c_sz, _c_p]),
+    'ctcasr_seq_bn_workspace_bytes': (_c_sz, [_c_i64, _c_int]),
+    'ctcasr_seq_bn_fwd': (_c_int, [_c_p, _c_p, _c_int, _c_int, _c_int] + [_c_p] * 4 +
+                          [_c_d, _c_d] + [_c_p] * 4 + [_c_sz, _c_p]),
+    'ctcasr_seq_bn_infer': (_c_int, [_c_p, _c_p, _c_int, _c_int, _c_int] + [_c_p] * 4 +
+                            [_c_d, _c_p, _c_p]),
+    'ctcasr_seq_bn_bwd': (_c_int, [_c_p, _c_p, _c_p, _c_int, _c_int, _c_int] + [_c_p] * 7 +
+                          [_c_sz, _c_p]),
     'ctcasr_step_guard': (_c_int, [_c_p, _c_p, _c_int, _c_p, _c_p, _c_p, _c_p, _c_p]),
     'ctcasr_rnn_timeout_word_offset': (_c_sz, [_c_int] * 5),
     'ctcasr_absmax': (_c_int, [_c_p, _c_i64, _c_p, _c_p]),
@@ -1662,6 +1671,102 @@ def grad_norm(grad, seg_offsets, grad_scale=1.0, max_norm=0.0, skip=None, out=No
                                    _dev(workspace, torch.uint8, 'workspace'), workspace.numel(),
                                    _stream()), 'grad_norm')
     return out[:segments + 1], out[segments + 1:]
+
+
+def seq_bn_workspace_bytes(rows, channels):
+    return load().ctcasr_seq_bn_workspace_bytes(int(rows), int(channels))
+
+
+def _seq_bn_shape(what, x, lengths, per_channel):
+    """(T, B, C) of a ``seq_bn_*`` call; refuses what the kernels would index out of bounds."""
+    if x.dim() != 3:
+        raise CtcAsrError('{}: x must be [T, B, C] (got {} dimensions).'.format(what, x.dim()))
+    steps, batch, channels = x.shape
+    if channels < 4 or channels % 4 != 0:
+        raise CtcAsrError('{}: {} channels; a multiple of 4 is needed.'.format(what, channels))
+    if steps < 1 or batch < 1:
+        raise CtcAsrError('{}: x is empty (shape {}).'.format(what, tuple(x.shape)))
+    if lengths is not None:
+        _expect_numel(what, 'lengths', lengths, batch)
+    for name, tensor in per_channel:
+        _expect_numel(what, name, tensor, channels)
+    return steps, batch, channels
+
+
+def _seq_bn_workspace(what, workspace, rows, channels, device):
+    need = seq_bn_workspace_bytes(rows, channels)
+    if workspace is None:
+        return _workspace(need, device)
+    if workspace.numel() < need:
+        raise CtcAsrError('{}: workspace holds {} bytes, {} needed.'
+                          .format(what, workspace.numel(), need))
+    return workspace
+
+
+@_on_tensor_device
+def seq_bn_fwd(x, lengths, gamma, beta, running_mean, running_var, decay, eps, workspace=None):
+    """Sequence-wise batch normalisation, training mode: ``x`` float32 [T, B, C] is normalised
+    per channel over the counted rows - row (t, b) counts when ``lengths`` (int32 [B]) is None or
+    ``t < clamp(lengths[b], 0, T)`` - with statistics summed in float64 in a fixed order.
+    Returns ``(y, mean, rstd)``: y = (x - mean) * (gamma * rstd) + beta on counted rows and +0
+    elsewhere; ``mean`` / ``rstd`` float32 [C] are what `seq_bn_bwd` takes.  Moves
+    ``running_mean`` / ``running_var`` (float32 [C], in place) by
+    ``decay * running + (1 - decay) * batch``; a channel with non-finite statistics, and a batch
+    without a counted row, leave them alone."""
+    steps, batch, channels = _seq_bn_shape(
+        'seq_bn_fwd', x, lengths, (('gamma', gamma), ('beta', beta),
+                                   ('running_mean', running_mean), ('running_var', running_var)))
+    workspace = _seq_bn_workspace('seq_bn_fwd', workspace, steps * batch, channels, x.device)
+    y = torch.empty_like(x)
+    mean = torch.empty(channels, dtype=torch.float32, device=x.device)
+    rstd = torch.empty(channels, dtype=torch.float32, device=x.device)
+    _check(load().ctcasr_seq_bn_fwd(
+        _dev(x, name='x'), _dev(lengths, torch.int32, 'lengths'), steps, batch, channels,
+        _dev(gamma, name='gamma'), _dev(beta, name='beta'),
+        _dev(running_mean, name='running_mean'), _dev(running_var, name='running_var'),
+        float(decay), float(eps), _dev(y, name='y'), _dev(mean, name='mean'),
+        _dev(rstd, name='rstd'), _dev(workspace, torch.uint8, 'workspace'), workspace.numel(),
+        _stream()), 'seq_bn_fwd')
+    return y, mean, rstd
+
+
+@_on_tensor_device
+def seq_bn_infer(x, lengths, gamma, beta, running_mean, running_var, eps):
+    """`seq_bn_fwd`'s ``y`` with the running statistics in place of the batch's: mean =
+    ``running_mean``, rstd = 1 / sqrt(``running_var`` + eps).  One launch; writes no statistics."""
+    steps, batch, channels = _seq_bn_shape(
+        'seq_bn_infer', x, lengths, (('gamma', gamma), ('beta', beta),
+                                     ('running_mean', running_mean),
+                                     ('running_var', running_var)))
+    y = torch.empty_like(x)
+    _check(load().ctcasr_seq_bn_infer(
+        _dev(x, name='x'), _dev(lengths, torch.int32, 'lengths'), steps, batch, channels,
+        _dev(gamma, name='gamma'), _dev(beta, name='beta'),
+        _dev(running_mean, name='running_mean'), _dev(running_var, name='running_var'),
+        float(eps), _dev(y, name='y'), _stream()), 'seq_bn_infer')
+    return y
+
+
+@_on_tensor_device
+def seq_bn_bwd(dy, x, lengths, mean, rstd, gamma, dgamma, dbeta, workspace=None):
+    """Backward pass of `seq_bn_fwd`: returns ``dx`` (+0 on uncounted rows) and ADDS the
+    gradients of gamma and beta to ``dgamma`` / ``dbeta`` (float32 [C], in place).  ``x``,
+    ``lengths``: as given to the forward pass; ``mean``, ``rstd``: what it returned."""
+    steps, batch, channels = _seq_bn_shape(
+        'seq_bn_bwd', x, lengths, (('mean', mean), ('rstd', rstd), ('gamma', gamma),
+                                   ('dgamma', dgamma), ('dbeta', dbeta)))
+    if tuple(dy.shape) != tuple(x.shape):
+        raise CtcAsrError('seq_bn_bwd: dy has shape {}, x has {}.'
+                          .format(tuple(dy.shape), tuple(x.shape)))
+    workspace = _seq_bn_workspace('seq_bn_bwd', workspace, steps * batch, channels, x.device)
+    dx = torch.empty_like(x)
+    _check(load().ctcasr_seq_bn_bwd(
+        _dev(dy, name='dy'), _dev(x, name='x'), _dev(lengths, torch.int32, 'lengths'), steps,
+        batch, channels, _dev(mean, name='mean'), _dev(rstd, name='rstd'),
+        _dev(gamma, name='gamma'), _dev(dgamma, name='dgamma'), _dev(dbeta, name='dbeta'),
+        _dev(dx, name='dx'), _dev(workspace, torch.uint8, 'workspace'), workspace.numel(),
+        _stream()), 'seq_bn_bwd')
+    return dx
 
 
 def rnn_timeout_words(cell, workspace, num_steps, batch, hidden):

@@ -28,6 +28,7 @@ from ctc_asr_amd.params import ema_alpha_at
 CONV_KERNEL_SIZES = ((11, 41), (11, 21), (11, 21))   # (time, freq), asr/util/tf_contrib.py:66
 CONV_STRIDES = ((2, 2), (1, 2), (1, 2))              # asr/util/tf_contrib.py:67
 GATES = {'lstm': 4, 'gru': 3, 'rnn_relu': 1, 'rnn_tanh': 1}
+BN_EPS = 1e-5       # `ModelConfig.rnn_batch_norm`: the constant under the root
 
 
 class InfeasibleAlignmentError(ValueError):
@@ -41,7 +42,8 @@ class ModelConfig:
     def __init__(self, used_model='ds2', conv_filters=(32, 32, 96), num_units_dense=2048,
                  num_layers_rnn=4, num_units_rnn=2048, rnn_cell='rnn_relu', cudnn=True,
                  relu_cutoff=20.0, conv_dropout_rate=0.0, rnn_dropout_rate=0.0,
-                 dense_dropout_rate=0.1, num_classes_=None, num_features=80, beam_width=1024):
+                 dense_dropout_rate=0.1, num_classes_=None, num_features=80, beam_width=1024,
+                 rnn_batch_norm=False, rnn_bn_decay=0.99):
         if used_model not in ('ds1', 'ds2'):
             raise ValueError('Unsupported model "{}" in flags.'.format(used_model))
         if rnn_cell not in GATES:
@@ -64,6 +66,13 @@ class ModelConfig:
         self.num_classes = int(num_classes_ or num_classes())
         self.num_features = int(num_features)
         self.beam_width = int(beam_width)
+        # sequence-wise batch normalisation of the input of recurrent layers 2..L (no counterpart
+        # in the reference): off by default, and then nothing below differs from the reference's
+        self.rnn_batch_norm = bool(rnn_batch_norm)
+        self.rnn_bn_decay = float(rnn_bn_decay)
+        if self.rnn_batch_norm and not 0.0 < self.rnn_bn_decay < 1.0:
+            raise ValueError('rnn_bn_decay={}: a decay inside (0, 1) is needed.'
+                             .format(rnn_bn_decay))
 
     @classmethod
     def from_flags(cls, flags):
@@ -73,7 +82,9 @@ class ModelConfig:
                    relu_cutoff=flags.relu_cutoff, conv_dropout_rate=flags.conv_dropout_rate,
                    rnn_dropout_rate=flags.rnn_dropout_rate,
                    dense_dropout_rate=flags.dense_dropout_rate, num_classes_=flags.num_classes,
-                   beam_width=flags.beam_width)
+                   beam_width=flags.beam_width,
+                   rnn_batch_norm=getattr(flags, 'rnn_batch_norm', False),
+                   rnn_bn_decay=getattr(flags, 'rnn_bn_decay', 0.99))
 
     @property
     def cell(self):
@@ -123,6 +134,10 @@ def param_spec(cfg):
     gates, hidden = GATES[cfg.cell], cfg.num_units_rnn
     in_size = cfg.rnn_input_size()
     for i in range(cfg.num_layers_rnn):
+        if cfg.rnn_batch_norm and i > 0:
+            # (in front of the layer's weights: inside its slice of `ParamArena.layer_slices`)
+            spec.append(('rnn{}/bn_gamma'.format(i), (in_size,)))
+            spec.append(('rnn{}/bn_beta'.format(i), (in_size,)))
         spec.append(('rnn{}/w_ih'.format(i), (2, gates * hidden, in_size)))
         spec.append(('rnn{}/w_hh'.format(i), (2, gates * hidden, hidden)))
         spec.append(('rnn{}/b_ih'.format(i), (2, gates * hidden)))
@@ -155,6 +170,9 @@ def init_params(cfg, seed=0):
     for name, shape in param_spec(cfg):
         if name.endswith('bias') or name.endswith('b_ih') or name.endswith('b_hh'):
             params[name] = np.zeros(shape, dtype=np.float32)
+        elif name.endswith('bn_gamma') or name.endswith('bn_beta'):
+            params[name] = np.full(shape, 1.0 if name.endswith('bn_gamma') else 0.0,
+                                   dtype=np.float32)
         elif name.startswith('conv'):
             k_t, k_f, c_in, c_out = shape
             std = math.sqrt(2.0 / (k_t * k_f * c_in + k_t * k_f * c_out))
@@ -319,6 +337,8 @@ def predicted_input_bounds(cfg, training):
     rate = cfg.rnn_dropout_rate if training else 0.0
     bounds = []
     for i in range(cfg.num_layers_rnn):
+        if cfg.rnn_batch_norm and i > 0:
+            bound = None            # a normalised input has no bound
         if rate > 0.0 and (i > 0 or not cfg.cudnn) and bound is not None:
             bound = bound / (1.0 - rate)
         bounds.append(bound)
@@ -516,6 +536,15 @@ class CTCModel:
         self.gpu_metrics = os.environ.get('CTCASR_GPU_METRICS', '1') == '1'
         self._rnn_ws = {}               # (cell, B, H) -> (zero-initialised workspace, T')
         self.dropout_seed = int(seed) * 0x9E3779B1 + 1
+        # running statistics of the sequence-wise batch normalisation ([layer - 1][0] mean, [1]
+        # variance): no gradient, no Adam, no average - in no arena, and shared by the trained and
+        # the averaged weights (`ema_weights`); None without ``rnn_batch_norm``
+        self.bn_state = None
+        if cfg.rnn_batch_norm and cfg.num_layers_rnn > 1:
+            self.bn_state = torch.zeros((cfg.num_layers_rnn - 1, 2, 2 * cfg.num_units_rnn),
+                                        dtype=torch.float32, device=self.device)
+            self.bn_state[:, 1].fill_(1.0)
+        self._bn_ws = None              # workspace of the `hip.seq_bn_*` calls (main stream only)
         self._acts = None
         self._w_hh_t = [torch.empty((2, cfg.num_units_rnn, GATES[cfg.cell] * cfg.num_units_rnn),
                                     dtype=torch.float32, device=self.device)
@@ -656,6 +685,10 @@ class CTCModel:
                     # the transpose are needed - made on demand
                     above_f16 = f16_form(i + 1, 'rnn{}'.format(i + 1)) \
                         if i + 1 < cfg.num_layers_rnn else dense4_f16
+                    # (a normalisation above: the pieces of that layer's input are not pieces of
+                    # this layer's output - the gradient GEMMs take the bf16 form)
+                    bn_above = self.bn_state is not None and i + 1 < cfg.num_layers_rnn
+                    above_f16 = above_f16 and not bn_above
                     if training and self.bwd_f16 and above_f16 and own_dgrad:
                         pieces.dg16 = hip.dgrad16_pack_weights(
                             w_ih, hidden, split_gemm.W_SCALE,
@@ -666,6 +699,12 @@ class CTCModel:
                         pieces.make_tr16(
                             buf(name + '/t16', lambda: split_gemm.empty16(
                                 cols, gh2, split_gemm.H_B, self.device)),
+                            buf(name + '/t', lambda: torch.empty(
+                                (cols, gh2), dtype=torch.float32, device=self.device)))
+                    elif training and bn_above:
+                        pieces.make_tr(
+                            buf(name + '/tbf16', lambda: split_gemm.empty(
+                                cols, gh2, split_gemm.A_ORDER, self.device)),
                             buf(name + '/t', lambda: torch.empty(
                                 (cols, gh2), dtype=torch.float32, device=self.device)))
                 else:
@@ -875,11 +914,29 @@ class CTCModel:
         x = rnn_in.contiguous()
         workspace = self._rnn_workspace(cell, t_out, batch, hidden)
         rnn_rate = cfg.rnn_dropout_rate if training else 0.0
+        bn_on = self.bn_state is not None
+        bn_saved = []                   # per layer (un-normalised input, mean, rstd) or None
         for i in range(cfg.num_layers_rnn):
             # dropout placement: cuDNN drops the input of layers 2..L (asr/model.py:203); the
             # DropoutWrapper of the BasicRNNCell path drops every cell's input AND output
             # (asr/util/tf_contrib.py:190-194)
             seeds = [None, None]
+            # sequence-wise batch normalisation: the first thing a layer >= 1 does to its input
+            # (then the dropout).  The counted rows are the rows the recurrence runs over.
+            bn_saved.append(None)
+            if bn_on and i > 0:
+                bn_name = 'rnn{}/bn_'.format(i)
+                state = self.bn_state[i - 1]
+                if training:
+                    x_bn, bn_mean, bn_rstd = hip.seq_bn_fwd(
+                        x, rnn_len, p[bn_name + 'gamma'], p[bn_name + 'beta'], state[0],
+                        state[1], cfg.rnn_bn_decay, BN_EPS,
+                        workspace=self._bn_workspace(t_out * batch, 2 * hidden))
+                    bn_saved[i] = (x, bn_mean, bn_rstd)
+                else:
+                    x_bn = hip.seq_bn_infer(x, rnn_len, p[bn_name + 'gamma'],
+                                            p[bn_name + 'beta'], state[0], state[1], BN_EPS)
+                x, in_bound = x_bn, None
             if rnn_rate > 0.0 and (i > 0 or not cfg.cudnn):
                 seeds[0] = self._next_seed()
                 x = hip.dropout(x, rnn_rate, seeds[0])
@@ -932,11 +989,12 @@ class CTCModel:
                 # the fp16-pipe kernel can hand the fp16 pieces of its output to whoever multiplies
                 # them next (the next layer's projection / dense4; this layer's dW_hh): worth it
                 # when that consumer takes the fp16 form at the kernel's own scale (|h| <= 1, no
-                # dropout in between) and every row runs all steps
+                # dropout and no normalisation in between) and every row runs all steps
                 y16 = None
                 consumer = 'rnn{}'.format(i + 1) if i + 1 < cfg.num_layers_rnn else 'dense4'
                 if (f16_rec and self.rnn_fwd_pieces and rnn_len is None and
                         not (rnn_rate > 0.0 and (not cfg.cudnn or i + 1 < cfg.num_layers_rnn)) and
+                        not (bn_on and i + 1 < cfg.num_layers_rnn) and
                         hip.rnn_fwd_f16_supported(cell, t_out, batch, hidden, rnn_flags)):
                     pieces = self._weight_split(consumer)
                     if pieces is not None and pieces[2] is not None:
@@ -963,7 +1021,7 @@ class CTCModel:
         acts.update(layer_in=layer_in, layer_out=layer_out, reserves=reserves, rnn_ws=workspace,
                     rnn_len=rnn_len, t_out=t_out, drop_seeds=drop_seeds, rnn_rate=rnn_rate,
                     in_split=in_split, out_split=[None] * cfg.num_layers_rnn,
-                    in_split16=in_split16)
+                    in_split16=in_split16, bn_saved=bn_saved)
 
         rnn_flat = x.view(t_out * batch, 2 * hidden)
         flat_split, k4_pieces = None, self._weight_split('dense4')
@@ -1016,6 +1074,14 @@ class CTCModel:
         acts = self._acts or {}
         return dict(acts.get('arithmetic', {}))
 
+    def _bn_workspace(self, rows, channels):
+        """The workspace of the `hip.seq_bn_fwd` / `seq_bn_bwd` calls: one buffer, as every call
+        runs on the main stream and is done with it when the next one starts."""
+        need = hip.seq_bn_workspace_bytes(rows, channels)
+        if self._bn_ws is None or self._bn_ws.numel() < need:
+            self._bn_ws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.device)
+        return self._bn_ws
+
     def _rnn_workspace(self, cell, t_out, batch, hidden):
         """The recurrence workspace shared by every layer and pass of this model: zero-filled
         when created (the persistent kernels' time-out word is sticky - a launch never clears
@@ -1050,7 +1116,7 @@ class CTCModel:
         """Whether layer ``layer``'s forward recurrence runs on half of the chip in step ranges
         with the NEXT layer's input projection on the other half: pays when that projection is a
         big GEMM (another LSTM layer follows), the steps map to the same time index for every row
-        and nothing (dropout) sits between the layers."""
+        and nothing (dropout, batch normalisation) sits between the layers."""
         if self._weight_split('rnn{}'.format(layer + 1)) is not None:
             # the split projection of the next layer is a 1.1 ms GEMM at B = 16: not worth slowing
             # this layer's recurrence to half of the chip for (C2: 21.8 against 22.3 ms per step)
@@ -1058,7 +1124,8 @@ class CTCModel:
         return (self.fwd_chunks > 1 and cell == 'lstm' and hidden == 1024 and
                 batch <= self.fwd_pipeline_max_batch and
                 rnn_len is None and
-                rnn_rate == 0.0 and layer + 1 < self.cfg.num_layers_rnn and
+                rnn_rate == 0.0 and self.bn_state is None and
+                layer + 1 < self.cfg.num_layers_rnn and
                 t_out >= 8 * self.fwd_chunks and
                 hip.rnn_persistent_supported(cell, t_out, batch, hidden))
 
@@ -1222,6 +1289,9 @@ class CTCModel:
         cfg, p, g, acts = self.cfg, self.arena.p, self.arena.g, self._acts
         if acts is None or 'dlogits' not in acts:
             raise RuntimeError('backward() needs inference_fn() and loss_fn() first.')
+        if self.bn_state is not None and not acts['training']:
+            raise RuntimeError('backward() through rnn_batch_norm needs a training-mode forward '
+                               'pass: the batch statistics it normalised with.')
         slices = {name: (start, stop) for name, start, stop in self.arena.layer_slices}
 
         def done(layer):
@@ -1630,6 +1700,15 @@ class CTCModel:
                     dy_below = torch.mm(dxw2d, w_ih).view(t_out, batch, -1)
                 if seeds[0] is not None:
                     dy_below = hip.dropout(dy_below, rnn_rate, seeds[0])
+                if acts['bn_saved'][i] is not None:
+                    # back through the normalisation of this layer's input; the gradients of
+                    # gamma and beta are added to their slots of the arena (on this stream: the
+                    # layer's hook fires behind work that is enqueued after this point)
+                    bn_in, bn_mean, bn_rstd = acts['bn_saved'][i]
+                    dy_below = hip.seq_bn_bwd(
+                        dy_below.contiguous(), bn_in, acts['rnn_len'], bn_mean, bn_rstd,
+                        p[name + '/bn_gamma'], g[name + '/bn_gamma'], g[name + '/bn_beta'],
+                        workspace=self._bn_workspace(rows, 2 * hidden))
 
             def weight_grads(name=name, x=x, y=y, dxw=dxw, dxw2d=dxw2d, i=i, chunks=chunks,
                              last=bounds[-2], partial_weight_grads=partial_weight_grads,

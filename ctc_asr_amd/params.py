@@ -299,6 +299,20 @@ FLAGS.define('float', 'max_grad_norm', 0.0,
 FLAGS.define('bool', 'report_grad_norms', False,
              'Compute the global and per-layer gradient norms every step and log them.')
 
+
+def _bn_decay_check(value):
+    if not 0.0 < value < 1.0:           # (a NaN fails both comparisons)
+        raise ValueError('--rnn_bn_decay={} is outside 0 < d < 1.'.format(value))
+
+
+# Sequence-wise batch normalisation of the input of recurrent layers 2..L (no counterpart in the
+# reference; off: the parameters, the checkpoints and every launch of a step are what they were).
+FLAGS.define('bool', 'rnn_batch_norm', False,
+             'Normalise the input of recurrent layers 2..L per channel over all frames of the '
+             'batch; adds rnn{i}/bn_gamma and rnn{i}/bn_beta and running statistics.')
+FLAGS.define('float', 'rnn_bn_decay', 0.99,
+             'Decay of the running statistics of --rnn_batch_norm (0 < d < 1).', _bn_decay_check)
+
 # Augmentation of training batches on the device (no counterpart in the reference, which does not
 # augment; all off: a training batch launches what it always did).  Only the targets
 # 'train_bucket' and 'train_batch' augment; evaluate / predict / align never do.
@@ -589,6 +603,9 @@ def get_parameters():
         # reference's, line for line)
         rows.append('\tGradients (max_grad_norm={}, report_grad_norms={});'.format(
             FLAGS.max_grad_norm, FLAGS.report_grad_norms))
+    if FLAGS.rnn_batch_norm:
+        rows.append('\tBatchNorm (rnn_batch_norm={}, rnn_bn_decay={});'.format(
+            FLAGS.rnn_batch_norm, FLAGS.rnn_bn_decay))
     if FLAGS.spec_augment or FLAGS.speed_perturb:
         rows.append('\tAugmentation (spec_augment={}, freq_masks={} x {}, time_masks={} x {}, '
                     'time_permille={}, speed_perturb={});'.format(

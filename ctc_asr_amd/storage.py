@@ -48,6 +48,9 @@ def save_checkpoint(train_dir, model, epoch, extra=None):
              'shapes': arena.shapes, 'offsets': arena.offsets, 'extra': extra or {}}
     if getattr(arena, 'ema', None) is not None:
         state['ema'] = arena.ema.cpu()      # the averaged parameters (--ema_decay)
+    if getattr(model, 'bn_state', None) is not None:
+        # running statistics of --rnn_batch_norm (in a data-parallel run: the writing rank's)
+        state['bn_state'] = model.bn_state.cpu()
     path = os.path.join(train_dir, 'model-{}.pt'.format(model.step_count))
     tmp = path + '.tmp'
     torch.save(state, tmp)
@@ -77,9 +80,19 @@ def restore_checkpoint(path, model, weights='param'):
         arena.ema.copy_(state['ema'] if state.get('ema') is not None else arena.param)
     arena.m.copy_(state['m'])
     arena.v.copy_(state['v'])
+    if getattr(model, 'bn_state', None) is not None:
+        # (the comparison of `shapes` above has refused a file written without --rnn_batch_norm)
+        model.bn_state.copy_(state['bn_state'])
     model.step_count = int(state['step'])
     model.dropout_seed = int(state['dropout_seed'])
     return int(state['epoch'])
+
+
+def _refuse_batch_norm(cfg, what):
+    if getattr(cfg, 'rnn_batch_norm', False):
+        raise ValueError('{}: the reference has no variables for --rnn_batch_norm (gamma, beta, '
+                         'running statistics); TensorFlow checkpoints are served with the flag '
+                         'off only.'.format(what))
 
 
 def export_tf_checkpoint(train_dir, arena, cfg, global_step, weights='param'):
@@ -88,6 +101,7 @@ def export_tf_checkpoint(train_dir, arena, cfg, global_step, weights='param'):
     Optimizer slots are not written (the reference's cuDNN layers keep theirs as opaque
     blobs); returns the checkpoint prefix.  ``weights='ema'`` (--eval_ema) writes the averaged
     parameters under the same names."""
+    _refuse_batch_norm(cfg, 'export_tf_checkpoint')
     os.makedirs(train_dir, exist_ok=True)
     variables = tf_names.to_tf_variables(arena.export(weights), cfg)
     variables['global_step'] = np.array(int(global_step), dtype=np.int64)
@@ -102,6 +116,7 @@ def import_tf_checkpoint(path, arena, cfg):
     """Load the model variables of a TensorFlow checkpoint (a prefix, or a directory holding a
     ``checkpoint`` file) into ``arena``; Adam moments restart at zero.  Returns global_step.
     Optimizer slot variables (``.../Adam``, ``beta1_power`` ...) in the file are ignored."""
+    _refuse_batch_norm(cfg, 'import_tf_checkpoint')
     prefix = tf_bundle.latest_checkpoint(path) if os.path.isdir(path) else path
     if prefix is None or not os.path.isfile(prefix + '.index'):
         raise ValueError('No TensorFlow checkpoint at {}'.format(path))

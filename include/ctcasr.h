@@ -1138,6 +1138,63 @@ int ctcasr_resample(const void *in, int format, int channels, int64_t n, int rat
                     const float *table, int16_t *out, int64_t n_out, int32_t *status,
                     ctcasr_stream_t stream);
 
+/* ---- K20: sequence-wise batch normalisation between the recurrent layers ----------------------
+ * No counterpart in the reference (its stack has no normalisation).  The input of a recurrent
+ * layer is normalised per channel over every counted frame of the batch.  (Additions only, as for
+ * K19: CTCASR_ABI_VERSION stays.)
+ *   x        fp32 [T, B, C], time-major, contiguous, 16-byte aligned, C % 4 == 0.  Only read.
+ *   lengths  int32 [B] or NULL.  Row r = t * B + b is COUNTED when lengths is NULL or
+ *            t < clamp(lengths[b], 0, T); N = the number of counted rows.
+ *   gamma, beta, mean, rstd, running_mean, running_var, dgamma, dbeta: fp32 [C], 4-byte aligned.
+ *   y, dx    fp32 [T, B, C], 16-byte aligned, tensors of their own (x is the previous layer's
+ *            output, whose backward pass still reads it).
+ *   workspace  ctcasr_seq_bn_workspace_bytes(T * B, C) bytes, 8-byte aligned: the chunk sums and
+ *            two floats per channel.  Nothing is allocated behind the caller.
+ * ctcasr_seq_bn_fwd (training), three launches:
+ *   S1 = sum of x, S2 = sum of x^2 per channel over the counted rows, in fp64 ((double)x * (double)x
+ *   is exact).  Order (pinned): the rows are cut BY ROW NUMBER into chunks of CTCASR_SEQ_BN_ROWS
+ *   consecutive rows - the cut does not move with lengths; inside a chunk a channel's values are
+ *   added in ascending row order starting from +0 (S2 by one fp64 fma per value), uncounted rows
+ *   are left out; the chunk sums are added in ascending chunk order starting from +0.  No float
+ *   atomics, no cross-lane step: results are bit-reproducible and do not depend on the grid
+ *   (ctcasr_set_option("seq_bn_blocks", k), 0 <= k <= 65536, sets the workgroup count of the
+ *   streaming launches of all three entry points; 0: the default).
+ *   mean64 = S1 / N, var64 = S2 / N - mean64 * mean64 (two roundings: product, difference), a
+ *   negative var64 is 0 (a NaN stays), rstd64 = 1 / sqrt(var64 + eps).
+ *   mean = (float)mean64, rstd = (float)rstd64 are written for the backward pass.
+ *   Counted rows: y = fmaf(x - mean, a, beta), a = gamma * rstd (one fp32 product).  Uncounted
+ *   rows: y = +0.0 whatever x holds there (x is not read).
+ *   Running statistics: running = (float)(decay * (double)running + (1 - decay) * batch64) with
+ *   batch64 = mean64 / var64 (the population variance), written by the launch that finishes the
+ *   sums.  A channel whose mean64 or var64 is not finite leaves both of its running values alone.
+ *   N == 0: y is all zeros, mean = rstd = 0, the running values are untouched.
+ * ctcasr_seq_bn_infer, one launch: the same y with mean = running_mean and
+ *   rstd = (float)(1 / sqrt((double)running_var + eps)).  Writes no statistics, takes no workspace.
+ * ctcasr_seq_bn_bwd, three launches: xhat = (x - mean) * rstd in fp32 (two roundings);
+ *   s1 = sum of dy, s2 = sum of dy * xhat over the counted rows in fp64 in the order above (the
+ *   product of two fp32 values is exact in fp64; one fma per value).  dbeta[c] += (float)s1,
+ *   dgamma[c] += (float)s2: ADDED to what is there, one writer per channel.
+ *   m1 = (float)(s1 / N), m2 = (float)(s2 / N) (both 0 for N == 0).  Counted rows:
+ *   dx = a * ((dy - m1) - xhat * m2), every operation rounded on its own; uncounted rows: +0.0.
+ * Errors, before any launch: a null pointer (lengths excepted), T or B < 1, T * B > 2^31 - 1,
+ * C < 4 or C % 4 != 0, x / y / dy / dx not 16-byte aligned, decay outside [0, 1] or eps not a
+ * positive finite number: CTCASR_ERR_BAD_ARGUMENT; workspace null, short or not 8-byte aligned:
+ * CTCASR_ERR_WORKSPACE. */
+#define CTCASR_SEQ_BN_ROWS 64
+size_t ctcasr_seq_bn_workspace_bytes(int64_t rows, int C);
+int ctcasr_seq_bn_fwd(const float *x, const int32_t *lengths, int T, int B, int C,
+                      const float *gamma, const float *beta, float *running_mean,
+                      float *running_var, double decay, double eps, float *y, float *mean,
+                      float *rstd, void *workspace, size_t workspace_bytes,
+                      ctcasr_stream_t stream);
+int ctcasr_seq_bn_infer(const float *x, const int32_t *lengths, int T, int B, int C,
+                        const float *gamma, const float *beta, const float *running_mean,
+                        const float *running_var, double eps, float *y, ctcasr_stream_t stream);
+int ctcasr_seq_bn_bwd(const float *dy, const float *x, const int32_t *lengths, int T, int B, int C,
+                      const float *mean, const float *rstd, const float *gamma, float *dgamma,
+                      float *dbeta, float *dx, void *workspace, size_t workspace_bytes,
+                      ctcasr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

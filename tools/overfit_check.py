@@ -2,7 +2,7 @@
 """End-to-end learning check: the DS2 model (own convolutions, persistent BiLSTM-1024 kernels,
 CTC, Adam) memorises a small batch of noise "utterances" with random transcripts - the loss
 falls towards zero and the greedy / beam decodes become the transcripts.
-    python tools/overfit_check.py [steps batch seconds]"""
+    python tools/overfit_check.py [steps batch seconds] [--rnn_batch_norm]"""
 import os
 import sys
 import time
@@ -21,10 +21,10 @@ class Flags:
     learning_rate, adam_beta1, adam_beta2, adam_epsilon = 3e-4, 0.9, 0.999, 1e-8
 
 
-def run(steps=300, batch=8, seconds=2.0, verbose=True):
+def run(steps=300, batch=8, seconds=2.0, verbose=True, rnn_batch_norm=False):
     cfg = ModelConfig(used_model='ds2', conv_filters=(32, 32), num_units_dense=512,
                       num_layers_rnn=2, num_units_rnn=1024, rnn_cell='lstm', cudnn=True,
-                      dense_dropout_rate=0.0)
+                      dense_dropout_rate=0.0, rnn_batch_norm=rnn_batch_norm)
     trainer = Trainer(cfg, flags=Flags, device='cuda', seed=3)
     feats, lengths, labels, texts = synthetic_batch(batch, seconds, seed=5, chars_per_second=6.0)
     feats_d = torch.tensor(feats, device='cuda')
@@ -51,6 +51,7 @@ def run(steps=300, batch=8, seconds=2.0, verbose=True):
 
 
 if __name__ == '__main__':
-    args = [float(v) for v in sys.argv[1:4]]
+    batch_norm = '--rnn_batch_norm' in sys.argv[1:]
+    args = [float(v) for v in sys.argv[1:] if v != '--rnn_batch_norm'][:3]
     run(*(int(args[0]) if len(args) > 0 else 300, int(args[1]) if len(args) > 1 else 8,
-          args[2] if len(args) > 2 else 2.0))
+          args[2] if len(args) > 2 else 2.0), rnn_batch_norm=batch_norm)
