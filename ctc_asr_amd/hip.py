@@ -39,6 +39,9 @@ RESAMPLE_MAX_TABLE = 16640      # ctcasr_resample: the most weights (L * taps) o
 RESAMPLE_RATES = (4000, 192000)  # ... the rates it takes,
 RESAMPLE_MAX_CHANNELS = 8       # ... and the most channels it mixes down
 SEQ_BN_ROWS = 64                # ctcasr_seq_bn_*: consecutive rows per chunk of the pinned sums
+ALIGN_LONG_TILE_STATES = 1024   # ctcasr_ctc_align_long: lattice states per tile,
+ALIGN_LONG_TILE_FRAMES = 256    # ... frames per tile when the call passes 0,
+ALIGN_LONG_MAX = (1 << 22, 1 << 20, 64)   # ... and the most frames, labels and classes it serves
 CELL_IDS = {'rnn_relu': 0, 'rnn_tanh': 1, 'lstm': 2, 'gru': 3}
 CELL_GATES = {'rnn_relu': 1, 'rnn_tanh': 1, 'lstm': 4, 'gru': 3}
 
@@ -72,6 +75,9 @@ SIGNATURES = {
                          [_c_p] * 3 + [_c_sz, _c_p]),
     'ctcasr_ctc_align_workspace_bytes': (_c_sz, [_c_int] * 4),
     'ctcasr_ctc_align': (_c_int, [_c_p] * 4 + [_c_int] * 5 + [_c_p] * 5 + [_c_sz, _c_p]),
+    'ctcasr_ctc_align_long_workspace_bytes': (_c_sz, [_c_i64, _c_int, _c_i64, _c_int]),
+    'ctcasr_ctc_align_long': (_c_int, [_c_p, _c_p, _c_i64, _c_int, _c_int, _c_i64, _c_int] +
+                              [_c_p] * 6 + [_c_sz, _c_p]),
     'ctcasr_edit_distance_workspace_bytes': (_c_sz, [_c_int] * 3),
     'ctcasr_edit_distance': (_c_int, [_c_p] * 6 + [_c_int] * 3 + [_c_p] * 6 + [_c_sz, _c_p]),
     'ctcasr_rnn_reserve_bytes': (_c_sz, [_c_int] * 4),
@@ -579,6 +585,58 @@ def ctc_align(logits, labels, label_offsets, seq_len, max_label_len, blank=None,
         _dev(status, torch.int32, 'status'), _dev(workspace, torch.uint8, 'workspace'),
         workspace.numel(), _stream()), 'ctc_align')
     return path, score, frame_logp, status
+
+
+def ctc_align_long_workspace_bytes(num_steps, classes, num_labels, tile_frames=0):
+    """Bytes `ctc_align_long` needs; 0 for a shape it does not serve."""
+    return load().ctcasr_ctc_align_long_workspace_bytes(int(num_steps), int(classes),
+                                                        int(num_labels), int(tile_frames))
+
+
+@_on_tensor_device
+def ctc_align_long(logits, labels, blank=None, tile_frames=0, frame_logp=True, logp=False,
+                   workspace=None, max_workspace_bytes=64 << 30):
+    """CTC forced alignment (Viterbi) of ONE sequence of any length: the lattice is tiled in the
+    workspace (``ctcasr_ctc_align_long``), K11's arithmetic operation for operation.  logits
+    f32[T, C] or time-major f32[T, 1, C]; labels int32[L] on the device.  Returns (path i32[T],
+    score f64[1], frame_logp f32[T] or None, logp f32[T, C] or None, status i32[1]): ``logp`` is
+    the log-softmax table the lattice ran on.  A non-zero status is data, not an error.  The
+    workspace grows with T x L (2 bits per cell): a need above ``max_workspace_bytes`` raises
+    ValueError before anything is allocated."""
+    if logits.dim() == 3 and logits.shape[1] == 1:
+        logits = logits.reshape(logits.shape[0], logits.shape[2])
+    if logits.dim() != 2:
+        raise CtcAsrError('ctc_align_long: logits must be [T, C] or [T, 1, C] (got shape {}).'
+                          .format(tuple(logits.shape)))
+    num_steps, classes = logits.shape
+    num_labels = int(labels.numel())
+    blank = classes - 1 if blank is None else int(blank)
+    dev = logits.device
+    if num_steps > ALIGN_LONG_MAX[0] or num_labels > ALIGN_LONG_MAX[1] or \
+            classes > ALIGN_LONG_MAX[2]:
+        raise CtcAsrError('ctc_align_long: T = {}, L = {}, C = {} is outside what the kernel '
+                          'serves (T <= {}, L <= {}, C <= {}).'
+                          .format(num_steps, num_labels, classes, *ALIGN_LONG_MAX))
+    need = ctc_align_long_workspace_bytes(num_steps, classes, num_labels, tile_frames)
+    if need > int(max_workspace_bytes):
+        raise ValueError('ctc_align_long: T = {} frames x L = {} labels needs a workspace of {} '
+                         'bytes, above max_workspace_bytes = {}.'
+                         .format(num_steps, num_labels, need, int(max_workspace_bytes)))
+    if workspace is None:
+        workspace = _workspace(need, dev)
+    path = torch.empty(num_steps, dtype=torch.int32, device=dev)
+    score = torch.empty(1, dtype=torch.float64, device=dev)
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    frame_logp = torch.empty(num_steps, dtype=torch.float32, device=dev) if frame_logp else None
+    logp = torch.empty((num_steps, classes), dtype=torch.float32, device=dev) if logp else None
+    _check(load().ctcasr_ctc_align_long(
+        _dev(logits, name='logits'), _dev(labels, torch.int32, 'labels'), num_steps, classes,
+        blank, num_labels, int(tile_frames), _dev(path, torch.int32, 'path'),
+        _dev(score, torch.float64, 'score'), _dev(frame_logp, name='frame_logp'),
+        _dev(logp, name='logp'), _dev(status, torch.int32, 'status'),
+        _dev(workspace, torch.uint8, 'workspace'), workspace.numel(), _stream()),
+        'ctc_align_long')
+    return path, score, frame_logp, logp, status
 
 
 def edit_distance_workspace_bytes(batch, max_hyp_len, max_ref_len):

@@ -1266,6 +1266,15 @@ class CTCModel:
             flat, offsets, max_len, _ = self.pack_labels(labels, self.device)
         return hip.ctc_align(logits, flat, offsets, seq_len, max_len)
 
+    def align_long_fn(self, logits, labels):
+        """CTC forced alignment of ONE sequence of any length (``hip.ctc_align_long``): logits
+        [T, C] or [T, 1, C], ``labels`` a list of ids or an int32 device tensor.  Returns (path
+        i32[T], score f64[1], frame_logp f32[T], logp None, status i32[1])."""
+        if not torch.is_tensor(labels):
+            labels = torch.tensor([int(v) for v in labels], dtype=torch.int32,
+                                  device=self.device)
+        return hip.ctc_align_long(logits, labels)
+
     @staticmethod
     def check_status(status):
         bad = status.cpu().numpy()

@@ -7,6 +7,7 @@ The flag *names and defaults* are the drop-in knob API of the reference
 ``from asr.params import FLAGS`` keep working after changing the import.
 """
 
+import math
 import os
 import sys
 
@@ -562,6 +563,44 @@ FLAGS.define('int', 'max_segment_seconds', 15,
              _int_range('max_segment_seconds', 1, 30))
 FLAGS.define('string', 'transcribe_output', '',
              'transcribe.py: JSON-lines file, one line per piece; empty: print.')
+
+# A long recording WITH its text (no counterpart in the reference): `python -m
+# ctc_asr_amd.align_long` places --transcript on --input (one alignment over the whole recording,
+# `hip.ctc_align_long`), writes the word times to --align_output and, with --corpus_out_dir /
+# --corpus_out_csv, cuts the recording at the pauses between words into a training corpus.
+# Nothing else reads these flags.
+FLAGS.define('string', 'transcript', '', 'align_long.py: text file holding what --input says.')
+FLAGS.define('string', 'corpus_out_dir', '', 'align_long.py: directory the cut WAV files go to.')
+FLAGS.define('string', 'corpus_out_csv', '',
+             'align_long.py: manifest (path;label;length) of the cut corpus; a JSON-lines report '
+             'of every utterance is written next to it.')
+FLAGS.define('int', 'cut_max_seconds', 15, 'Longest utterance that is cut, in seconds (1..17).',
+             _int_range('cut_max_seconds', 1, 17))
+FLAGS.define('int', 'cut_min_gap_ms', 200,
+             'Shortest pause between two words at which a cut is made, in ms (0..5000).',
+             _int_range('cut_min_gap_ms', 0, 5000))
+FLAGS.define('int', 'cut_pad_ms', 100,
+             'Audio kept before the first and after the last word of an utterance, in ms '
+             '(0..1000).', _int_range('cut_pad_ms', 0, 1000))
+
+
+def parse_cut_min_confidence(text):
+    """--cut_min_confidence: '' (off) -> None, otherwise a finite float."""
+    if text == '':
+        return None
+    try:
+        value = float(text)
+    except ValueError:
+        value = float('nan')
+    if not math.isfinite(value):
+        raise ValueError('--cut_min_confidence={} is neither empty nor a finite number.'
+                         .format(text))
+    return value
+
+
+FLAGS.define('string', 'cut_min_confidence', '',
+             'Utterances whose mean log-probability over their label frames is below this are '
+             'reported as low_confidence and not written; empty: off.', parse_cut_min_confidence)
 
 # ####### Constants (asr/params.py:138-155). #########
 NP_FLOAT = np.float32

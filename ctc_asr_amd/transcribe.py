@@ -81,6 +81,44 @@ class _Clock:
         self.last = now
 
 
+def upload_recording(model, wav_path, timings=None):
+    """(int16 device tensor of the recording, the `_Clock` started after the file was read):
+    ``read_wav`` and one upload, or under ``--resample_input`` any WAV, uploaded in its own layout
+    and converted on the device ('upload' holds both)."""
+    if FLAGS.resample_input:
+        rate, audio = load_audio(wav_path)
+        clock = _Clock(timings)
+        pcm = upload_audio(rate, audio, model.device, wav_path)
+    else:
+        audio = read_wav(wav_path)
+        clock = _Clock(timings)
+        pcm = torch.from_numpy(np.ascontiguousarray(audio)).to(model.device)
+    clock.lap('upload')
+    return pcm, clock
+
+
+def forward_pieces(model, pcm, start, length, batch_size, feature_type, normalization):
+    """The pieces ``(start, length)`` of `vad.segment` through the model, a batch at a time in
+    `batch_order`: yields ``(rows, logits [T, B, C], seq_len)`` per batch, ``rows`` the indices
+    of the batch's pieces.  Per batch one `hip.gather_segments`, `hip.features` with the flags'
+    feature settings and ``inference_fn(training=False)``: `transcribe` and
+    `align_long.align_recording` launch the same work in the same order."""
+    if not len(start):
+        return
+    seg_start = torch.from_numpy(start).to(model.device)
+    seg_len = torch.from_numpy(length).to(model.device)
+    for rows in batch_order(length, batch_size):
+        index = torch.tensor(rows, dtype=torch.int64, device=model.device)
+        batch, num = hip.gather_segments(pcm, seg_start[index], seg_len[index],
+                                         max_samples=int(length[rows[0]]))
+        feats, lengths = hip.features(batch, num, feature_type, normalization,
+                                      FLAGS.features_drop_every_second_frame,
+                                      FLAGS.sampling_rate)
+        logits, seq_len = model.inference_fn(feats, lengths, training=False)
+        model.check_rnn_error()
+        yield rows, logits, seq_len
+
+
 def transcribe(model, wav_path, timestamps=False, scorer=None, nbest=0, settings=None,
                batch_size=None, timings=None, report=None):
     """{'plaintext', 'segments', 'audio_seconds', 'speech_seconds'} of one recording.
@@ -97,23 +135,11 @@ def transcribe(model, wav_path, timestamps=False, scorer=None, nbest=0, settings
     settings = vad.VadSettings.from_flags(FLAGS) if settings is None else settings
     batch_size = FLAGS.batch_size if batch_size is None else int(batch_size)
     feature_type, normalization = _check_feature_args(None, None)
-    if FLAGS.resample_input:
-        # the file's own layout goes up once and is converted there ('upload' holds both)
-        rate, audio = load_audio(wav_path)
-        clock = _Clock(timings)
-        pcm = upload_audio(rate, audio, model.device, wav_path)
-    else:
-        audio = read_wav(wav_path)
-        clock = _Clock(timings)
-        pcm = torch.from_numpy(np.ascontiguousarray(audio)).to(model.device)
-    clock.lap('upload')
+    pcm, clock = upload_recording(model, wav_path, timings)
     start, length, threshold = vad.segment(pcm, settings)
     clock.lap('segmentation')
     count = len(start)
     texts, words, labels = [''] * count, [[] for _ in range(count)], [[] for _ in range(count)]
-    if count:
-        seg_start = torch.from_numpy(start).to(model.device)
-        seg_len = torch.from_numpy(length).to(model.device)
     hop = alignment.frame_seconds(model.cfg, FLAGS.features_drop_every_second_frame)
     pending = []
 
@@ -134,15 +160,8 @@ def transcribe(model, wav_path, timestamps=False, scorer=None, nbest=0, settings
         clock.lap('alignment')
         del pending[:]
 
-    for rows in batch_order(length, batch_size):
-        index = torch.tensor(rows, dtype=torch.int64, device=model.device)
-        batch, num = hip.gather_segments(pcm, seg_start[index], seg_len[index],
-                                         max_samples=int(length[rows[0]]))
-        feats, lengths = hip.features(batch, num, feature_type, normalization,
-                                      FLAGS.features_drop_every_second_frame,
-                                      FLAGS.sampling_rate)
-        logits, seq_len = model.inference_fn(feats, lengths, training=False)
-        model.check_rnn_error()
+    for rows, logits, seq_len in forward_pieces(model, pcm, start, length, batch_size,
+                                                feature_type, normalization):
         pending.append((rows, logits, seq_len))
         clock.lap('forward')
         # (the longest pieces bound the prefix-tree pool: size the group on them)

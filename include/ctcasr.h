@@ -224,6 +224,50 @@ int ctcasr_ctc_align(const float *logits, const int32_t *labels, const int32_t *
                      int32_t *path, float *score, float *frame_logp, int32_t *status,
                      void *workspace, size_t workspace_bytes, ctcasr_stream_t stream);
 
+/* ---- K21: CTC forced alignment of one long sequence -------------------------------------------
+ * K11's alignment without K11's ceiling (2L + 1 <= 1152): one sequence of T frames against L
+ * labels, the lattice tiled in the workspace - CTCASR_ALIGN_LONG_TILE_STATES states by
+ * tile_frames frames (0: CTCASR_ALIGN_LONG_TILE_FRAMES; a value above T counts as T) per
+ * workgroup, one launch per anti-diagonal of tiles, rows + cols - 1 of them, between a launch
+ * that builds the table and one that walks the path back.  No workgroup waits for another: a tile
+ * reads only what earlier launches wrote, and the host never synchronises.  logits [T, C] (a
+ * time-major [T, 1, C] tensor is the same memory), labels int32 [L].
+ *
+ * PINNED: the arithmetic is K11's, operation for operation.
+ *   - the fp32 log-softmax table per frame: mx = the sequential fmaxf over the row, sum = the
+ *     sequential sum of expf(row[c] - mx), lz = mx + logf(sum), table[c] = row[c] - lz;
+ *   - the lattice in fp64: delta_0(0) = table_0[blank], delta_0(1) = table_0[l_1], delta_t(s) =
+ *     max(...) + (double)table_t[ext[s]]; predecessors compared with strict > in the order s,
+ *     s - 1, s - 2, the skip s - 2 taken only into a non-blank state with ext[s] != ext[s - 2];
+ *   - at the end S - 1 wins over S - 2 unless S - 2 is strictly better.
+ * Max and add do not depend on how the lattice is tiled: path, score and frame_logp are a pure
+ * function of the table, bit for bit, for every tile_frames, and equal K11's where K11 serves
+ * (its float score is this one rounded).  Tiles through which no path from the start to the end
+ * can pass are skipped; that changes no output.
+ *   path       int32 [T]: the state of the best path at frame t (as K11)
+ *   score      double [1]: the fp64 lattice value of the best path, unrounded (0 for T = 0, L = 0)
+ *   frame_logp [T] table value of the class the path emits at frame t; may be NULL
+ *   logp       [T, C] receives the table the lattice ran on (written whatever the status); may
+ *              be NULL
+ *   status     int32 [1]: 0 ok; 1 T < L + adjacent repeats; 2 a label id out of range or the
+ *              blank; 3 a non-finite logit.  Non-zero: score -inf (NaN for 3), path -1 and
+ *              frame_logp 0 throughout.  Every output is fully written.
+ * Limits: C <= 64, T <= 2^22, L <= 2^20, at most 65536 tile rows (else CTCASR_ERR_UNSUPPORTED).
+ * T = 0 is served (status 0 for L = 0, else 1) and needs no logits and no path; L = 0 needs no
+ * labels.  Any other null pointer, a negative size or tile_frames, C < 2 or a blank outside
+ * [0, C): CTCASR_ERR_BAD_ARGUMENT, before the device is touched.  Workspace:
+ * ctcasr_ctc_align_long_workspace_bytes(T, C, L, tile_frames) bytes (0 for arguments the call
+ * would refuse), 8-byte aligned; its contents on entry do not matter.  It holds the table, 2
+ * bits of back-pointer per cell, one fp64 per state and tile row, one fp64 per frame and tile
+ * column. */
+#define CTCASR_ALIGN_LONG_TILE_STATES 1024
+#define CTCASR_ALIGN_LONG_TILE_FRAMES 256
+size_t ctcasr_ctc_align_long_workspace_bytes(int64_t T, int C, int64_t L, int tile_frames);
+int ctcasr_ctc_align_long(const float *logits, const int32_t *labels, int64_t T, int C, int blank,
+                          int64_t L, int tile_frames, int32_t *path, double *score,
+                          float *frame_logp, float *logp, int32_t *status, void *workspace,
+                          size_t workspace_bytes, ctcasr_stream_t stream);
+
 /* ---- K13: edit distance ------------------------------------------------------------------------
  * Replaces tf.edit_distance(decoded, labels) (asr/model.py:338) and the Levenshtein distance of
  * asr/util/metrics.py:110-141, for a whole batch in one launch, and adds the error breakdown.
