@@ -42,6 +42,9 @@ SEQ_BN_ROWS = 64                # ctcasr_seq_bn_*: consecutive rows per chunk of
 ALIGN_LONG_TILE_STATES = 1024   # ctcasr_ctc_align_long: lattice states per tile,
 ALIGN_LONG_TILE_FRAMES = 256    # ... frames per tile when the call passes 0,
 ALIGN_LONG_MAX = (1 << 22, 1 << 20, 64)   # ... and the most frames, labels and classes it serves
+SEARCH_MAX_LABEL_LEN = 576      # ctcasr_ctc_search: the longest phrase (2L - 1 <= 1151 states),
+SEARCH_MAX_HITS = 1024          # ... the most hits it stores per pair,
+SEARCH_WAVES = 4                # ... and the pairs one workgroup takes
 CELL_IDS = {'rnn_relu': 0, 'rnn_tanh': 1, 'lstm': 2, 'gru': 3}
 CELL_GATES = {'rnn_relu': 1, 'rnn_tanh': 1, 'lstm': 4, 'gru': 3}
 
@@ -78,6 +81,9 @@ SIGNATURES = {
     'ctcasr_ctc_align_long_workspace_bytes': (_c_sz, [_c_i64, _c_int, _c_i64, _c_int]),
     'ctcasr_ctc_align_long': (_c_int, [_c_p, _c_p, _c_i64, _c_int, _c_int, _c_i64, _c_int] +
                               [_c_p] * 6 + [_c_sz, _c_p]),
+    'ctcasr_ctc_search_workspace_bytes': (_c_sz, [_c_int] * 3),
+    'ctcasr_ctc_search': (_c_int, [_c_p, _c_p] + [_c_int] * 4 + [_c_p, _c_p, _c_int, _c_int] +
+                          [_c_p] * 3 + [_c_int, _c_int] + [_c_p] * 9 + [_c_sz, _c_p]),
     'ctcasr_edit_distance_workspace_bytes': (_c_sz, [_c_int] * 3),
     'ctcasr_edit_distance': (_c_int, [_c_p] * 6 + [_c_int] * 3 + [_c_p] * 6 + [_c_sz, _c_p]),
     'ctcasr_rnn_reserve_bytes': (_c_sz, [_c_int] * 4),
@@ -637,6 +643,78 @@ def ctc_align_long(logits, labels, blank=None, tile_frames=0, frame_logp=True, l
         _dev(workspace, torch.uint8, 'workspace'), workspace.numel(), _stream()),
         'ctc_align_long')
     return path, score, frame_logp, logp, status
+
+
+def ctc_search_workspace_bytes(num_steps, batch, classes):
+    return load().ctcasr_ctc_search_workspace_bytes(int(num_steps), int(batch), int(classes))
+
+
+@_on_tensor_device
+def ctc_search(logits, seq_len, labels, label_offsets, pair_utt, pair_phrase, min_score,
+               max_hits=16, max_label_len=None, blank=None, per_frame=False, workspace=None):
+    """CTC phrase spotting (``ctcasr_ctc_search``): pair h scores phrase pair_phrase[h] against
+    utterance pair_utt[h] on a Viterbi lattice with a free start and a free end.  logits
+    f32[T, B, C]; seq_len i32[B]; labels / label_offsets (i32[P + 1]) hold the P phrases, each
+    once; min_score f64[P]; pair_utt / pair_phrase i32[H].  Returns (hits i32[H, max_hits, 2],
+    hit_score f64[H, max_hits], n_hits i32[H], best_score f64[H], best_span i32[H, 2], end_score
+    f64[H, T] or None, end_start i32[H, T] or None, status i32[H]); the per-frame outputs only
+    with ``per_frame``.  ``max_label_len`` defaults to the longest phrase.  A non-zero status is
+    data, not an error: the caller reads it."""
+    num_steps, batch, classes = _decode_shape('ctc_search', logits, seq_len)
+    pairs = pair_utt.numel()
+    phrases = label_offsets.numel() - 1
+    if phrases < 0:
+        raise CtcAsrError('ctc_search: label_offsets holds no entry (P + 1 expected).')
+    _expect_numel('ctc_search', 'pair_phrase', pair_phrase, pairs)
+    _expect_numel('ctc_search', 'min_score', min_score, phrases)
+    _dev(label_offsets, torch.int32, 'label_offsets')
+    # the ABI takes bare pointers: keep every row the kernel may read inside `labels`
+    off64 = label_offsets.long()
+    low, high, longest = torch.stack([off64.min(), off64.max(),
+                                      (off64[1:] - off64[:-1]).max() if phrases else
+                                      off64.new_zeros(())]).tolist()
+    if low < 0 or high > labels.numel():
+        raise CtcAsrError('ctc_search: a row lies outside `labels`.')
+    max_label_len = max(longest, 0) if max_label_len is None else int(max_label_len)
+    max_hits = int(max_hits)
+    blank = classes - 1 if blank is None else int(blank)
+    dev = logits.device
+    hits = torch.empty((pairs, max(max_hits, 0), 2), dtype=torch.int32, device=dev)
+    hit_score = torch.empty((pairs, max(max_hits, 0)), dtype=torch.float64, device=dev)
+    n_hits = torch.empty(pairs, dtype=torch.int32, device=dev)
+    best_score = torch.empty(pairs, dtype=torch.float64, device=dev)
+    best_span = torch.empty((pairs, 2), dtype=torch.int32, device=dev)
+    status = torch.empty(pairs, dtype=torch.int32, device=dev)
+    end_score = end_start = None
+    if per_frame:
+        end_score = torch.empty((pairs, num_steps), dtype=torch.float64, device=dev)
+        end_start = torch.empty((pairs, num_steps), dtype=torch.int32, device=dev)
+    if workspace is None:
+        workspace = _workspace(ctc_search_workspace_bytes(num_steps, batch, classes), dev)
+
+    def ptr(tensor, dtype, name):
+        # an empty tensor has no address to give: the kernel reads none of it then
+        return _dev(tensor, dtype, name) if tensor.numel() else None
+
+    # (an empty `labels`, and `min_score` without a phrase, still need an address: every phrase
+    # is empty or out of range then, and neither is read)
+    labels_ptr = _dev(labels, torch.int32, 'labels') if labels.numel() else \
+        _dev(label_offsets, torch.int32, 'label_offsets')
+    _check(load().ctcasr_ctc_search(
+        ptr(logits, torch.float32, 'logits'), _dev(seq_len, torch.int32, 'seq_len'), num_steps,
+        batch, classes, blank, labels_ptr, _dev(label_offsets, torch.int32, 'label_offsets'),
+        phrases, max_label_len,
+        _dev(min_score, torch.float64, 'min_score') if phrases else
+        _dev(label_offsets, torch.int32, 'label_offsets'),
+        _dev(pair_utt, torch.int32, 'pair_utt'), _dev(pair_phrase, torch.int32, 'pair_phrase'),
+        pairs, max_hits, ptr(hits, torch.int32, 'hits'),
+        ptr(hit_score, torch.float64, 'hit_score'), _dev(n_hits, torch.int32, 'n_hits'),
+        _dev(best_score, torch.float64, 'best_score'), _dev(best_span, torch.int32, 'best_span'),
+        None if end_score is None else ptr(end_score, torch.float64, 'end_score'),
+        None if end_start is None else ptr(end_start, torch.int32, 'end_start'),
+        _dev(status, torch.int32, 'status'), _dev(workspace, torch.uint8, 'workspace'),
+        workspace.numel(), _stream()), 'ctc_search')
+    return hits, hit_score, n_hits, best_score, best_span, end_score, end_start, status
 
 
 def edit_distance_workspace_bytes(batch, max_hyp_len, max_ref_len):

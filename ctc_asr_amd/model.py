@@ -1275,6 +1275,55 @@ class CTCModel:
                                   device=self.device)
         return hip.ctc_align_long(logits, labels)
 
+    def search_fn(self, logits, seq_len, phrases, min_score_per_label, max_hits=16, pairs=None):
+        """CTC phrase spotting (``hip.ctc_search``): where in the utterances of ``logits``
+        [T, B, C] are the ``phrases`` (a list of id lists) said?  ``pairs`` is a list of (utt,
+        phrase) index pairs; the default is all P x B of them, grouped by utterance.  The
+        threshold of phrase p is ``min_score_per_label * len(phrase_p)`` in float64.  One launch,
+        one read-back.  Returns ``(hits, per_pair)``: ``hits`` is one list of ``{'phrase', 'utt',
+        'start', 'end', 'score', 'score_per_label'}`` (frames, both inclusive; pairs in the
+        order given, a pair's hits in time order), ``per_pair`` a dict of numpy arrays ``utt``,
+        ``phrase``, ``n_hits``, ``best_score``, ``best_span`` [H, 2] and ``status`` (0 ok, 1 the
+        utterance is too short for the phrase, 2 a bad phrase or pair, 3 a non-finite logit)."""
+        rows = [[int(v) for v in phrase] for phrase in phrases]
+        batch = int(logits.shape[1])
+        if pairs is None:
+            pairs = [(b, p) for b in range(batch) for p in range(len(rows))]
+        pairs = [(int(b), int(p)) for b, p in pairs]
+        count, max_hits = len(pairs), int(max_hits)
+        offsets = np.zeros(len(rows) + 1, dtype=np.int32)
+        offsets[1:] = np.cumsum([len(r) for r in rows])
+        flat = np.array([v for r in rows for v in r] or [0], dtype=np.int32)
+        lengths = np.array([len(r) for r in rows], dtype=np.float64)
+        min_score = np.float64(min_score_per_label) * lengths
+        dev = logits.device
+        host = [torch.as_tensor(flat), torch.as_tensor(offsets), torch.as_tensor(min_score),
+                torch.tensor([b for b, _ in pairs], dtype=torch.int32),
+                torch.tensor([p for _, p in pairs], dtype=torch.int32)]
+        flat_d, offsets_d, min_score_d, utt_d, phrase_d = (t.to(dev) for t in host)
+        hits, hit_score, n_hits, best_score, best_span, _, _, status = hip.ctc_search(
+            logits, seq_len, flat_d, offsets_d, utt_d, phrase_d, min_score_d, max_hits=max_hits)
+        # one read-back: an int32 is exact in a double
+        packed = torch.cat([hits.reshape(count, 2 * max_hits).double(), hit_score,
+                            n_hits[:, None].double(), best_score[:, None], best_span.double(),
+                            status[:, None].double()], dim=1).cpu().numpy()
+        spans = packed[:, :2 * max_hits].astype(np.int32).reshape(count, max_hits, 2)
+        scores = packed[:, 2 * max_hits:3 * max_hits]
+        tail = packed[:, 3 * max_hits:]
+        per_pair = {'utt': np.array([b for b, _ in pairs], dtype=np.int32),
+                    'phrase': np.array([p for _, p in pairs], dtype=np.int32),
+                    'n_hits': tail[:, 0].astype(np.int32), 'best_score': tail[:, 1].copy(),
+                    'best_span': tail[:, 2:4].astype(np.int32),
+                    'status': tail[:, 4].astype(np.int32)}
+        found = []
+        for h, (b, p) in enumerate(pairs):
+            for k in range(min(int(per_pair['n_hits'][h]), max_hits)):
+                score = float(scores[h, k])
+                found.append({'phrase': p, 'utt': b, 'start': int(spans[h, k, 0]),
+                              'end': int(spans[h, k, 1]), 'score': score,
+                              'score_per_label': score / len(rows[p])})
+        return found, per_pair
+
     @staticmethod
     def check_status(status):
         bad = status.cpu().numpy()

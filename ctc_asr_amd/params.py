@@ -602,6 +602,30 @@ FLAGS.define('string', 'cut_min_confidence', '',
              'Utterances whose mean log-probability over their label frames is below this are '
              'reported as low_confidence and not written; empty: off.', parse_cut_min_confidence)
 
+# Phrase spotting (no counterpart in the reference): `python -m ctc_asr_amd.search` looks for the
+# phrases of --phrases in --input, scoring them against the logits (`hip.ctc_search`), not against
+# the decoded text.  Nothing else reads these flags.
+SEARCH_MAX_HITS = 1024     # hip.SEARCH_MAX_HITS: the most hits the kernel stores per pair
+
+
+def _check_search_min_score(value):
+    if not (math.isfinite(value) and value <= 0):
+        raise ValueError('--search_min_score={} is not a finite number <= 0.'.format(value))
+
+
+FLAGS.define('string', 'phrases', '',
+             'search.py: text file, one phrase a line; blank lines are skipped.')
+FLAGS.define('float', 'search_min_score', -1.0,
+             'Lowest score PER LABEL of a hit: the log of (best path through the phrase) over '
+             '(the greedy path on the same frames), divided by the number of labels; a finite '
+             'float <= 0.  The default is a choice, not a measured value: calibrate it on the '
+             'summary lines search.py prints for every phrase.', _check_search_min_score)
+FLAGS.define('int', 'search_max_hits', 16,
+             'Most hits kept per phrase and piece (1..{}).'.format(SEARCH_MAX_HITS),
+             _int_range('search_max_hits', 1, SEARCH_MAX_HITS))
+FLAGS.define('string', 'search_output', '',
+             'search.py: JSON-lines file, one line per hit, then one per phrase; empty: print.')
+
 # ####### Constants (asr/params.py:138-155). #########
 NP_FLOAT = np.float32
 

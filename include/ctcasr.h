@@ -268,6 +268,80 @@ int ctcasr_ctc_align_long(const float *logits, const int32_t *labels, int64_t T,
                           float *frame_logp, float *logp, int32_t *status, void *workspace,
                           size_t workspace_bytes, ctcasr_stream_t stream);
 
+/* ---- K22: CTC phrase spotting -------------------------------------------------------------------
+ * Is this phrase said in here, and where?  (No counterpart in the reference.)  P phrases, each
+ * stored once, scored against the logits directly: pair h runs phrase pair_phrase[h] over
+ * utterance pair_utt[h] on a Viterbi lattice with a free start and a free end, and the hits -
+ * non-overlapping spans whose score reaches the phrase's threshold - are picked on the device.
+ * One wavefront per pair, the lattice in registers (K14's shape).  (An added entry point, as
+ * K19 - K21: CTCASR_ABI_VERSION stays.)
+ *   logits, seq_len  as ctcasr_ctc_score takes them; blank is any id in [0, C)
+ *   labels         int32, the concatenated label ids of the P phrases
+ *   label_offsets  int32 [P + 1]
+ *   min_score      double [P]: the threshold of phrase p (<= 0 to be of use; NaN: no hit ever)
+ *   pair_utt, pair_phrase  int32 [H]: any order, any subset, any repetition
+ *
+ * PINNED: the arithmetic (tests/search_reference.py restates it).
+ *   - table = the output of ctcasr_log_softmax_fwd on the logits, bit for bit.
+ *   - fill[t, b] = the fmaxf over table[t, b, 0 .. C-1], fp32: what the greedy path emits.  A row
+ *     of the table that is NaN (a NaN or +inf logit, or a row of -inf, makes one) has fill NaN.
+ *   - a phrase of L >= 1 labels has S = 2L - 1 states, no blank in front and none behind: even
+ *     u is label lab[u / 2], odd u is the blank.
+ *   - cost_t(u) = (double)table[t, b, ext(u)] - (double)fill[t, b], never positive.
+ *   - the lattice: fp64, max-sum, over frames 0 <= t < seq_len[b]; state u carries a value
+ *     d_t(u) and the frame s_t(u) at which its path entered state 0.  Candidates in this order,
+ *     a later one replacing the best so far only when strictly greater, starting from -inf:
+ *       1. stay   d_{t-1}(u);
+ *       2. step   d_{t-1}(u - 1), u >= 1;
+ *       3. skip   d_{t-1}(u - 2), even u >= 2 with lab[u/2] != lab[u/2 - 1];
+ *       4. entry  u == 0 only: the value 0.0 with start t.
+ *     The first three do not exist at t = 0.  d_t(u) = best + cost_t(u); whenever that is -inf
+ *     the start is -1.
+ *   - end_score[h, t] = d_t(S - 1), end_start[h, t] = s_t(S - 1); -inf and -1 for t >= seq_len.
+ *     end_score[t] is the log of (best path through the phrase that ends at t) over (the greedy
+ *     path on the same frames): 0 exactly when the two coincide.
+ *   - best_score / best_span = the first t, by strict >, that reaches the largest end_score,
+ *     with its start: (start, t).  -inf and (-1, -1) when nothing is finite.
+ *   - hits: one pass in ascending t with pending = none, flushed_end = -1.  Frame t is a
+ *     candidate (score, start, t) when end_score[t] > -inf and end_score[t] >= min_score[phrase].
+ *     The first rule that applies handles it:
+ *       1. start <= flushed_end: dropped;
+ *       2. no pending: it becomes pending;
+ *       3. start <= pending.end: it replaces pending when score > pending.score, or when score
+ *          == pending.score and start == pending.start (the same occurrence, its last label held
+ *          longer); otherwise it is dropped;
+ *       4. otherwise pending is flushed - appended, flushed_end = pending.end - and the
+ *          candidate becomes pending.
+ *     After the last frame pending is flushed.
+ *   hits       int32 [H, max_hits, 2]: (start, end) frames, both inclusive, of the first max_hits
+ *              flushed hits; pairwise disjoint, ascending.  NULL iff max_hits == 0
+ *   hit_score  double [H, max_hits].  NULL iff max_hits == 0
+ *   n_hits     int32 [H]: every flushed hit counts, stored or not.  Rows of hits / hit_score at
+ *              or beyond min(n_hits, max_hits) hold (-1, -1) and -inf
+ *   best_score double [H], best_span int32 [H, 2]
+ *   end_score  double [H, T], end_start int32 [H, T]: each may be NULL
+ *   status     int32 [H]: 0 ok; 1 seq_len < L + adjacent repeats (no span exists: the outputs
+ *              hold the no-hit values above); 2 a label id out of range or the blank, L == 0,
+ *              L > max_label_len or a negative row, pair_utt or pair_phrase out of range,
+ *              seq_len > T or < 0; 3 fill is NaN in some frame t < seq_len of the utterance.
+ *              2 and 3: n_hits 0, span (-1, -1), hit rows empty, best_score and end_score[0 .. T)
+ *              -inf for 2 and NaN for 3, end_start -1.
+ * Frames at or beyond seq_len are never read by a pair.  A pair's outputs do not depend on the
+ * other pairs of the call or on their order, bit for bit.  Every output element is written.
+ * C <= 64, 2 * max_label_len - 1 <= 1151, max_hits <= 1024 (else CTCASR_ERR_UNSUPPORTED).  A
+ * negative size, C < 2, a blank outside [0, C), a null required pointer, hits / hit_score null
+ * while max_hits > 0: CTCASR_ERR_BAD_ARGUMENT, before the device is touched.  H == 0 returns
+ * CTCASR_OK and launches nothing.  Workspace: ctcasr_ctc_search_workspace_bytes(T, B, C) (the
+ * table and fill); a short one gives CTCASR_ERR_WORKSPACE; its contents on entry do not matter. */
+size_t ctcasr_ctc_search_workspace_bytes(int T, int B, int C);
+int ctcasr_ctc_search(const float *logits, const int32_t *seq_len, int T, int B, int C, int blank,
+                      const int32_t *labels, const int32_t *label_offsets, int P, int max_label_len,
+                      const double *min_score, const int32_t *pair_utt, const int32_t *pair_phrase,
+                      int H, int max_hits, int32_t *hits, double *hit_score, int32_t *n_hits,
+                      double *best_score, int32_t *best_span, double *end_score,
+                      int32_t *end_start, int32_t *status, void *workspace, size_t workspace_bytes,
+                      ctcasr_stream_t stream);
+
 /* ---- K13: edit distance ------------------------------------------------------------------------
  * Replaces tf.edit_distance(decoded, labels) (asr/model.py:338) and the Levenshtein distance of
  * asr/util/metrics.py:110-141, for a whole batch in one launch, and adds the error breakdown.
