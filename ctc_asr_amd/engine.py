@@ -200,11 +200,27 @@ class Trainer:
     def __init__(self, cfg, flags=None, device=None, seed=0, params=None, world_size=1, rank=0,
                  bucket_bytes=64 << 20, conv_autotune=None, allreduce_early=None,
                  force_reducer=False, reduce=True, collective_stand_in=None, max_grad_norm=None,
-                 report_grad_norms=None, grad_accum_steps=None, ema_decay=None, lr_schedule=None):
+                 report_grad_norms=None, grad_accum_steps=None, ema_decay=None, lr_schedule=None,
+                 mwer_nbest=None, mwer_beam_width=None, mwer_ctc_weight=None, mwer_risk=None):
         self.world, self.rank = world_size, rank
 
         def flag(name, default):
             return getattr(flags, name, default) if flags is not None else default
+
+        # Minimum word error rate training (keyword arguments, else the flags of the same names,
+        # else off): with ``mwer_nbest`` >= 2 a step's loss is the expected error count over the
+        # n-best list of its own logits plus ``mwer_ctc_weight`` times the CTC loss
+        # (`CTCModel.mwer_loss_fn`); each rank decodes its own shard.  With 0 `train_step`
+        # launches exactly what it launches without it.
+        mwer = {'nbest': int(flag('mwer_nbest', 0) if mwer_nbest is None else mwer_nbest)}
+        for name, given in (('beam_width', mwer_beam_width), ('ctc_weight', mwer_ctc_weight),
+                            ('risk', mwer_risk)):
+            default = _params.MWER_DEFAULTS['mwer_' + name]
+            mwer[name] = flag('mwer_' + name, default) if given is None else given
+        _params.check_mwer_settings(**mwer)
+        self.mwer = mwer if mwer['nbest'] else None
+        self.last_expected_risk = None  # device float32[B]: R_b of the last (micro-)step
+        self.last_mwer_paths = None     # device int32[B]: the sizes of its lists
 
         # The schedule of a run (keyword arguments, else the flags of the same names, else off):
         # ``grad_accum_steps`` micro-batches are summed into one update, ``ema_decay`` > 0 keeps
@@ -393,11 +409,15 @@ class Trainer:
         self._refuse_open_update('save_checkpoint')
         return storage.save_checkpoint(train_dir, self.model, epoch, extra)
 
-    def train_step(self, features, feature_len, labels, check=True):
+    def train_step(self, features, feature_len, labels, check=True, originals=None):
         """forward + CTC + backward (+ all-reduce) + Adam on this rank's shard of the global
         batch; returns the local mean loss (device scalar).  The global loss is the mean over
         ranks of the local means (equal shard sizes), so gradients are summed and scaled by
         1 / world_size inside the Adam kernel.
+
+        ``originals``: the transcripts of the batch, read only by MWER training with the word
+        risk (``mwer_nbest`` >= 2; default: the labels decoded).  The loss is then the expected
+        error count plus the weighted CTC loss, and `last_expected_risk` holds the former.
 
         ``check=True``: errors are raised without stalling the host - an infeasible alignment
         (where ``tf.nn.ctc_loss`` raises), a non-finite loss or a timed-out persistent kernel
@@ -429,14 +449,19 @@ class Trainer:
         accum = self.grad_accum_steps
         last = self._micro == accum - 1
         label = self.model.step_count + 1
+        # (off: the calls below are the calls of a trainer that knows nothing of MWER)
+        extra = {'mwer': self.mwer, 'originals': originals} if self.mwer else {}
         if accum > 1:
             label = '{} (micro-step {} of {})'.format(label, self._micro + 1, accum)
             loss = self.model.forward_backward(features, feature_len, labels,
                                                reduce_hook=self.reducer if last else None,
-                                               check=False, accumulate=self._micro > 0)
+                                               check=False, accumulate=self._micro > 0, **extra)
         else:
             loss = self.model.forward_backward(features, feature_len, labels,
-                                               reduce_hook=self.reducer, check=False)
+                                               reduce_hook=self.reducer, check=False, **extra)
+        if self.mwer:
+            self.last_expected_risk = self.model.last_mwer['expected_risk']
+            self.last_mwer_paths = self.model.last_mwer['n_hyps']
         # Invalid gradients never reach the parameters: the guard word is computed on the device
         # from this step's CTC status, its loss and the recurrence time-out words, and the Adam
         # kernel drops the update when it is set - whenever the host gets to look.

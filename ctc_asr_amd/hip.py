@@ -76,6 +76,10 @@ SIGNATURES = {
     'ctcasr_ctc_score_workspace_bytes': (_c_sz, [_c_int] * 5),
     'ctcasr_ctc_score': (_c_int, [_c_p, _c_p] + [_c_int] * 4 + [_c_p] * 3 + [_c_int] * 2 +
                          [_c_p] * 3 + [_c_sz, _c_p]),
+    'ctcasr_ctc_mwer_workspace_bytes': (_c_sz, [_c_int] * 5),
+    'ctcasr_ctc_mwer': (_c_int, [_c_p, _c_p] + [_c_int] * 4 + [_c_p] * 4 + [_c_int, _c_int, _c_f,
+                                                                              _c_int] +
+                        [_c_p] * 6 + [_c_sz, _c_p]),
     'ctcasr_ctc_align_workspace_bytes': (_c_sz, [_c_int] * 4),
     'ctcasr_ctc_align': (_c_int, [_c_p] * 4 + [_c_int] * 5 + [_c_p] * 5 + [_c_sz, _c_p]),
     'ctcasr_ctc_align_long_workspace_bytes': (_c_sz, [_c_i64, _c_int, _c_i64, _c_int]),
@@ -556,6 +560,70 @@ def ctc_score(logits, seq_len, labels, label_offsets, utt, max_label_len=None, b
         _dev(status, torch.int32, 'status'), _dev(workspace, torch.uint8, 'workspace'),
         workspace.numel(), _stream()), 'ctc_score')
     return score, status
+
+
+def ctc_mwer_workspace_bytes(num_steps, batch, classes, nbest, max_label_len):
+    return load().ctcasr_ctc_mwer_workspace_bytes(num_steps, batch, classes, int(nbest),
+                                                  int(max_label_len))
+
+
+@_on_tensor_device
+def ctc_mwer(logits, seq_len, labels, label_offsets, n_hyps, risk, max_label_len=None, blank=None,
+             scale=1.0, accumulate=False, grad=None, workspace=None):
+    """Gradient of the expected risk over n-best lists (``ctcasr_ctc_mwer``).  logits f32[T, B, C];
+    seq_len i32[B]; labels / label_offsets (i32[B * N + 1]) in `ctc_score`'s packed form, row
+    ``b * N + i`` being hypothesis i of utterance b; n_hyps i32[B]; risk f32[B * N] (N is read off
+    it).  ``accumulate``: the gradient is added to what ``grad`` holds.  Returns (grad f32[T, B,
+    C], expected_risk f32[B], score f32[B * N], posterior f32[B * N], status i32[B * N]).
+    ``max_label_len`` defaults to the longest row.  A non-zero status is data, not an error."""
+    num_steps, batch, classes = _decode_shape('ctc_mwer', logits, seq_len)
+    if n_hyps.numel() != batch:
+        raise CtcAsrError('ctc_mwer: n_hyps holds {} entries for a batch of {}.'
+                          .format(n_hyps.numel(), batch))
+    rows = risk.numel()
+    if batch < 1 or rows < batch or rows % batch:
+        raise CtcAsrError('ctc_mwer: risk holds {} entries for a batch of {}.'
+                          .format(rows, batch))
+    nbest = rows // batch
+    if label_offsets.numel() != rows + 1:
+        raise CtcAsrError('ctc_mwer: label_offsets holds {} entries for {} hypotheses.'
+                          .format(label_offsets.numel(), rows))
+    _dev(label_offsets, torch.int32, 'label_offsets')
+    # the ABI takes bare pointers: keep every row the kernel may read inside `labels`
+    off64 = label_offsets.long()
+    low, high, longest = torch.stack([off64.min(), off64.max(),
+                                      (off64[1:] - off64[:-1]).max()]).tolist()
+    if low < 0 or high > labels.numel():
+        raise CtcAsrError('ctc_mwer: a row lies outside `labels`.')
+    max_label_len = max(longest, 0) if max_label_len is None else int(max_label_len)
+    blank = classes - 1 if blank is None else blank
+    dev = logits.device
+    if accumulate and grad is None:
+        raise CtcAsrError('ctc_mwer: accumulate needs the gradient to add to.')
+    grad = torch.empty_like(logits) if grad is None else grad
+    _expect_numel('ctc_mwer', 'grad', grad, logits.numel())
+    need = ctc_mwer_workspace_bytes(num_steps, batch, classes, nbest, max_label_len)
+    if workspace is None:
+        workspace = _workspace(need, dev)
+    elif workspace.numel() < need:
+        raise CtcAsrError('ctc_mwer: the workspace holds {} bytes, {} needed.'
+                          .format(workspace.numel(), need))
+    expected_risk = torch.empty(batch, dtype=torch.float32, device=dev)
+    score = torch.empty(rows, dtype=torch.float32, device=dev)
+    posterior = torch.empty(rows, dtype=torch.float32, device=dev)
+    status = torch.empty(rows, dtype=torch.int32, device=dev)
+    # an empty `labels` has no address to give: the kernel reads none of it then
+    labels_ptr = _dev(labels, torch.int32, 'labels') if labels.numel() else \
+        _dev(label_offsets, torch.int32, 'label_offsets')
+    _check(load().ctcasr_ctc_mwer(
+        _dev(logits, name='logits'), _dev(seq_len, torch.int32, 'seq_len'), num_steps, batch,
+        classes, blank, labels_ptr, _dev(label_offsets, torch.int32, 'label_offsets'),
+        _dev(n_hyps, torch.int32, 'n_hyps'), _dev(risk, name='risk'), nbest, max_label_len,
+        float(scale), int(bool(accumulate)), _dev(grad, name='grad'),
+        _dev(expected_risk, name='expected_risk'), _dev(score, name='score'),
+        _dev(posterior, name='posterior'), _dev(status, torch.int32, 'status'),
+        _dev(workspace, torch.uint8, 'workspace'), workspace.numel(), _stream()), 'ctc_mwer')
+    return grad, expected_risk, score, posterior, status
 
 
 def ctc_align_workspace_bytes(num_steps, batch, classes, max_label_len):

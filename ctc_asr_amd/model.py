@@ -23,7 +23,7 @@ import torch
 
 from ctc_asr_amd import hip, metrics, split_gemm
 from ctc_asr_amd.labels import num_classes
-from ctc_asr_amd.params import ema_alpha_at
+from ctc_asr_amd.params import check_mwer_settings, ema_alpha_at
 
 CONV_KERNEL_SIZES = ((11, 41), (11, 21), (11, 21))   # (time, freq), asr/util/tf_contrib.py:66
 CONV_STRIDES = ((2, 2), (1, 2), (1, 2))              # asr/util/tf_contrib.py:67
@@ -1256,6 +1256,82 @@ class CTCModel:
             self.check_status(status)
         return per_utt.mean()
 
+    def mwer_loss_fn(self, logits, seq_length, labels, originals=None, nbest=4, beam_width=64,
+                     ctc_weight=0.01, risk='word', check=True):
+        """Expected error count over the n-best list plus ``ctc_weight`` times the CTC loss
+        (minimum word error rate training), mean over the batch.  In this order: `loss_fn`'s CTC
+        launch with ``grad_scale = ctc_weight / B``; the plain n-best search (no language model)
+        of the SAME logits at ``beam_width``; the risk of every hypothesis - ``'label'``: the
+        edit distance of the decoder's dense output against the packed references, on the device
+        (`hip.edit_distance`); ``'word'``: the word edit distance against ``originals`` (the
+        transcripts; default: the references decoded) through `metrics.word_ids` /
+        `metrics.error_counts`, after one read-back of the list -; `hip.ctc_mwer` with ``scale =
+        1 / B``, accumulating into the CTC gradient.  The sum stays in ``self._acts['dlogits']``
+        for `backward`.  ``last_per_utterance_loss`` is ``expected_risk + ctc_weight * ctc_loss``
+        (what `step_guard` looks at), ``last_status`` the CTC status of the references, and
+        ``last_mwer`` holds the list as the kernel took it and what it returned, on the device."""
+        from ctc_asr_amd.labels import decode
+        check_mwer_settings(nbest, beam_width, ctc_weight, risk)
+        nbest = int(nbest)
+        if nbest < 2:
+            raise ValueError('mwer_loss_fn(): nbest={} is not in 2..64.'.format(nbest))
+        if isinstance(labels, tuple) and len(labels) == 4 and torch.is_tensor(labels[0]):
+            flat, offsets, max_len, rows = labels       # already packed by `pack_labels`
+        else:
+            flat, offsets, max_len, rows = self.pack_labels(labels, self.device)
+        num_steps, batch = int(logits.shape[0]), int(logits.shape[1])
+        per_utt, grad, status = hip.ctc_loss_fwd_bwd(logits, flat, offsets, seq_length, max_len,
+                                                     grad_scale=float(ctc_weight) / batch)
+        out, out_len, _, n_paths = hip.ctc_beam_decode_nbest(logits, seq_length, beam_width,
+                                                            nbest)
+        dev = out.device
+        # (a row of non-finite logits has no defined answer: keep what it claims inside the row)
+        lengths = out_len.reshape(-1).clamp(0, num_steps)
+        hyp_flat, hyp_offsets = self._pack_rows(out, lengths)
+        if risk == 'label':
+            ref_len = (offsets[1:] - offsets[:-1]).repeat_interleave(nbest).contiguous()
+            distance = hip.edit_distance(
+                out, torch.arange(batch * nbest, device=dev, dtype=torch.int32) * num_steps,
+                lengths, flat, offsets[:-1].repeat_interleave(nbest).contiguous(), ref_len)[0]
+            risks = distance.to(torch.float32)
+            longest = int(lengths.max())
+        else:
+            # the one read-back of the list that the word risk costs
+            host = torch.cat([out.reshape(-1), lengths, n_paths]).cpu().numpy()
+            host_out = host[:batch * nbest * num_steps].reshape(batch, nbest, num_steps)
+            host_len = host[batch * nbest * num_steps:-batch].reshape(batch, nbest)
+            if originals is None or len(originals) == 0:
+                originals = [decode(row) for row in rows]
+            if len(originals) != batch:
+                raise ValueError('mwer_loss_fn(): {} transcripts for a batch of {}.'.format(
+                    len(originals), batch))
+            used = [(b, k) for b in range(batch) for k in range(int(host[-batch + b]))]
+            texts = [decode(host_out[b, k, :host_len[b, k]].tolist()) for b, k in used]
+            ref_words, hyp_words = metrics.word_ids([originals[b] for b, _ in used], texts)
+            counts = metrics.error_counts(hyp_words, ref_words, self.device)
+            host_risk = np.zeros((batch, nbest), dtype=np.float32)
+            for (b, k), count in zip(used, counts[:, 0]):
+                host_risk[b, k] = count
+            risks = torch.from_numpy(host_risk.reshape(-1)).to(dev)
+            longest = int(host_len.max())
+        grad, expected, score, posterior, hyp_status = hip.ctc_mwer(
+            logits, seq_length, hyp_flat, hyp_offsets, n_paths, risks,
+            max_label_len=max(longest, 0), scale=1.0 / batch, accumulate=True, grad=grad)
+        total = expected + float(ctc_weight) * per_utt
+        if self._acts is not None:
+            self._acts['dlogits'] = grad
+            if self._acts.get('input_poison') is not None and \
+                    self._acts['input_poison'].shape == total.shape:
+                total = total + self._acts['input_poison']
+        self.last_status, self.last_per_utterance_loss = status, total
+        self.last_mwer = {'labels': hyp_flat, 'label_offsets': hyp_offsets, 'n_hyps': n_paths,
+                          'risk': risks, 'expected_risk': expected, 'score': score,
+                          'posterior': posterior, 'status': hyp_status, 'out': out,
+                          'out_len': out_len, 'ctc_loss': per_utt}
+        if check:
+            self.check_status(status)
+        return total.mean()
+
     def align_fn(self, logits, seq_len, labels):
         """CTC forced alignment of ``labels`` (the forms `loss_fn` takes) to ``logits``: returns
         (path i32[B, T], score f32[B], frame_logp f32[B, T], status i32[B]) as device tensors
@@ -1911,11 +1987,17 @@ class CTCModel:
             main.wait_stream(side)
 
     def forward_backward(self, features, feature_len, labels, reduce_hook=None, check=True,
-                         accumulate=False):
-        """One training forward + backward; returns the mean CTC loss (device scalar).
+                         accumulate=False, mwer=None, originals=None):
+        """One training forward + backward; returns the mean loss (device scalar): the CTC loss,
+        or with ``mwer`` (the keyword arguments of `mwer_loss_fn`: nbest, beam_width, ctc_weight,
+        risk) the expected risk plus the weighted CTC loss, against ``originals``.
         ``accumulate``: see `backward`."""
         logits, seq_length = self.inference_fn(features, feature_len, training=True)
-        loss = self.loss_fn(logits, seq_length, labels, check=check)
+        if mwer:
+            loss = self.mwer_loss_fn(logits, seq_length, labels, originals=originals,
+                                     check=check, **mwer)
+        else:
+            loss = self.loss_fn(logits, seq_length, labels, check=check)
         if accumulate:
             self.backward(reduce_hook, accumulate=True)
         else:
@@ -2136,6 +2218,17 @@ class CTCModel:
         weights = np.exp(masked - peak)
         return weights / weights.sum(), selected
 
+    @staticmethod
+    def _pack_rows(out, lengths):
+        """(labels, label_offsets) in `hip.ctc_score`'s packed form of the rows of a decoder's
+        dense, zero-padded ``out`` [..., T]; ``lengths`` int32, one per row, on the device."""
+        num_steps = out.shape[-1]
+        offsets = torch.zeros(lengths.numel() + 1, dtype=torch.int32, device=out.device)
+        offsets[1:] = torch.cumsum(lengths, 0)
+        frames = torch.arange(num_steps, device=out.device, dtype=torch.int32)
+        return out.reshape(-1, num_steps)[frames[None, :] < lengths[:, None]].contiguous(), \
+            offsets
+
     def _nbest_launch(self, logits, seq_len, top_paths, beam_width, scorer, rescorer):
         """One n-best launch, one `hip.ctc_score` launch over all B * N hypotheses, one
         read-back; returns one dict per utterance (see `nbest_fn`)."""
@@ -2151,11 +2244,7 @@ class CTCModel:
         rows = torch.arange(batch, device=out.device, dtype=torch.int32)
         utt = torch.where(ranks[None, :] < n_paths[:, None], rows[:, None].expand(-1, top_paths),
                           torch.full_like(out_len, -1)).reshape(-1).contiguous()
-        lengths = out_len.reshape(-1)
-        offsets = torch.zeros(batch * top_paths + 1, dtype=torch.int32, device=out.device)
-        offsets[1:] = torch.cumsum(lengths, 0)
-        frames = torch.arange(num_steps, device=out.device, dtype=torch.int32)
-        flat = out.reshape(-1, num_steps)[frames[None, :] < lengths[:, None]].contiguous()
+        flat, offsets = self._pack_rows(out, out_len.reshape(-1))
         ctc, status = hip.ctc_score(logits, seq_len, flat, offsets, utt,
                                     max_label_len=max(int(out_len.max()), 0))
         out, out_len, logp, n_paths, ctc, status = (

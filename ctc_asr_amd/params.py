@@ -537,6 +537,69 @@ def _validate_nbest(flags):
 
 FLAGS.define_validator(_validate_nbest)
 
+# Minimum word error rate training (no counterpart in the reference; off while --mwer_nbest is 0:
+# a step then launches what it always did).  A training step decodes the n-best list of its own
+# logits, scores every hypothesis against the transcript and adds the gradient of the expected
+# error count (hip.ctc_mwer) to --mwer_ctc_weight times the CTC gradient.  The usual last stage
+# after CTC training; the search is the plain one (no language model) at its own, narrow width.
+MWER_NBEST_RANGE = (2, 64)
+MWER_BEAM_RANGE = (2, 1024)
+MWER_RISKS = ('word', 'label')
+MWER_DEFAULTS = {'mwer_beam_width': 64, 'mwer_ctc_weight': 0.01, 'mwer_risk': 'word'}
+
+
+def _mwer_nbest_check(value):
+    if value != 0 and not MWER_NBEST_RANGE[0] <= value <= MWER_NBEST_RANGE[1]:
+        raise ValueError('--mwer_nbest={} is neither 0 (off) nor in {}..{}.'.format(
+            value, *MWER_NBEST_RANGE))
+
+
+def _mwer_ctc_weight_check(value):
+    if not (np.isfinite(value) and value >= 0.0):
+        raise ValueError('--mwer_ctc_weight={} is not a finite value >= 0.'.format(value))
+
+
+def check_mwer_settings(nbest, beam_width, ctc_weight, risk):
+    """ValueError for a value or combination that MWER training refuses (``nbest`` 0: off, and
+    then nothing else is looked at); what the flags and `engine.Trainer` both go by."""
+    nbest = int(nbest)
+    if nbest == 0:
+        return
+    _mwer_nbest_check(nbest)
+    if not nbest <= int(beam_width) <= MWER_BEAM_RANGE[1]:
+        raise ValueError('--mwer_beam_width={} is outside --mwer_nbest ({})..{}.'.format(
+            beam_width, nbest, MWER_BEAM_RANGE[1]))
+    _mwer_ctc_weight_check(ctc_weight)
+    _one_of('mwer_risk', MWER_RISKS)(risk)
+
+
+FLAGS.define('int', 'mwer_nbest', 0,
+             'Hypotheses per utterance of the expected-risk term of a training step (0: off; '
+             '2..64).', _mwer_nbest_check)
+FLAGS.define('int', 'mwer_beam_width', MWER_DEFAULTS['mwer_beam_width'],
+             'Leaves kept by the beam search of a training step (--mwer_nbest..1024); '
+             '--beam_width is not used there.', _int_range('mwer_beam_width', *MWER_BEAM_RANGE))
+FLAGS.define('float', 'mwer_ctc_weight', MWER_DEFAULTS['mwer_ctc_weight'],
+             'Weight of the CTC loss beside the expected risk (finite, >= 0; a choice, not a '
+             'measured optimum).', _mwer_ctc_weight_check)
+FLAGS.define('string', 'mwer_risk', MWER_DEFAULTS['mwer_risk'],
+             "The error count whose expectation is minimised: 'word' or 'label'.",
+             _one_of('mwer_risk', MWER_RISKS))
+
+
+def _validate_mwer(flags):
+    if flags.mwer_nbest == 0:
+        changed = [name for name, default in MWER_DEFAULTS.items()
+                   if getattr(flags, name) != default]
+        if changed:
+            raise ValueError('--{} needs --mwer_nbest >= 2.'.format(changed[0]))
+        return
+    check_mwer_settings(flags.mwer_nbest, flags.mwer_beam_width, flags.mwer_ctc_weight,
+                        flags.mwer_risk)
+
+
+FLAGS.define_validator(_validate_mwer)
+
 # Long recordings (no counterpart in the reference): `python -m ctc_asr_amd.transcribe` cuts
 # --input at its pauses (ctc_asr_amd/vad.py), batches the pieces and puts their texts back on one
 # time axis.  Nothing else reads these flags.
@@ -690,4 +753,8 @@ def get_parameters():
                     .format(FLAGS.lr_schedule, FLAGS.minimum_lr, FLAGS.lr_warmup_steps,
                             FLAGS.lr_total_steps, FLAGS.grad_accum_steps, FLAGS.ema_decay,
                             FLAGS.eval_ema))
+    if FLAGS.mwer_nbest:
+        rows.append('\tMWER (mwer_nbest={:,d}, mwer_beam_width={:,d}, mwer_ctc_weight={}, '
+                    'mwer_risk={});'.format(FLAGS.mwer_nbest, FLAGS.mwer_beam_width,
+                                            FLAGS.mwer_ctc_weight, FLAGS.mwer_risk))
     return '\n'.join(rows)

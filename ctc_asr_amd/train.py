@@ -44,8 +44,12 @@ def train_epoch(trainer, target, epoch, rank, world, writer=None, seed=None):
     for batch in input_fn():
         features, labels = batch
         # (the labels as the reader thread has uploaded them: no host-to-device copy here)
-        loss = trainer.train_step(features['spectrogram'], features['spectrogram_length'],
-                                  batch.packed_labels)
+        if trainer.mwer:                # (the word risk scores against the transcripts)
+            loss = trainer.train_step(features['spectrogram'], features['spectrogram_length'],
+                                      batch.packed_labels, originals=features['label_plaintext'])
+        else:
+            loss = trainer.train_step(features['spectrogram'], features['spectrogram_length'],
+                                      batch.packed_labels)
         steps += 1
         logger.add_audio(batch.audio_seconds * world)
         if trainer.accumulating:        # (an open update: nothing to log or check yet)
@@ -60,10 +64,18 @@ def train_epoch(trainer, target, epoch, rank, world, writer=None, seed=None):
             # on every rank; the host is synchronised here anyway)
             grad_norms = None if trainer.last_grad_norms is None \
                 else trainer.last_grad_norms.tolist()
+            # (--mwer_nbest: the expected error count per utterance and the mean size of the lists
+            # of the step just read, averaged over ranks - every rank takes part)
+            mwer_risk = mwer_paths = None
+            if trainer.mwer:
+                mwer_risk = float(trainer.global_mean(trainer.last_expected_risk.mean()))
+                mwer_paths = float(trainer.global_mean(trainer.last_mwer_paths.float().mean()))
             if rank == 0:
                 line, examples_per_sec, audio_per_sec = logger.line(model.step_count, value)
                 if grad_norms is not None:
                     line += '; grad_norm={:.4g}'.format(grad_norms[-1])
+                if mwer_risk is not None:
+                    line += '; risk={:.4g}'.format(mwer_risk)
                 ema_decay_t = None
                 if trainer.lr_scheduled:
                     line += '; learning_rate={:.4g}'.format(trainer.lr)
@@ -89,6 +101,9 @@ def train_epoch(trainer, target, epoch, rank, world, writer=None, seed=None):
                     writer.scalar('Metrics/word_error_rate', wer, step)
                     writer.scalar('examples_per_sec', examples_per_sec, step)
                     writer.scalar('audio_seconds_per_sec', audio_per_sec, step)
+                    if mwer_risk is not None:
+                        writer.scalar('mwer_expected_risk', mwer_risk, step)
+                        writer.scalar('mwer_mean_paths', mwer_paths, step)
                     if grad_norms is not None:
                         writer.scalar('grad_norm', grad_norms[-1], step)
                         for name, norm in zip(model.grad_norm_names, grad_norms):

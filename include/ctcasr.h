@@ -199,6 +199,71 @@ int ctcasr_ctc_score(const float *logits, const int32_t *seq_len, int T, int B, 
                      int H, int max_label_len, float *score, int32_t *status, void *workspace,
                      size_t workspace_bytes, ctcasr_stream_t stream);
 
+/* ---- K23: expected-risk gradient over n-best lists (MWER training) ------------------------------
+ * The gradient, with respect to the logits, of the expected error count over an n-best list (no
+ * counterpart in the reference): the training signal that ctcasr_ctc_beam_decode_nbest, K14 and
+ * K13 lack between them.  CTC forward AND backward lattices of B * N hypotheses, folded into one
+ * gradient with per-hypothesis weights computed on the device.  (An added entry point, as K19 -
+ * K22: CTCASR_ABI_VERSION stays.)
+ *   logits, seq_len  as ctcasr_ctc_score takes them; blank is any id in [0, C)
+ *   labels         int32, the concatenated label ids of all B * N rows
+ *   label_offsets  int32 [B * N + 1]; row b * N + i is hypothesis i (rank i) of utterance b
+ *   n_hyps         int32 [B]: rows i >= n_hyps[b] of utterance b are unused - nothing of them is
+ *                  read, neither their offsets' labels nor their risk.  A negative value counts as
+ *                  0 (the n-best search's n_paths = -1), one above N as N.
+ *   risk           float [B * N]: W_i, an error count (any finite value)
+ *   scale, accumulate  see grad
+ *
+ * PINNED: the arithmetic (tests/mwer_reference.py restates it).  Per utterance b the VALID
+ * hypotheses are its used rows of status 0, in rank order, with s_i = score and W_i = risk:
+ *   - score[h] is bit for bit what ctcasr_ctc_score returns for the same row: the table of
+ *     ctcasr_log_softmax_fwd, lse3's operand order, fp64 state, fp32 exp / log of the
+ *     differences, for every states-per-lane count;
+ *   - in fp64, from the fp32 scores widened to double: P_i = exp(s_i - max s) / sum_j exp(s_j -
+ *     max s) (sums in ascending rank; if every valid score is -inf they share the mass equally),
+ *     R_b = sum_i P_i W_i, c_i = P_i (W_i - R_b), so sum_i c_i = 0;
+ *   - occ_i[t, k] = the sum over the extended states u of y_i with l'[u] = k of exp(alpha_i(t, u) +
+ *     beta_i(t, u) - s_i) (K9's occupancy; 0 throughout when s_i = -inf).  As d s_i / d logit[t, k]
+ *     = occ_i[t, k] - softmax[t, k] and the c_i sum to zero, the softmax terms cancel:
+ *         grad[t, b, k] = scale * sum_i c_i occ_i[t, k]       for t < seq_len[b],
+ *     the sum over i in ascending rank in fp64, times (double)scale, rounded to fp32 once;
+ *     every such row sums to zero over k up to rounding;
+ *   - accumulate != 0: grad[t, b, k] = (float)((double)grad_in[t, b, k] + that fp64 value);
+ *   - rows t >= seq_len[b] (a seq_len outside [0, T]: every row) are +0.0, or with accumulate
+ *     keep grad_in bit for bit;
+ *   - an utterance with fewer than two valid hypotheses has the fp64 value +0.0 in every row
+ *     below seq_len; R_b is then the one valid risk, or 0 with none.
+ * No float atomics: an utterance's outputs do not depend on the other utterances of the call, and
+ * two runs give equal bits.
+ *   grad           [T, B, C], see above
+ *   expected_risk  float [B]: R_b
+ *   score          float [B * N]; -inf for a non-zero status other than 3
+ *   posterior      float [B * N]: P_i; 0 for a row that is not valid
+ *   status         int32 [B * N]: K14's codes - 0 ok; 1 seq_len < L + adjacent repeats; 2 a label
+ *                  id out of range or the blank, seq_len > T or < 0, a row longer than
+ *                  max_label_len or of negative length - and, where K14 returns status 0 with a
+ *                  NaN score, K11's 3: a non-finite logit in the first seq_len frames.  score (the
+ *                  same NaN bits as K14's) and posterior of such a row, expected_risk of its
+ *                  utterance and every gradient element of the utterance with t < seq_len are then
+ *                  NaN.  An unused row has status -1, score -inf, posterior 0.
+ * Every output element is written (grad with accumulate: as pinned above).  Frames at or beyond
+ * seq_len are never read.  C <= 64, 2 * max_label_len + 1 <= 1152, B <= 65535 (else
+ * CTCASR_ERR_UNSUPPORTED); N < 1, C < 2, a blank outside [0, C), a negative size or a null pointer:
+ * CTCASR_ERR_BAD_ARGUMENT, before the device is touched.  Workspace:
+ * ctcasr_ctc_mwer_workspace_bytes(T, B, C, N, max_label_len) (0 for arguments the call would
+ * refuse): the table, both fp64 lattices of every row ([T] frames of 64 * ceil-to-{1,2,3,6,18}
+ * ((2 * max_label_len + 1) / 64) states), two fp64 per row and one word per utterance; its
+ * contents on entry do not matter.
+ * Left out on purpose: a language model term in s_i, the reference appended to the list, risks
+ * computed inside the call. */
+size_t ctcasr_ctc_mwer_workspace_bytes(int T, int B, int C, int N, int max_label_len);
+int ctcasr_ctc_mwer(const float *logits, const int32_t *seq_len, int T, int B, int C, int blank,
+                    const int32_t *labels, const int32_t *label_offsets, const int32_t *n_hyps,
+                    const float *risk, int N, int max_label_len, float scale, int accumulate,
+                    float *grad, float *expected_risk, float *score, float *posterior,
+                    int32_t *status, void *workspace, size_t workspace_bytes,
+                    ctcasr_stream_t stream);
+
 /* ---- K11: CTC forced alignment ----------------------------------------------------------------
  * The Viterbi (max-sum) form of K9's alpha recursion: the single best alignment of each
  * utterance's label to its frames (no counterpart in the reference).  Inputs and status codes
