@@ -21,6 +21,9 @@
 // LM = true fuses a language model in where TensorFlow calls its BeamScorer (`BeamLm` below:
 // ExpandState / GetStateExpansionScore in both loops, GetStateEndExpansionScore at the end);
 // LM = false compiles all of it out and is the search as it was.
+// K24: the scorer is a policy, `LM` its number - 0 none, 1 the dense automaton, 2 a word n-gram
+// over a lexicon trie (`BeamWordLm`): the same search, the same places where the scorer enters; only
+// where an edge's score and state come from differs.
 #include "common.h"
 
 #define BEAM_THREADS 256
@@ -69,8 +72,8 @@ struct BeamLdsLm : BeamLds {
     int lm_state[BEAM_SLOTS];
     float lm_e[BEAM_SLOTS];
 };
-template <bool LM> struct BeamLdsOf { typedef BeamLds type; };
-template <> struct BeamLdsOf<true> { typedef BeamLdsLm type; };
+template <int LM> struct BeamLdsOf { typedef BeamLdsLm type; };
+template <> struct BeamLdsOf<0> { typedef BeamLds type; };
 
 // The scorer of the fused search: a deterministic weighted automaton over label ids, TensorFlow's
 // BeamScorer with an integer state.  Entering label c in state s costs score[s * C + c] (the
@@ -83,6 +86,106 @@ struct BeamLm {
     const float *final;
     int states;
 };
+
+// K24, the implicit scorer: the automaton is the composition of a lexicon trie with the contexts of
+// a back-off word n-gram, far too large to tabulate.  A leaf's state is the pair (trie node,
+// context).  The trie node is `lm_state` of the leaf's slot; the context is a constant of the
+// leaf's tree node and lives in the workspace (`pool_ctx`), next to the memo of the node's space
+// edge (`pool_sp_ctx` < 0: not computed yet; `pool_sp_score`: its float bits) - LDS has no room
+// for a second int per slot.  The three pool pointers are part of the struct so that the kernel's
+// arguments are those of the dense scorer's kernel; the host fills them in from the workspace.
+// Every index read from a table is clamped into its array.
+struct BeamWordLm {
+    const int *trie_next;            // [nodes, C]  -1: no edge; node 0 the root, 1 the OOV sink
+    const int *trie_word;            // [nodes]     word id that ends here, or -1
+    const long long *ctx_begin;      // [contexts + 1]
+    const int *succ_word;            // [succ]      ascending inside a context's range
+    const double *succ_lp;           // [succ]
+    const int *succ_ctx;             // [succ]
+    const double *ctx_backoff;       // [contexts]
+    const int *ctx_parent;           // [contexts]
+    long long succ;
+    int nodes, contexts, order, space;
+    double bonus, oov;               // oov -inf: closed vocabulary
+    long long *stats;                // NULL or [B, 2]: branches expanded, space edges looked up
+    int *pool_ctx, *pool_sp_ctx, *pool_sp_score;
+};
+template <int LM> struct BeamLmOf { typedef BeamLm type; };
+template <> struct BeamLmOf<2> { typedef BeamWordLm type; };
+
+// the scorer as one utterance sees it: the word model's pools start at the utterance's first node
+__device__ __forceinline__ const BeamLm &lm_of_row(const BeamLm &lm, size_t) { return lm; }
+__device__ __forceinline__ BeamWordLm lm_of_row(BeamWordLm lm, size_t first) {
+    lm.pool_ctx += first;
+    lm.pool_sp_ctx += first;
+    lm.pool_sp_score += first;
+    return lm;
+}
+
+#define WORDLM_MAX_ORDER 5
+#define WORDLM_MAX_PROBES 11     // 64-way narrowing of a range below 2^63 to <= 64 entries
+
+// Wd(h, w), by a whole wave (all 64 lanes active, every argument wave-uniform): search h's
+// successor range for w; found: acc += succ_lp, done; else acc += ctx_backoff[h], h = ctx_parent[h],
+// again - at most `order` searches, each of at most WORDLM_MAX_PROBES + 1 probes (64 pivots per
+// probe: one coalesced-ish load per step instead of six dependent ones of a one-lane bisection).
+// Tables that would run longer give -inf (and context 0).  The adds are in fp64, in that order.
+__device__ double wordlm_wd(const BeamWordLm &m, int h, int w, int lane, int &next_ctx) {
+    double acc = 0.0;
+    next_ctx = 0;
+    h = min(max(h, 0), m.contexts - 1);
+    for (int it = 0; it < m.order; ++it) {
+        long long lo = min(max(m.ctx_begin[h], 0ll), m.succ);
+        long long hi = min(max(m.ctx_begin[h + 1], lo), m.succ);
+        for (int probe = 0; probe < WORDLM_MAX_PROBES && hi - lo > 64; ++probe) {
+            const long long step = (hi - lo + 63) / 64;
+            const long long p = lo + lane * step;
+            const int k = __popcll(__ballot(p < hi && m.succ_word[p] <= w));
+            if (k == 0) { hi = lo; break; }        // w is below the range's first word
+            const long long first = lo + (k - 1) * step;     // the last pivot <= w
+            hi = min(first + step, hi);
+            lo = first;
+        }
+        if (hi - lo > 64) return -INFINITY;
+        const long long p = lo + lane;
+        const unsigned long long hit = __ballot(p < hi && m.succ_word[p] == w);
+        if (hit) {
+            const long long at = lo + (__ffsll((long long)hit) - 1);
+            acc += m.succ_lp[at];
+            next_ctx = min(max(m.succ_ctx[at], 0), m.contexts - 1);
+            return acc;
+        }
+        acc += m.ctx_backoff[h];
+        h = min(max(m.ctx_parent[h], 0), m.contexts - 1);
+    }
+    return -INFINITY;
+}
+
+// The score of the word that trie node n closes in context h, without the bonus, and the context
+// after it: Wd(h, w) for a vocabulary word; with OOV on Wd(h, <unk>) in the sink and Wd(h, <unk>) +
+// oov anywhere else; -inf where nothing closes (the root: a leading or doubled space).  `walks`
+// counts the back-off walks actually run (for `stats`).
+__device__ double wordlm_close(const BeamWordLm &m, int n, int h, int lane, int &ctx, int &walks) {
+    ctx = 0;
+    if (n == 0) return -INFINITY;
+    const int w = n == 1 ? -1 : m.trie_word[n];
+    if (w >= 0) { ++walks; return wordlm_wd(m, h, w, lane, ctx); }
+    if (!(m.oov > -INFINITY)) return -INFINITY;
+    ++walks;
+    const double d = wordlm_wd(m, h, 0, lane, ctx);
+    return n == 1 ? d : d + m.oov;
+}
+
+// The end score of a hypothesis in (n, h): at the root Wd(h, </s>); where n closes a word that
+// word's score (no bonus) + Wd(ctx', </s>); else -inf.  fp64, rounded once.
+__device__ float wordlm_end(const BeamWordLm &m, int n, int h, int lane) {
+    int ctx, walks = 0;
+    if (n == 0) return (float)wordlm_wd(m, h, 1, lane, ctx);
+    const double d = wordlm_close(m, n, h, lane, ctx, walks);
+    if (!(d > -INFINITY)) return -INFINITY;
+    int unused;
+    return (float)(d + wordlm_wd(m, ctx, 1, lane, unused));
+}
 
 // a ranks below b in the heap order (lower total; equal totals: the younger node)
 __device__ __forceinline__ bool worse(const BeamLds &L, int a, int b) {
@@ -160,12 +263,17 @@ __device__ void bitonic_sort(unsigned long long *keys, int n_pow2, int tid) {
 // coalesced row load each per branch, fetched one branch ahead like the children row - and a
 // child's value is x[c] + (prev + score): TensorFlow's GetStateExpansionScore.  An edge of -inf
 // is no candidate and creates no node.
+// LM == 2: lane c holds the trie's edge (branch's node, c) instead - one coalesced row load -, the
+// space's lane the memo of the branch's tree node; the context and the memo come from the
+// workspace one branch ahead too.  The memo is filled by the whole wave on the node's first
+// expansion (`wordlm_close`: a chain of dependent loads, run once per tree node, not per frame).
 // NBEST changes nothing here: it gives the n-best kernels copies of their own, so that the
 // inliner sees the top-1 kernels' callees exactly as it did before there were four kernels.
-template <int PER, bool LM, bool NBEST>
+template <int PER, int LM, bool NBEST>
 __device__ void beam_expand(typename BeamLdsOf<LM>::type &L, int lane, int W, int C, int blank,
                             int nslots, int nheap0, int *pool_parent, int *pool_label,
-                            int *pool_children, int nodes_per_utt, const BeamLm &lm) {
+                            int *pool_children, int nodes_per_utt,
+                            const typename BeamLmOf<LM>::type &lm) {
     int nheap = nheap0, nfree = 0, nodes = L.misc[1];
     for (int base = 0; base < nslots; base += 64) {      // free slots, ordered
         const bool is_free = base + lane < nslots && !L.alive[base + lane];
@@ -218,16 +326,29 @@ __device__ void beam_expand(typename BeamLdsOf<LM>::type &L, int lane, int W, in
     // the model's rows of a branch's state, likewise (the blank's column is never read)
     float lms_next = -INFINITY;
     int lmn_next = 0;
+    // LM == 2: the branch's trie node, context and space-edge memo (context < 0: not computed)
+    int wn_next = 0, wh_next = 0, wsc_next = 0, wss_next = 0;
+    int n_expanded = 0, n_lookups = 0;
     auto lm_fetch = [&](int slot) {
-        if constexpr (LM) {
+        if constexpr (LM == 1) {
             if (lane < C && lane != blank) {
                 const size_t at = (size_t)L.lm_state[slot] * C + lane;
                 lms_next = lm.score[at];
                 lmn_next = min(max(lm.next[at], 0), lm.states - 1);
             }
         }
+        if constexpr (LM == 2) {
+            const int node = L.node[slot];
+            wn_next = L.lm_state[slot];
+            wh_next = gload(&lm.pool_ctx[node]);
+            wsc_next = gload(&lm.pool_sp_ctx[node]);
+            wss_next = gload(&lm.pool_sp_score[node]);
+            lmn_next = -1;
+            if (lane < C && lane != blank && lane != lm.space && wn_next != 1)
+                lmn_next = min(max(lm.trie_next[(size_t)wn_next * C + lane], -1), lm.nodes - 1);
+        }
     };
-    if constexpr (LM) {
+    if constexpr (LM != 0) {
         if (nheap0 > 0) lm_fetch(L.branches[0]);
     }
     for (int j = 0; j < nheap0; ++j) {
@@ -236,9 +357,11 @@ __device__ void beam_expand(typename BeamLdsOf<LM>::type &L, int lane, int W, in
         const int kidv = kid_next;           // tree nodes of this branch's children (-1: none yet)
         if (j + 1 < nheap0 && lane < C)
             kid_next = gload(&pool_children[(size_t)L.node[L.branches[j + 1]] * C + lane]);
-        const float lms = lms_next;          // the model's edges out of this branch's state
-        const int lmn = lmn_next;
-        if constexpr (LM) {
+        float lms = lms_next;                // the model's edges out of this branch's state
+        int lmn = lmn_next;
+        const int wn = wn_next, wh = wh_next;
+        int wsc = wsc_next, wss = wss_next;
+        if constexpr (LM != 0) {
             if (j + 1 < nheap0) lm_fetch(L.branches[j + 1]);
         }
         // branches come in descending old total and the bottom only rises: once a branch cannot
@@ -252,11 +375,34 @@ __device__ void beam_expand(typename BeamLdsOf<LM>::type &L, int lane, int W, in
         }
         if (!(ot > -INFINITY)) continue;
         if (lane == 0) L.expanded[s] = 1;
+        if constexpr (LM == 2) {
+            ++n_expanded;
+            if (wsc < 0) {      // the node's first expansion: its space edge, once and for all
+                const double d = wordlm_close(lm, wn, wh, lane, wsc, n_lookups);
+                wss = __float_as_int((float)(d + lm.bonus));
+                if (lane == 0) {
+                    gstore(&lm.pool_sp_score[L.node[s]], wss);
+                    gstore(&lm.pool_sp_ctx[L.node[s]], wsc);
+                }
+            }
+            if (lane == lm.space) {
+                lms = __int_as_float(wss);
+                lmn = 0;
+            } else if (lane < C && lane != blank) {
+                if (wn == 1 || lmn >= 0) {
+                    lms = (float)lm.bonus;
+                    lmn = wn == 1 ? 1 : lmn;
+                } else {
+                    lms = lm.oov > -INFINITY ? (float)(lm.oov + lm.bonus) : -INFINITY;
+                    lmn = 1;
+                }
+            }
+        }
         const int slabel = L.label[s];
         const unsigned long long active = L.kids_in_beam[s];
         float v = -INFINITY;
         if (lane < C && lane != blank && !((active >> lane) & 1ull)) {
-            if constexpr (LM) v = L.x[lane] + ((lane == slabel ? L.o_blank[s] : ot) + lms);
+            if constexpr (LM != 0) v = L.x[lane] + ((lane == slabel ? L.o_blank[s] : ot) + lms);
             else v = L.x[lane] + (lane == slabel ? L.o_blank[s] : ot);
         }
         // children that could enter right now; the bottom only rises while we insert
@@ -306,6 +452,14 @@ __device__ void beam_expand(typename BeamLdsOf<LM>::type &L, int lane, int W, in
                     gstore(&pool_label[kid], c);
                 }
                 if (lane < C) gstore(&pool_children[(size_t)kid * C + lane], -1);
+                if constexpr (LM == 2) {
+                    // the child's context, and a memo that says "not computed": a workspace that
+                    // another launch left behind never serves a stale entry
+                    if (lane == 0) {
+                        gstore(&lm.pool_ctx[kid], c == lm.space ? wsc : wh);
+                        gstore(&lm.pool_sp_ctx[kid], -1);
+                    }
+                }
             }
             if (lane == 0) {
                 L.node[ns] = kid; L.label[ns] = c; L.parent[ns] = pnode; L.pslot[ns] = s;
@@ -314,7 +468,7 @@ __device__ void beam_expand(typename BeamLdsOf<LM>::type &L, int lane, int W, in
                 L.kids_in_beam[ns] = 0ull;
                 atomicOr(&L.kids_in_beam[s], 1ull << c);
             }
-            if constexpr (LM) {
+            if constexpr (LM != 0) {
                 const int st = __builtin_amdgcn_readlane(lmn, c);
                 const int e = __builtin_amdgcn_readlane(__float_as_int(lms), c);
                 if (lane == 0) { L.lm_state[ns] = st; L.lm_e[ns] = __int_as_float(e); }
@@ -339,19 +493,22 @@ __device__ void beam_expand(typename BeamLdsOf<LM>::type &L, int lane, int W, in
         }
     }
     if (lane == 0) { L.misc[0] = nheap; L.misc[1] = nodes; }
+    if constexpr (LM == 2) {
+        if (lane == 0) { L.misc[4] += n_expanded; L.misc[5] += n_lookups; }
+    }
 }
 
 // LM = false is the search without a model: every use of `lm` is compiled out.
 // NBEST = true returns the `top_paths` best leaves of the final beam instead of one (out
 // [B, top_paths, T], out_len / logp [B, top_paths], n_paths [B]); the search loop is the same, and
 // NBEST = false reads neither `top_paths` nor `n_paths` and is the kernel as it was.
-template <bool LM, bool NBEST>
+template <int LM, bool NBEST>
 __global__ void __launch_bounds__(BEAM_THREADS)
 beam_decode_kernel(const float *__restrict__ logits, const int *__restrict__ seq_len, int T, int B,
                    int C, int blank, int W, int norm_mode, int *__restrict__ out,
                    int *__restrict__ out_len, float *__restrict__ logp, int *pool_parent,
                    int *pool_label, int *pool_slot, int *pool_children, int nodes_per_utt,
-                   BeamLm lm, int top_paths, int *__restrict__ n_paths) {
+                   typename BeamLmOf<LM>::type lm_all, int top_paths, int *__restrict__ n_paths) {
     typedef typename BeamLdsOf<LM>::type Lds;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     Lds &L = *reinterpret_cast<Lds *>(smem);
@@ -362,6 +519,7 @@ beam_decode_kernel(const float *__restrict__ logits, const int *__restrict__ seq
     pool_label += (size_t)b * nodes_per_utt;
     pool_slot += (size_t)b * nodes_per_utt;
     pool_children += (size_t)b * nodes_per_utt * C;
+    const auto &lm = lm_of_row(lm_all, (size_t)b * nodes_per_utt);
     const int nslots = 2 * W;
 
     for (int s = tid; s < nslots; s += BEAM_THREADS) { L.alive[s] = 0; L.was_alive[s] = 0; }
@@ -376,7 +534,11 @@ beam_decode_kernel(const float *__restrict__ logits, const int *__restrict__ seq
     if (tid == 0) {
         L.node[0] = 0; L.label[0] = -1; L.parent[0] = -1; L.alive[0] = 1;
         L.n_total[0] = 0.f; L.n_blank[0] = 0.f; L.n_label[0] = -INFINITY;
-        if constexpr (LM) { L.lm_state[0] = 0; L.lm_e[0] = 0.f; }
+        if constexpr (LM != 0) { L.lm_state[0] = 0; L.lm_e[0] = 0.f; }
+        if constexpr (LM == 2) {
+            gstore(&lm.pool_ctx[0], 0); gstore(&lm.pool_sp_ctx[0], -1);
+            L.misc[4] = 0; L.misc[5] = 0;
+        }
         gstore(&pool_parent[0], -1); gstore(&pool_label[0], -1); gstore(&pool_slot[0], 0);
         L.heap[0] = 0;
         L.misc[0] = 1; L.misc[1] = 1; L.misc[3] = 0;
@@ -418,7 +580,7 @@ beam_decode_kernel(const float *__restrict__ logits, const int *__restrict__ seq
             const int lab = L.label[s];
             if (lab >= 0) {
                 const int ps = L.pslot[s];
-                if constexpr (LM) {
+                if constexpr (LM != 0) {
                     if (ps >= 0)
                         nl = lse2f(nl, (lab == L.label[ps] ? L.o_blank[ps] : L.o_total[ps]) +
                                            L.lm_e[s]);
@@ -479,7 +641,21 @@ beam_decode_kernel(const float *__restrict__ logits, const int *__restrict__ seq
     }
 
     // ---- best leaf and its label path --------------------------------------------------------------
-    if constexpr (LM) {
+    if constexpr (LM == 2) {
+        // the end scores of the (at most W) final leaves, one wave per leaf, all waves at work
+        const int nheap = L.misc[0];
+        for (int i = tid >> 6; i < nheap; i += BEAM_THREADS / 64) {
+            const int s = L.heap[i];
+            const float e = wordlm_end(lm, L.lm_state[s], gload(&lm.pool_ctx[L.node[s]]), lane);
+            if (lane == 0) L.n_total[s] += e;
+        }
+        if (lm.stats && tid == 0) {
+            lm.stats[2 * b] = L.misc[4];
+            lm.stats[2 * b + 1] = L.misc[5];
+        }
+        __syncthreads();
+    }
+    if constexpr (LM == 1) {
         // TensorFlow's TopPaths: the end score of each leaf's state joins its total first
         if (lm.final) {
             const int nheap = L.misc[0];
@@ -570,12 +746,19 @@ extern "C" size_t ctcasr_ctc_beam_workspace_bytes(int T, int B, int C, int beam_
 
 namespace {
 
+// ... and with a word model three more ints per tree node: its context and its space-edge memo
+size_t wordlm_workspace_bytes(int T, int B, int C, int beam_width) {
+    if (T <= 0 || B <= 0 || C <= 0 || beam_width <= 0) return 0;
+    return (size_t)B * nodes_per_utt(T, beam_width, C) * (6 + (size_t)C) * sizeof(int) + 256;
+}
+
 // arguments, limits, workspace layout and launch of all entry points (lm: NULL without a model;
 // top_paths 0: the top-1 entry points, whose `logp` may be NULL and which have no `n_paths`)
 int beam_launch(const float *logits, const int32_t *seq_len, int T, int B, int C, int blank,
                 int beam_width, int norm_mode, const BeamLm *lm, int top_paths, int32_t *out,
                 int32_t *out_len, float *logp, int32_t *n_paths, void *workspace,
-                size_t workspace_bytes, ctcasr_stream_t stream) {
+                size_t workspace_bytes, ctcasr_stream_t stream,
+                const BeamWordLm *word = nullptr) {
     const bool nbest = top_paths != 0 || n_paths;
     if (nbest && (!logp || !n_paths || top_paths < 1 || top_paths > beam_width))
         return CTCASR_ERR_BAD_ARGUMENT;
@@ -584,15 +767,21 @@ int beam_launch(const float *logits, const int32_t *seq_len, int T, int B, int C
         return CTCASR_ERR_BAD_ARGUMENT;
     if (lm && (!lm->next || !lm->score || lm->states < 1)) return CTCASR_ERR_BAD_ARGUMENT;
     if (beam_width > BEAM_MAX_WIDTH || C > BEAM_MAX_CLASSES) return CTCASR_ERR_UNSUPPORTED;
-    if (!workspace || workspace_bytes < ctcasr_ctc_beam_workspace_bytes(T, B, C, beam_width))
+    if (!workspace || workspace_bytes < (word ? wordlm_workspace_bytes(T, B, C, beam_width)
+                                              : ctcasr_ctc_beam_workspace_bytes(T, B, C, beam_width)))
         return CTCASR_ERR_WORKSPACE;
     const size_t n = nodes_per_utt(T, beam_width, C);
     int *pool_parent = reinterpret_cast<int *>(workspace);
     int *pool_label = pool_parent + (size_t)B * n;
     int *pool_slot = pool_label + (size_t)B * n;
     int *pool_children = pool_slot + (size_t)B * n;
-    const size_t lds = lm ? sizeof(BeamLdsLm) : sizeof(BeamLds);
-#define BEAM_LAUNCH(LM, NBEST)                                                                  \
+    const size_t lds = lm || word ? sizeof(BeamLdsLm) : sizeof(BeamLds);
+    // the word model's three pools trail the plain search's four
+    BeamWordLm wlm = word ? *word : BeamWordLm{};
+    wlm.pool_ctx = pool_children + (size_t)B * n * C;
+    wlm.pool_sp_ctx = wlm.pool_ctx + (size_t)B * n;
+    wlm.pool_sp_score = wlm.pool_sp_ctx + (size_t)B * n;
+#define BEAM_LAUNCH(LM, NBEST, MODEL)                                                                \
     do {                                                                                        \
         if (hipFuncSetAttribute(reinterpret_cast<const void *>(&beam_decode_kernel<LM, NBEST>), \
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=        \
@@ -600,13 +789,14 @@ int beam_launch(const float *logits, const int32_t *seq_len, int T, int B, int C
             return CTCASR_ERR_LAUNCH;                                                           \
         beam_decode_kernel<LM, NBEST><<<B, BEAM_THREADS, lds, (hipStream_t)stream>>>(           \
             logits, seq_len, T, B, C, blank, beam_width, norm_mode, out, out_len, logp,         \
-            pool_parent, pool_label, pool_slot, pool_children, (int)n, lm ? *lm : BeamLm{},     \
-            top_paths, n_paths);                                                                \
+            pool_parent, pool_label, pool_slot, pool_children, (int)n, MODEL, top_paths,        \
+            n_paths);                                                                           \
     } while (0)
-    if (lm && nbest) BEAM_LAUNCH(true, true);
-    else if (lm) BEAM_LAUNCH(true, false);
-    else if (nbest) BEAM_LAUNCH(false, true);
-    else BEAM_LAUNCH(false, false);
+    if (word) BEAM_LAUNCH(2, true, wlm);
+    else if (lm && nbest) BEAM_LAUNCH(1, true, *lm);
+    else if (lm) BEAM_LAUNCH(1, false, *lm);
+    else if (nbest) BEAM_LAUNCH(0, true, BeamLm{});
+    else BEAM_LAUNCH(0, false, BeamLm{});
 #undef BEAM_LAUNCH
     return ctcasr_launch_status();
 }
@@ -656,4 +846,87 @@ extern "C" int ctcasr_ctc_beam_decode_nbest(const float *logits, const int32_t *
     return beam_launch(logits, seq_len, T, B, C, blank, beam_width, norm_mode,
                        lm_next ? &lm : nullptr, top_paths, out, out_len, logp, n_paths, workspace,
                        workspace_bytes, stream);
+}
+
+// ---- K24: word n-gram over a lexicon trie, fused into the search ----------------------------------
+namespace {
+
+// the caller's tables as the kernels take them; false: an argument error
+bool wordlm_tables(const ctcasr_wordlm_t *lm, BeamWordLm *m) {
+    if (!lm || !lm->succ_word || !lm->succ_lp || !lm->succ_ctx || !lm->ctx_begin ||
+        !lm->ctx_backoff || !lm->ctx_parent || lm->num_ctx < 1 || lm->num_succ < 0 ||
+        lm->order < 1 || lm->order > WORDLM_MAX_ORDER)
+        return false;
+    *m = BeamWordLm{};
+    m->trie_next = lm->trie_next;
+    m->trie_word = lm->trie_word;
+    m->ctx_begin = reinterpret_cast<const long long *>(lm->ctx_begin);
+    m->succ_word = lm->succ_word;
+    m->succ_lp = lm->succ_lp;
+    m->succ_ctx = lm->succ_ctx;
+    m->ctx_backoff = lm->ctx_backoff;
+    m->ctx_parent = lm->ctx_parent;
+    m->succ = lm->num_succ;
+    m->nodes = lm->num_nodes;
+    m->contexts = lm->num_ctx;
+    m->order = lm->order;
+    m->space = lm->space;
+    m->bonus = lm->bonus;
+    m->oov = lm->oov_score;
+    m->stats = reinterpret_cast<long long *>(lm->stats);
+    return true;
+}
+
+// one wave per pair, the device function of the search
+__global__ void __launch_bounds__(BEAM_THREADS)
+wordlm_lookup_kernel(BeamWordLm m, const int *__restrict__ ctx, const int *__restrict__ word, int n,
+                     float *__restrict__ score, int *__restrict__ next_ctx) {
+    const int lane = threadIdx.x & 63;
+    const int waves = BEAM_THREADS / 64;
+    for (long long i = (long long)blockIdx.x * waves + (threadIdx.x >> 6); i < n;
+         i += (long long)gridDim.x * waves) {
+        int nc;
+        const double d = wordlm_wd(m, ctx[i], word[i], lane, nc);
+        if (lane == 0) {
+            score[i] = (float)d;
+            next_ctx[i] = nc;
+        }
+    }
+}
+
+}  // namespace
+
+extern "C" size_t ctcasr_ctc_beam_wordlm_workspace_bytes(int T, int B, int C, int beam_width) {
+    return wordlm_workspace_bytes(T, B, C, beam_width);
+}
+
+extern "C" int ctcasr_ctc_beam_decode_wordlm(const float *logits, const int32_t *seq_len, int T,
+                                             int B, int C, int blank, int beam_width,
+                                             int norm_mode, int top_paths,
+                                             const ctcasr_wordlm_t *lm, int32_t *out,
+                                             int32_t *out_len, float *logp, int32_t *n_paths,
+                                             void *workspace, size_t workspace_bytes,
+                                             ctcasr_stream_t stream) {
+    BeamWordLm m;
+    if (top_paths < 1 || !n_paths || !wordlm_tables(lm, &m)) return CTCASR_ERR_BAD_ARGUMENT;
+    if (!m.trie_next || !m.trie_word || m.nodes < 2 || m.space < 0 || m.space >= C ||
+        m.space == blank || !(m.bonus == m.bonus) || m.bonus - m.bonus != 0.0 ||
+        !(m.oov == m.oov) || m.oov == INFINITY)
+        return CTCASR_ERR_BAD_ARGUMENT;
+    return beam_launch(logits, seq_len, T, B, C, blank, beam_width, norm_mode, nullptr, top_paths,
+                       out, out_len, logp, n_paths, workspace, workspace_bytes, stream, &m);
+}
+
+extern "C" int ctcasr_wordlm_lookup(const ctcasr_wordlm_t *lm, const int32_t *ctx,
+                                    const int32_t *word, int n, float *score, int32_t *next_ctx,
+                                    ctcasr_stream_t stream) {
+    BeamWordLm m;
+    if (!wordlm_tables(lm, &m) || !ctx || !word || !score || !next_ctx || n < 0)
+        return CTCASR_ERR_BAD_ARGUMENT;
+    if (n == 0) return CTCASR_OK;
+    const int waves = BEAM_THREADS / 64;
+    const int grid = (int)std::min<long long>(((long long)n + waves - 1) / waves, 1 << 16);
+    wordlm_lookup_kernel<<<grid, BEAM_THREADS, 0, (hipStream_t)stream>>>(m, ctx, word, n, score,
+                                                                          next_ctx);
+    return ctcasr_launch_status();
 }

@@ -70,6 +70,10 @@ SIGNATURES = {
     'ctcasr_ctc_beam_lm_workspace_bytes': (_c_sz, [_c_int] * 4),
     'ctcasr_ctc_beam_decode_lm': (_c_int, [_c_p, _c_p] + [_c_int] * 6 + [_c_p] * 3 + [_c_int] +
                                   [_c_p] * 4 + [_c_sz, _c_p]),
+    'ctcasr_ctc_beam_wordlm_workspace_bytes': (_c_sz, [_c_int] * 4),
+    'ctcasr_ctc_beam_decode_wordlm': (_c_int, [_c_p, _c_p] + [_c_int] * 7 + [_c_p] * 6 +
+                                      [_c_sz, _c_p]),
+    'ctcasr_wordlm_lookup': (_c_int, [_c_p] * 3 + [_c_int] + [_c_p] * 3),
     'ctcasr_ctc_beam_nbest_workspace_bytes': (_c_sz, [_c_int] * 4),
     'ctcasr_ctc_beam_decode_nbest': (_c_int, [_c_p, _c_p] + [_c_int] * 7 + [_c_p] * 3 + [_c_int] +
                                      [_c_p] * 5 + [_c_sz, _c_p]),
@@ -513,6 +517,95 @@ def ctc_beam_decode_nbest(logits, seq_len, beam_width, top_paths, scorer=None, b
     if bool((n_paths < 0).any()):
         raise CtcAsrError('ctc_beam_decode_nbest: prefix-tree pool exhausted')
     return out, out_len, logp, n_paths
+
+
+class WordLm(ctypes.Structure):
+    """``ctcasr_wordlm_t`` of include/ctcasr.h."""
+    _fields_ = [(name, _c_p) for name in ('trie_next', 'trie_word', 'ctx_begin', 'succ_word',
+                                          'succ_lp', 'succ_ctx', 'ctx_backoff', 'ctx_parent')] + \
+               [('num_succ', _c_i64), ('num_nodes', ctypes.c_int32), ('num_ctx', ctypes.c_int32),
+                ('order', ctypes.c_int32), ('space', ctypes.c_int32), ('bonus', _c_d),
+                ('oov_score', _c_d), ('stats', _c_p)]
+
+
+def _wordlm_struct(scorer, device, stats=None):
+    """(`WordLm` of a scaled `lm.WordLmScorer` on ``device``, the tensors it points into)."""
+    tensors = scorer.to(device)
+    names = ('trie_next', 'trie_word', 'ctx_begin', 'succ_word', 'succ_lp', 'succ_ctx',
+             'ctx_backoff', 'ctx_parent')
+    kinds = (torch.int32, torch.int32, torch.int64, torch.int32, torch.float64, torch.int32,
+             torch.float64, torch.int32)
+    # an empty table has no address to give: nothing of it is read then
+    fields = {name: _dev(t, kind, name) if t.numel() else None
+              for name, kind, t in zip(names, kinds, tensors)}
+    return WordLm(num_succ=scorer.num_successors, num_nodes=scorer.num_nodes,
+                  num_ctx=scorer.num_contexts, order=scorer.order, space=scorer.space,
+                  bonus=scorer.bonus, oov_score=scorer.oov_score,
+                  stats=None if stats is None else _dev(stats, torch.int64, 'stats'),
+                  **fields), tensors
+
+
+def ctc_beam_wordlm_workspace_bytes(num_steps, batch, classes, beam_width):
+    return load().ctcasr_ctc_beam_wordlm_workspace_bytes(num_steps, batch, classes,
+                                                         int(beam_width))
+
+
+@_on_tensor_device
+def ctc_beam_decode_wordlm(logits, seq_len, beam_width, scorer, top_paths=1, blank=None,
+                           normalization='max', stats=None):
+    """`ctc_beam_decode_nbest` with a word n-gram fused into the search: ``scorer`` is an
+    `lm.WordLmScorer`, already scaled (`WordLmScorer.scaled`).  Returns (out i32[B, N, T], out_len
+    i32[B, N], logp f32[B, N], n_paths i32[B]) in the order of `ctc_beam_decode_nbest`;
+    ``top_paths`` 1 is the top-1 decode.  ``stats``: None or int64 [B, 2] on the device, which
+    receives the branches expanded and the word lookups performed per utterance."""
+    num_steps, batch, classes = _decode_shape('ctc_beam_decode_wordlm', logits, seq_len)
+    if scorer.num_classes != classes:
+        raise CtcAsrError('ctc_beam_decode_wordlm: the scorer has {} classes, the logits {}.'
+                          .format(scorer.num_classes, classes))
+    blank = classes - 1 if blank is None else blank
+    top_paths = int(top_paths)
+    dev = logits.device
+    if stats is not None:
+        _expect_numel('ctc_beam_decode_wordlm', 'stats', stats, 2 * batch)
+    tables, keep = _wordlm_struct(scorer, dev, stats)
+    rows = max(top_paths, 0)
+    out = torch.empty((batch, rows, num_steps), dtype=torch.int32, device=dev)
+    out_len = torch.empty((batch, rows), dtype=torch.int32, device=dev)
+    logp = torch.empty((batch, rows), dtype=torch.float32, device=dev)
+    n_paths = torch.empty(batch, dtype=torch.int32, device=dev)
+    workspace = _workspace(load().ctcasr_ctc_beam_wordlm_workspace_bytes(
+        num_steps, batch, classes, int(beam_width)), dev)
+    _check(load().ctcasr_ctc_beam_decode_wordlm(
+        _dev(logits, name='logits'), _dev(seq_len, torch.int32, 'seq_len'), num_steps, batch,
+        classes, blank, int(beam_width), {'max': 0, 'log_softmax': 1}[normalization], top_paths,
+        ctypes.addressof(tables), _dev(out, torch.int32, 'out'),
+        _dev(out_len, torch.int32, 'out_len'), _dev(logp, name='logp'),
+        _dev(n_paths, torch.int32, 'n_paths'), _dev(workspace, torch.uint8, 'workspace'),
+        workspace.numel(), _stream()), 'ctc_beam_decode_wordlm')
+    del keep
+    if bool((n_paths < 0).any()):
+        raise CtcAsrError('ctc_beam_decode_wordlm: prefix-tree pool exhausted')
+    return out, out_len, logp, n_paths
+
+
+@_on_tensor_device
+def wordlm_lookup(scorer, ctx, word):
+    """(score f32[n], next_ctx i32[n]) of the pairs (ctx[i], word[i]), int32 on the device: the
+    float32 rounding of the back-off walk Wd, by the device function the search uses."""
+    if ctx.numel() != word.numel():
+        raise CtcAsrError('wordlm_lookup: {} contexts for {} words.'
+                          .format(ctx.numel(), word.numel()))
+    ctx_ptr, word_ptr = _dev(ctx, torch.int32, 'ctx'), _dev(word, torch.int32, 'word')
+    count = ctx.numel()
+    tables, keep = _wordlm_struct(scorer, ctx.device)
+    score = torch.empty(count, dtype=torch.float32, device=ctx.device)
+    next_ctx = torch.empty(count, dtype=torch.int32, device=ctx.device)
+    if count:
+        _check(load().ctcasr_wordlm_lookup(
+            ctypes.addressof(tables), ctx_ptr, word_ptr, count, _dev(score, name='score'),
+            _dev(next_ctx, torch.int32, 'next_ctx'), _stream()), 'wordlm_lookup')
+    del keep
+    return score, next_ctx
 
 
 def ctc_score_workspace_bytes(num_steps, batch, classes, hyps, max_label_len):

@@ -21,7 +21,7 @@ import os
 import numpy as np
 import torch
 
-from ctc_asr_amd import hip, metrics, split_gemm
+from ctc_asr_amd import hip, lm, metrics, split_gemm
 from ctc_asr_amd.labels import num_classes
 from ctc_asr_amd.params import check_mwer_settings, ema_alpha_at
 
@@ -2132,10 +2132,20 @@ class CTCModel:
         if greedy:
             out, out_len = hip.ctc_greedy_decode(logits, seq_len)
         elif scorer is not None:
-            out, out_len, _ = hip.ctc_beam_decode_lm(logits, seq_len, beam_width, scorer)
+            out, out_len = self._fused_top1(logits, seq_len, beam_width, scorer)
         else:
             out, out_len, _ = hip.ctc_beam_decode(logits, seq_len, beam_width)
         return self._decoded_to_text(out.cpu().numpy(), out_len.cpu().numpy(), originals)
+
+    @staticmethod
+    def _fused_top1(logits, seq_len, beam_width, scorer):
+        """(out [B, T], out_len [B]) of the search with ``scorer`` fused in: a word model
+        (`lm.WordLmScorer`) through its own entry point, any other through the dense one."""
+        if isinstance(scorer, lm.WordLmScorer):
+            out, out_len, _, _ = hip.ctc_beam_decode_wordlm(logits, seq_len, beam_width, scorer)
+            return out[:, 0], out_len[:, 0]
+        out, out_len, _ = hip.ctc_beam_decode_lm(logits, seq_len, beam_width, scorer)
+        return out, out_len
 
     @staticmethod
     def _decoded_to_text(out, out_len, originals):
@@ -2160,6 +2170,7 @@ class CTCModel:
         tree pool (256 MB per utterance at width 1024, T' = 500) and ``max_utterances``."""
         beam_width = self.cfg.beam_width if beam_width is None else beam_width
         sizer = hip.ctc_beam_workspace_bytes if scorer is None else \
+            hip.ctc_beam_wordlm_workspace_bytes if isinstance(scorer, lm.WordLmScorer) else \
             hip.ctc_beam_lm_workspace_bytes
         per_utt = max(1, sizer(num_steps, 1, self.cfg.num_classes, beam_width))
         utterances = max(batch, min(max_utterances, budget_bytes // per_utt))
@@ -2186,7 +2197,7 @@ class CTCModel:
             lengths[start:stop] = seq_len
             start = stop
         if scorer is not None:
-            out, out_len, _ = hip.ctc_beam_decode_lm(joint, lengths, beam_width, scorer)
+            out, out_len = self._fused_top1(joint, lengths, beam_width, scorer)
         else:
             out, out_len, _ = hip.ctc_beam_decode(joint, lengths, beam_width)
         out, out_len = out.cpu().numpy(), out_len.cpu().numpy()
@@ -2235,8 +2246,12 @@ class CTCModel:
         from ctc_asr_amd.labels import decode
         beam_width = self.cfg.beam_width if beam_width is None else beam_width
         top_paths = int(top_paths)
-        out, out_len, logp, n_paths = hip.ctc_beam_decode_nbest(logits, seq_len, beam_width,
-                                                                top_paths, scorer=scorer)
+        if isinstance(scorer, lm.WordLmScorer):
+            out, out_len, logp, n_paths = hip.ctc_beam_decode_wordlm(logits, seq_len, beam_width,
+                                                                     scorer, top_paths)
+        else:
+            out, out_len, logp, n_paths = hip.ctc_beam_decode_nbest(logits, seq_len, beam_width,
+                                                                    top_paths, scorer=scorer)
         num_steps, batch = int(logits.shape[0]), int(logits.shape[1])
         # every rank is a hypothesis of the scoring launch; the empty ranks beyond n_paths point
         # at no utterance (status 2: their waves leave at once)

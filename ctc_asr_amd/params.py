@@ -488,13 +488,39 @@ FLAGS.define('string', 'align_output', '', 'align.py: JSON-lines output, one lin
 
 # Language model fused into the beam search (no counterpart in the reference): evaluate.py and
 # predict.py decode with the model of --lm_path; `python -m ctc_asr_amd.lm` builds one.
-FLAGS.define('string', 'lm_path', '', 'Character n-gram (.npz of ctc_asr_amd.lm) the beam search '
-             'scores with; empty: no language model.')
+FLAGS.define('string', 'lm_path', '', 'Character or word n-gram (.npz of ctc_asr_amd.lm) the beam '
+             'search scores with; empty: no language model.')
 FLAGS.define('float', 'lm_weight', 1.0, 'Weight of the language model\'s log-probabilities.')
 FLAGS.define('float', 'lm_bonus', 0.0, 'Added to the score of every emitted label.')
 FLAGS.define('int', 'lm_order', 5, 'lm.py: order of the n-gram to build.')
 FLAGS.define('string', 'lm_corpus_csv', '', 'lm.py: path;label;length manifest whose transcripts '
              'the n-gram is built from.')
+# ... a word n-gram over a lexicon trie (--lm_unit word), looked up on the device when a hypothesis
+# closes a word; --lm_path / --rescore_lm_path take either kind of file.
+LM_UNITS = ('char', 'word')
+
+
+def _lm_unit_check(value):
+    if value not in LM_UNITS:
+        raise ValueError('--lm_unit={} is none of {}.'.format(value, ', '.join(LM_UNITS)))
+
+
+def _oov_score(name):
+    def check(value):
+        if np.isnan(value) or value == np.inf:
+            raise ValueError('--{}={} is neither -inf nor finite.'.format(name, value))
+    return check
+
+
+FLAGS.define('string', 'lm_unit', 'char', 'lm.py: the unit of the n-gram to build, char or word.',
+             _lm_unit_check)
+FLAGS.define('int', 'lm_vocab_size', 0, 'lm.py, word models: keep the most frequent words only '
+             '(0: all); every other word counts as <unk>.', _int_range('lm_vocab_size', 0))
+FLAGS.define('string', 'lm_corpus_text', '', 'lm.py, word models: a plain text file, one transcript '
+             'per line, normalised like a long transcript (digits are refused).')
+FLAGS.define('float', 'lm_oov_score', float('-inf'), 'Word models: added once to a word outside '
+             'the vocabulary, which then scores as <unk>; -inf (the default): closed vocabulary.',
+             _oov_score('lm_oov_score'))
 
 # N-best lists and second-pass rescoring (no counterpart in the reference): evaluate.py and
 # predict.py read the --nbest best hypotheses off the final beam, score each exactly
@@ -511,12 +537,15 @@ def _finite(name):
 
 FLAGS.define('int', 'nbest', 0, 'Hypotheses kept per utterance (0: off; at most --beam_width).',
              _int_range('nbest', *NBEST_RANGE))
-FLAGS.define('string', 'rescore_lm_path', '', 'Character n-gram (.npz of ctc_asr_amd.lm) that '
-             're-ranks the n-best list; needs --nbest >= 2.  Empty: no rescoring.')
+FLAGS.define('string', 'rescore_lm_path', '', 'Character or word n-gram (.npz of ctc_asr_amd.lm) '
+             'that re-ranks the n-best list; needs --nbest >= 2.  Empty: no rescoring.')
 FLAGS.define('float', 'rescore_lm_weight', 1.0, 'Weight of the rescoring model.',
              _finite('rescore_lm_weight'))
 FLAGS.define('float', 'rescore_lm_bonus', 0.0, 'Added per label by the rescoring model.',
              _finite('rescore_lm_bonus'))
+FLAGS.define('float', 'rescore_lm_oov_score', float('-inf'), 'A rescoring word model\'s '
+             '--lm_oov_score (-inf: closed vocabulary); the first pass keeps its own.',
+             _oov_score('rescore_lm_oov_score'))
 
 
 def _validate_nbest(flags):
@@ -529,13 +558,22 @@ def _validate_nbest(flags):
                          .format(flags.nbest))
     if flags.rescore_lm_path:
         from ctc_asr_amd import lm
-        try:
-            lm.load(flags.rescore_lm_path, flags.num_classes)
-        except OSError as error:
-            raise ValueError('--rescore_lm_path: {}'.format(error))
+        lm.check_file('--rescore_lm_path', flags.rescore_lm_path, flags.num_classes)
 
 
 FLAGS.define_validator(_validate_nbest)
+
+
+def _validate_lm_path(flags):
+    """--lm_path names a model to decode with, unless a corpus flag says that `ctc_asr_amd.lm` is
+    about to write it."""
+    if not flags.lm_path or flags.lm_corpus_csv or flags.lm_corpus_text:
+        return
+    from ctc_asr_amd import lm
+    lm.check_file('--lm_path', flags.lm_path, flags.num_classes)
+
+
+FLAGS.define_validator(_validate_lm_path)
 
 # Minimum word error rate training (no counterpart in the reference; off while --mwer_nbest is 0:
 # a step then launches what it always did).  A training step decodes the n-best list of its own

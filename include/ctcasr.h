@@ -264,6 +264,88 @@ int ctcasr_ctc_mwer(const float *logits, const int32_t *seq_len, int T, int B, i
                     int32_t *status, void *workspace, size_t workspace_bytes,
                     ctcasr_stream_t stream);
 
+/* ---- K24: word n-gram language model fused into the beam search ---------------------------------
+ * The search of K10 under a word-level model (no counterpart in the reference).  The decode-time
+ * automaton of a word n-gram is the composition of a lexicon trie with the n-gram's contexts - far
+ * too many states for the dense tables of ctcasr_ctc_beam_decode_lm -, so it stays implicit: a
+ * leaf's state is the pair (n, h) of a trie node and a context, the start state (0, 0), and a
+ * word's score is looked up with back-off when a hypothesis closes the word.  (Added entry points,
+ * as K19 - K23: CTCASR_ABI_VERSION stays.)
+ *
+ * Tables (device pointers; ctcasr_wordlm_t), C the classes of the logits:
+ *   trie_next   int32  [num_nodes, C]  -1: no edge.  Node 0 is the root, node 1 the out-of-
+ *                                      vocabulary sink (its row is never read).
+ *   trie_word   int32  [num_nodes]     the word id that ends at this node, or -1
+ *   ctx_begin   int64  [num_ctx + 1]   start of each context's successor range
+ *   succ_word   int32  [num_succ]      ascending inside a range; context 0 lists every word id
+ *   succ_lp     double [num_succ]      log-probability of the successor (weight folded in)
+ *   succ_ctx    int32  [num_succ]      the context after (h, w)
+ *   ctx_backoff double [num_ctx]       ln bo(h) (weight folded in)
+ *   ctx_parent  int32  [num_ctx]       h less its oldest word
+ * Word id 0 is <unk>, 1 is </s>.  order is 1 .. 5; space is the label that ends a word; bonus is
+ * added per label; oov_score is -inf (closed vocabulary) or finite ("OOV on").
+ *
+ * PINNED (tests/word_lm_reference.py restates it).  Wd(h, w), in fp64: acc = 0; search h's
+ * successor range for w; found: acc += succ_lp, the next context is succ_ctx, stop; otherwise
+ * acc += ctx_backoff[h], h = ctx_parent[h], search again.  The adds happen in exactly that order.
+ * At most `order` searches, each bounded; tables that would run longer give -inf (and context 0).
+ * No loop on the device is open-ended, whatever the tables hold, and every index read from a
+ * table is clamped into its array.  Each score below is computed in fp64 and rounded once to
+ * fp32.  The edge for label c out of (n, h); the blank's column is never read:
+ *   c not the space:  n == 1                       -> (1, h)     bonus
+ *                     m = trie_next[n, c] >= 0     -> (m, h)     bonus
+ *                     no trie edge, OOV on         -> (1, h)     oov_score + bonus
+ *                     no trie edge, OOV off        -> none       -inf
+ *   c the space:      n == 0                       -> none       -inf  (leading / doubled space)
+ *                     w = trie_word[n] >= 0        -> (0, ctx')  Wd(h, w) + bonus
+ *                     n == 1 (OOV on)              -> (0, ctx')  Wd(h, 0) + bonus
+ *                     other n, OOV on              -> (0, ctx')  (Wd(h, 0) + oov_score) + bonus
+ *                     other n, OOV off             -> none       -inf
+ * The end of a hypothesis in (n, h), without a bonus: n == 0: Wd(h, 1); n closes a word or an OOV
+ * by the rules above: (that word's score without the bonus) + Wd(ctx', 1); otherwise -inf.
+ * The search's own arithmetic is that of ctcasr_ctc_beam_decode_lm / _nbest, which read these
+ * values where they read lm_score / lm_next / lm_final: on the dense automaton over the reachable
+ * (n, h) pairs of a small model those entry points return the same bits.
+ *
+ * ctcasr_ctc_beam_decode_wordlm: the outputs, their order, n_paths = -1 on pool exhaustion and the
+ * refusals of ctcasr_ctc_beam_decode_nbest; top_paths = 1 is the top-1 decode.  A NULL table, order
+ * outside 1 .. 5, num_nodes < 2, num_ctx < 1, a space outside [0, C) or equal to the blank, a
+ * non-finite bonus, a NaN or +inf oov_score: CTCASR_ERR_BAD_ARGUMENT.  stats is NULL or int64
+ * [B, 2]: branches expanded and word lookups performed for space edges, per utterance.
+ * The trie node of a leaf lives with the beam; its context, and the space edge of its tree node
+ * (score and next context, computed once, on the node's first expansion), live in the workspace,
+ * initialised where the node is created: ctcasr_ctc_beam_wordlm_workspace_bytes(T, B, C,
+ * beam_width), three ints per tree node more than the plain search's.  Its contents on entry do
+ * not matter.
+ *
+ * ctcasr_wordlm_lookup: score[i] = fp32(Wd(ctx[i], word[i])) and next_ctx[i] for n pairs, by the
+ * device function the search uses (trie_*, space, bonus, oov_score and stats are not read; ctx[i]
+ * is clamped into [0, num_ctx)).  n == 0 returns CTCASR_OK and launches nothing.
+ * Left out on purpose: look-ahead scores inside a word, hashed or quantised storage, orders
+ * above 5, lattice output. */
+typedef struct ctcasr_wordlm {
+    const int32_t *trie_next;
+    const int32_t *trie_word;
+    const int64_t *ctx_begin;
+    const int32_t *succ_word;
+    const double *succ_lp;
+    const int32_t *succ_ctx;
+    const double *ctx_backoff;
+    const int32_t *ctx_parent;
+    int64_t num_succ;
+    int32_t num_nodes, num_ctx, order, space;
+    double bonus, oov_score;
+    int64_t *stats;
+} ctcasr_wordlm_t;
+size_t ctcasr_ctc_beam_wordlm_workspace_bytes(int T, int B, int C, int beam_width);
+int ctcasr_ctc_beam_decode_wordlm(const float *logits, const int32_t *seq_len, int T, int B, int C,
+                                  int blank, int beam_width, int norm_mode, int top_paths,
+                                  const ctcasr_wordlm_t *lm, int32_t *out, int32_t *out_len,
+                                  float *logp, int32_t *n_paths, void *workspace,
+                                  size_t workspace_bytes, ctcasr_stream_t stream);
+int ctcasr_wordlm_lookup(const ctcasr_wordlm_t *lm, const int32_t *ctx, const int32_t *word, int n,
+                         float *score, int32_t *next_ctx, ctcasr_stream_t stream);
+
 /* ---- K11: CTC forced alignment ----------------------------------------------------------------
  * The Viterbi (max-sum) form of K9's alpha recursion: the single best alignment of each
  * utterance's label to its frames (no counterpart in the reference).  Inputs and status codes
