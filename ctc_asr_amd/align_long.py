@@ -23,7 +23,13 @@ audiobook chapter and its text:
    `write_corpus` writes the ``ok`` ones as WAV files with a ``path;label;length`` manifest.
 
 The path has to spend every frame somewhere: audio the text does not cover is not skipped, it
-shows as words of low confidence around it.
+shows as words of low confidence around it - unless the transcript says where such audio lies.
+With ``--transcript_wildcard TOKEN`` every TOKEN of the transcript stands for "something is said
+here that the text does not hold", and ``--align_free_ends`` puts one before the first word and
+after the last: `parse_transcript` turns them into `hip.ALIGN_WILDCARD` labels, step 4 becomes one
+`CTCModel.align_partial_fn` call (``ctcasr_ctc_align_partial``: the wildcard takes one frame or
+more at the log-probability of each frame's best class), the result lists the spans it took as
+``skipped``, and no cut utterance reaches across one.  With neither flag nothing changes.
 """
 
 import json
@@ -37,6 +43,7 @@ from scipy.io import wavfile
 
 from ctc_asr_amd import alignment, storage, transcribe, vad
 from ctc_asr_amd.input_functions import _check_feature_args, num_frames
+from ctc_asr_amd.hip import ALIGN_WILDCARD
 from ctc_asr_amd.labels import decode, encode
 from ctc_asr_amd.model import CTCModel, ModelConfig
 from ctc_asr_amd.params import (CSV_DELIMITER, CSV_FIELDNAMES, FLAGS, MIN_EXAMPLE_LENGTH,
@@ -45,13 +52,11 @@ from ctc_asr_amd.params import (CSV_DELIMITER, CSV_FIELDNAMES, FLAGS, MIN_EXAMPL
 FEATURE_HOP = 160       # samples per feature frame (hip.VAD_HOP: WIN_STEP at 16 kHz)
 
 
-def normalize_transcript(text):
-    """The text as the alphabet spells it: lower case, ``a-z`` kept, apostrophes (``'`` and
-    ``’``) deleted, every other character a space, runs of spaces collapsed, ends stripped.  A
-    digit raises ``ValueError`` naming its offset: numbers must be spelled out, since dropping
-    spoken words silently would misalign everything after them.  An empty result is refused."""
+def _normalize(text, base=0):
+    """`normalize_transcript` of a stretch of text that begins at offset ``base`` of the whole;
+    the result may be empty."""
     out = []
-    for offset, char in enumerate(text):
+    for offset, char in enumerate(text, base):
         if char.isdigit():
             raise ValueError('transcript: the digit "{}" at offset {} must be spelled out as it '
                              'is spoken.'.format(char, offset))
@@ -60,10 +65,64 @@ def normalize_transcript(text):
             out.append(low)
         elif char not in "'’":
             out.append(' ')
-    result = ' '.join(''.join(out).split())
+    return ' '.join(''.join(out).split())
+
+
+def normalize_transcript(text):
+    """The text as the alphabet spells it: lower case, ``a-z`` kept, apostrophes (``'`` and
+    ``’``) deleted, every other character a space, runs of spaces collapsed, ends stripped.  A
+    digit raises ``ValueError`` naming its offset: numbers must be spelled out, since dropping
+    spoken words silently would misalign everything after them.  An empty result is refused."""
+    result = _normalize(text)
     if not result:
         raise ValueError('transcript: nothing is left of the text after normalisation.')
     return result
+
+
+def parse_transcript(text, wildcard='', free_ends=False):
+    """A transcript that may cover only part of the recording -> ``(text, labels)``.
+
+    The text is split on whitespace; a token equal to ``wildcard`` (unless that is empty) is a
+    wildcard, and every run of tokens between two of them goes through `normalize_transcript`'s
+    rules as one stretch (a digit is refused with its offset in the text given).  Wildcards with
+    nothing between them that normalises to a word are one wildcard; ``free_ends`` adds one
+    before the first word and one after the last unless one is there already.  ``labels`` are the
+    words of each run joined by single spaces, with `hip.ALIGN_WILDCARD` between the runs and NO
+    space label beside a wildcard: it takes the pauses around it.  ``text`` is the same in
+    words: the runs and, for each wildcard, the token given, or ``*`` for one that only
+    ``free_ends`` put there.  A transcript without a word is refused."""
+    items, run_begin, run_end = [], None, None        # items: ('words', str) or ('wild', str)
+
+    def close_run():
+        if run_begin is not None:
+            words = _normalize(text[run_begin:run_end], run_begin)
+            if words:
+                items.append(('words', words))
+
+    position = 0
+    for token in text.split():
+        begin = text.index(token, position)
+        position = begin + len(token)
+        if wildcard and token == wildcard:
+            close_run()
+            run_begin = None
+            if not items or items[-1][0] != 'wild':
+                items.append(('wild', token))
+        else:
+            run_begin = begin if run_begin is None else run_begin
+            run_end = position
+    close_run()
+    if not any(kind == 'words' for kind, _ in items):
+        raise ValueError('transcript: nothing is left of the text after normalisation.')
+    if free_ends:
+        if items[0][0] != 'wild':
+            items.insert(0, ('wild', '*'))
+        if items[-1][0] != 'wild':
+            items.append(('wild', '*'))
+    labels = []
+    for kind, value in items:
+        labels.extend(encode(value) if kind == 'words' else [ALIGN_WILDCARD])
+    return ' '.join(value for _, value in items), labels
 
 
 def hop_samples(cfg, drop_every_second_frame):
@@ -90,7 +149,8 @@ def frame_samples(start, length, frames, hop):
 def words_on_samples(path, labels, frame_begin, frame_end, frame_logp, sampling_rate=16000):
     """`alignment.segments` on sample times: the runs of labels between space labels, each from
     the first frame of its first label to the end of the last frame of its last label, with the
-    mean ``frame_logp`` over the frames of its labels.  Returns ``{'word', 'start', 'end',
+    mean ``frame_logp`` over the frames of its labels; a wildcard label ends a word as a space
+    does.  Returns ``{'word', 'start', 'end',
     'confidence', 'start_sample', 'end_sample', 'frames'}`` per word; times in seconds of the
     recording.  One pass over the path, whatever the number of labels."""
     path = np.asarray(path)
@@ -123,7 +183,7 @@ def words_on_samples(path, labels, frame_begin, frame_end, frame_logp, sampling_
         del current[:]
 
     for k, label in enumerate(labels):
-        if label == alignment.SPACE_ID:
+        if label == alignment.SPACE_ID or label == ALIGN_WILDCARD:
             close()
         else:
             current.append(k)
@@ -131,7 +191,37 @@ def words_on_samples(path, labels, frame_begin, frame_end, frame_logp, sampling_
     return words
 
 
-def align_recording(model, wav_path, text, settings=None, batch_size=None, report=None):
+def skipped_on_samples(path, labels, frame_begin, frame_end, sampling_rate=16000):
+    """What the wildcards of ``labels`` took: ``{'after_word', 'start', 'end', 'start_sample',
+    'end_sample', 'frames'}`` per wildcard in time order, from its first frame to the end of its
+    last.  ``after_word`` is the index (among `words_on_samples`' words) of the word before it,
+    -1 for a wildcard before the first word."""
+    path = np.asarray(path)
+    labels = [int(v) for v in labels]
+    if path.size == 0 or (path < 0).all():
+        return []
+    frames = np.nonzero((path & 1) == 1)[0]
+    seen, where, times = np.unique(path[frames] >> 1, return_index=True, return_counts=True)
+    first = dict(zip(seen.tolist(), frames[where].tolist()))
+    last = dict(zip(seen.tolist(), frames[where + times - 1].tolist()))
+    skipped, word, inside = [], -1, False
+    for k, label in enumerate(labels):
+        if label == ALIGN_WILDCARD:
+            a, b = first[k], last[k]
+            skipped.append({'after_word': word,
+                            'start': round(int(frame_begin[a]) / sampling_rate, 6),
+                            'end': round(int(frame_end[b]) / sampling_rate, 6),
+                            'start_sample': int(frame_begin[a]), 'end_sample': int(frame_end[b]),
+                            'frames': b - a + 1})
+        if label == ALIGN_WILDCARD or label == alignment.SPACE_ID:
+            inside = False
+        elif not inside:
+            inside, word = True, word + 1
+    return skipped
+
+
+def align_recording(model, wav_path, text, settings=None, batch_size=None, report=None,
+                    wildcard='', free_ends=False):
     """Place ``text`` on the recording ``wav_path``.  Returns ``{'status', 'score',
     'score_per_frame', 'words', 'pieces', 'audio_seconds', 'speech_seconds'}``: ``status`` one of
     `alignment.STATUS_NAMES` ('infeasible': the speech found is too short for the text),
@@ -140,12 +230,24 @@ def align_recording(model, wav_path, text, settings=None, batch_size=None, repor
     of pieces ('start', 'length' in samples, 'frames' kept and 'offset' of each), the
     concatenated 'logits' [T, C], the normalised 'text' and its 'labels', 'path', 'frame_logp',
     'frame_begin' / 'frame_end' in samples, 'hop_samples' and the recording itself ('audio',
-    int16 on the host)."""
+    int16 on the host).
+
+    ``wildcard`` / ``free_ends``: the text goes through `parse_transcript` in place of
+    `normalize_transcript`.  When that leaves a wildcard among the labels, the alignment is
+    `CTCModel.align_partial_fn`'s and the result also holds ``skipped`` (`skipped_on_samples`),
+    ``wildcard_frames``, ``covered_frames`` and ``score_per_covered_frame`` - the float64 sum of
+    ``frame_logp`` over the frames outside the wildcards, added in time order, over their number
+    (None without such a frame).  ``words`` holds words only; ``score`` and
+    ``score_per_frame`` run over all frames, wildcard frames included."""
     settings = vad.VadSettings.from_flags(FLAGS) if settings is None else settings
     batch_size = FLAGS.batch_size if batch_size is None else int(batch_size)
     feature_type, normalization = _check_feature_args(None, None)
-    text = normalize_transcript(text)
-    labels = encode(text)
+    if wildcard or free_ends:
+        text, labels = parse_transcript(text, wildcard, free_ends)
+    else:
+        text = normalize_transcript(text)
+        labels = encode(text)
+    partial = ALIGN_WILDCARD in labels
     pcm, _ = transcribe.upload_recording(model, wav_path)
     start, length, _ = vad.segment(pcm, settings)
     drop = FLAGS.features_drop_every_second_frame
@@ -159,7 +261,8 @@ def align_recording(model, wav_path, text, settings=None, batch_size=None, repor
     classes = model.cfg.num_classes
     logits = torch.cat(kept, dim=0).contiguous() if kept else \
         torch.empty((0, classes), dtype=torch.float32, device=model.device)
-    path, score, frame_logp, _, status = model.align_long_fn(logits, labels)
+    align_fn = model.align_partial_fn if partial else model.align_long_fn
+    path, score, frame_logp, _, status = align_fn(logits, labels)
     code = int(status.cpu().numpy()[0])
     path, frame_logp = path.cpu().numpy(), frame_logp.cpu().numpy()
     hop = hop_samples(model.cfg, drop)
@@ -176,17 +279,37 @@ def align_recording(model, wav_path, text, settings=None, batch_size=None, repor
                       frame_begin=frame_begin, frame_end=frame_end, hop_samples=hop,
                       audio=pcm.cpu().numpy())
     total = int(logits.shape[0])
-    return {'status': alignment.STATUS_NAMES[code],
-            'score': value if ok else None,
-            'score_per_frame': value / total if ok and total > 0 else None,
-            'words': words,
-            'pieces': len(start),
-            'audio_seconds': int(pcm.numel()) / FLAGS.sampling_rate,
-            'speech_seconds': int(sum(int(v) for v in length)) / FLAGS.sampling_rate}
+    result = {'status': alignment.STATUS_NAMES[code],
+              'score': value if ok else None,
+              'score_per_frame': value / total if ok and total > 0 else None,
+              'words': words,
+              'pieces': len(start),
+              'audio_seconds': int(pcm.numel()) / FLAGS.sampling_rate,
+              'speech_seconds': int(sum(int(v) for v in length)) / FLAGS.sampling_rate}
+    if partial:
+        result.update(partial_summary(path, labels, frame_logp) if ok else
+                      {'wildcard_frames': 0, 'covered_frames': 0,
+                       'score_per_covered_frame': None})
+        result['skipped'] = skipped_on_samples(path, labels, frame_begin, frame_end,
+                                               FLAGS.sampling_rate) if ok else []
+    return result
+
+
+def partial_summary(path, labels, frame_logp):
+    """``{'wildcard_frames', 'covered_frames', 'score_per_covered_frame'}`` of a path over labels
+    that hold wildcards: the last is the float64 sum of ``frame_logp`` over the frames outside
+    the wildcards, added one by one in time order, over their number."""
+    path = np.asarray(path)
+    ids = np.asarray([int(v) for v in labels] + [0], dtype=np.int64)
+    wild = ((path & 1) == 1) & (ids[np.where(path >= 0, path >> 1, len(ids) - 1)] == ALIGN_WILDCARD)
+    covered = np.asarray(frame_logp, dtype=np.float64)[~wild]
+    return {'wildcard_frames': int(wild.sum()), 'covered_frames': int(covered.size),
+            'score_per_covered_frame':
+                float(np.cumsum(covered)[-1]) / covered.size if covered.size else None}
 
 
 def cut_utterances(words, num_samples, max_seconds=15, min_gap_ms=200, pad_ms=100,
-                   min_confidence=None, sampling_rate=16000):
+                   min_confidence=None, sampling_rate=16000, barriers=None):
     """Group aligned words into utterances; integer arithmetic on sample positions throughout
     (``words``: 'word', 'start_sample', 'end_sample', 'confidence', 'frames', in time order).
 
@@ -203,6 +326,15 @@ def cut_utterances(words, num_samples, max_seconds=15, min_gap_ms=200, pad_ms=10
        (the mean ``frame_logp`` over its label frames below ``min_confidence``), else ``ok``;
     7. the label is its words joined by one space.
 
+    ``barriers``: the word indices after which a wildcard lies (`skipped_on_samples`'
+    ``after_word``; -1: before the first word).  A cut after such a word is mandatory - it is a
+    candidate whatever the gap, and ``reach`` never passes it - so no utterance holds audio the
+    text does not cover between two of its words.  Rule 5 stands: the gap between the two words
+    holds the wildcard's span, and an utterance takes at most ``pad`` of it, never more than half.
+    (It may reach into the span at all because the wildcard's border is known to one label frame
+    only: the tie rule lets a wildcard take the later frames of the label before it.)  Every
+    utterance then carries ``'beside_wildcard'``: its first or its last word borders a wildcard.
+
     Returns ``{'index', 'first_word', 'last_word', 'start_sample', 'end_sample', 'label',
     'status', 'forced', 'confidence'}`` per utterance, in time order."""
     rate = int(sampling_rate)
@@ -215,6 +347,10 @@ def cut_utterances(words, num_samples, max_seconds=15, min_gap_ms=200, pad_ms=10
     end = [int(w['end_sample']) for w in words]
     gap = [begin[k + 1] - end[k] for k in range(count - 1)]
     candidate = [g >= min_gap for g in gap] + [True]
+    barrier = set() if barriers is None else set(int(k) for k in barriers)
+    for k in barrier:
+        if 0 <= k < count:
+            candidate[k] = True
     groups, a = [], 0
     while a < count:
         if end[a] - begin[a] + 2 * pad > limit:
@@ -222,7 +358,8 @@ def cut_utterances(words, num_samples, max_seconds=15, min_gap_ms=200, pad_ms=10
             a += 1
             continue
         reach = a
-        while reach + 1 < count and end[reach + 1] - begin[a] + 2 * pad <= limit:
+        while reach + 1 < count and reach not in barrier and \
+                end[reach + 1] - begin[a] + 2 * pad <= limit:
             reach += 1
         cuts = [k for k in range(a, reach + 1) if candidate[k]]
         if cuts:
@@ -258,6 +395,8 @@ def cut_utterances(words, num_samples, max_seconds=15, min_gap_ms=200, pad_ms=10
                            'start_sample': low, 'end_sample': high,
                            'label': ' '.join(w['word'] for w in words[a:b + 1]),
                            'status': status, 'forced': forced, 'confidence': confidence})
+        if barriers is not None:
+            utterances[-1]['beside_wildcard'] = a - 1 in barrier or b in barrier
     return utterances
 
 
@@ -271,7 +410,8 @@ def write_corpus(audio, utterances, corpus_out_dir, corpus_out_csv, stem, sampli
     paths relative to ``corpus_out_dir``, lengths ``'{:.4f}'`` seconds), sorted by length
     ascending, ties in time order, the last row written twice as `synth.write_corpus` does (the
     training reader drops the last row).  `report_path` (next to the CSV) lists EVERY utterance,
-    one JSON line each, with its status, span, confidence and ``forced``.  Returns the rows."""
+    one JSON line each, with its status, span, confidence and ``forced`` (and
+    ``beside_wildcard`` where `cut_utterances` set it).  Returns the rows."""
     audio = np.asarray(audio)
     if audio.dtype != np.int16 or audio.ndim != 1:
         raise ValueError('write_corpus: the recording must be int16 mono samples.')
@@ -285,6 +425,8 @@ def write_corpus(audio, utterances, corpus_out_dir, corpus_out_csv, stem, sampli
                 'start_sample': low, 'end_sample': high, 'confidence': utt['confidence'],
                 'first_word': utt['first_word'], 'last_word': utt['last_word'],
                 'label': utt['label'], 'path': None}
+        if 'beside_wildcard' in utt:
+            line['beside_wildcard'] = bool(utt['beside_wildcard'])
         if utt['status'] == 'ok':
             name = '{}_{:05d}.wav'.format(stem, utt['index'])
             wavfile.write(os.path.join(corpus_out_dir, name), sampling_rate,
@@ -325,8 +467,13 @@ def check_flags():
 def main(argv=None):
     FLAGS.parse(sys.argv[1:] if argv is None else argv)
     check_flags()
+    partial = bool(FLAGS.transcript_wildcard) or FLAGS.align_free_ends
     with open(FLAGS.transcript, 'r', encoding='utf-8') as handle:
-        text = normalize_transcript(handle.read())
+        text = handle.read()
+    if partial:                # (checked here, before anything is loaded; parsed again below)
+        parse_transcript(text, FLAGS.transcript_wildcard, FLAGS.align_free_ends)
+    else:
+        text = normalize_transcript(text)
     if not torch.cuda.is_available():
         raise SystemExit('ctc_asr_amd.align_long needs an MI355X; no GPU is visible.')
     model = CTCModel(ModelConfig.from_flags(FLAGS), 'cuda', seed=FLAGS.random_seed or 1)
@@ -336,14 +483,26 @@ def main(argv=None):
     storage.restore_checkpoint(latest, model, weights='ema' if FLAGS.eval_ema else 'param')
     print('Inputs: {} / {}'.format(FLAGS.input, FLAGS.transcript))
     report = {}
-    result = align_recording(model, FLAGS.input, text, report=report)
+    if partial:
+        result = align_recording(model, FLAGS.input, text, report=report,
+                                 wildcard=FLAGS.transcript_wildcard,
+                                 free_ends=FLAGS.align_free_ends)
+    else:
+        result = align_recording(model, FLAGS.input, text, report=report)
     print('status {}, {} words on {} pieces, audio {:.2f} s, speech {:.2f} s, score per frame {}'
           .format(result['status'], len(result['words']), result['pieces'],
                   result['audio_seconds'], result['speech_seconds'], result['score_per_frame']))
+    skipped = result.get('skipped')
+    if skipped is not None:
+        print('{} wildcard spans on {} frames, {} frames covered, score per covered frame {}'
+              .format(len(skipped), result['wildcard_frames'], result['covered_frames'],
+                      result['score_per_covered_frame']))
     if FLAGS.align_output:
         with open(FLAGS.align_output, 'w', encoding='utf-8') as handle:
             for word in result['words']:
                 handle.write(json.dumps(word) + '\n')
+            for span in skipped or []:
+                handle.write(json.dumps(dict({'skipped': True}, **span)) + '\n')
         print('{} words -> {}'.format(len(result['words']), FLAGS.align_output))
     if result['status'] != 'ok':
         return 1
@@ -351,7 +510,9 @@ def main(argv=None):
         utterances = cut_utterances(result['words'], len(report['audio']), FLAGS.cut_max_seconds,
                                     FLAGS.cut_min_gap_ms, FLAGS.cut_pad_ms,
                                     parse_cut_min_confidence(FLAGS.cut_min_confidence),
-                                    FLAGS.sampling_rate)
+                                    FLAGS.sampling_rate,
+                                    None if skipped is None else
+                                    [span['after_word'] for span in skipped])
         stem = os.path.splitext(os.path.basename(FLAGS.input))[0]
         rows = write_corpus(report['audio'], utterances, FLAGS.corpus_out_dir,
                             FLAGS.corpus_out_csv, stem, FLAGS.sampling_rate)

@@ -34,6 +34,15 @@
 // start) or below S - 2 - 2(T - 1 - t) (cannot reach the end).  A reader substitutes -inf for what
 // a skipped tile would have written.  That is the true value for the first kind; a cell of the
 // second kind has only successors of the second kind, so no cell of a path to the end reads one.
+//
+// K25 (ctcasr_ctc_align_partial) is the same kernels with WILD = true: a label may be
+// CTCASR_ALIGN_WILDCARD, one more class whose log-probability at frame t is fill[t], the fmaxf over
+// the table's row.  It is an ordinary label state - a blank on either side, at least one frame,
+// different from every label, so the skip into and out of it is allowed - and nothing of the
+// lattice, the tiling or live() changes.  fill has no region in the workspace (the sizes are
+// K21's): a tile that holds a wildcard computes it per staged frame from s_lp, in LDS; a tile
+// that holds none does K21's work.  labels[] == -1 never indexes the table: the emission is
+// selected.  K21 launches the WILD = false forms, which are the kernels it always had.
 #include "common.h"
 
 #define ALONG_THREADS 256
@@ -43,6 +52,7 @@
 #define ALONG_STAGE_FRAMES 64     // frames of the table (and of the halo) staged in LDS at a time
 #define ALONG_CHUNK 64            // frames walked per backtrace round trip
 #define ALONG_CHUNK_BYTES 33      // back-pointer bytes per frame that such a walk can touch
+static_assert(ALONG_THREADS == 4 * ALONG_CHUNK, "K25's backtrace puts 4 threads on a frame");
 #define ALONG_MAX_C 64
 #define ALONG_MAX_T (1ll << 22)
 #define ALONG_MAX_L (1ll << 20)
@@ -93,6 +103,8 @@ struct AlongGeom {
 
 // ---- launch 1: the table, the label check, the repeat count --------------------------------
 // Thread g takes frame g and label g.  The row arithmetic is ctc_align_kernel's, line for line.
+// WILD: a wildcard is a label and no repeat; two of them side by side are refused as a bad label.
+template <bool WILD>
 __global__ void __launch_bounds__(ALONG_THREADS)
 ctc_align_long_prep_kernel(const float *__restrict__ logits, const int *__restrict__ labels,
                            long long T, int C, int blank, long long L, int *__restrict__ ctrl,
@@ -100,8 +112,12 @@ ctc_align_long_prep_kernel(const float *__restrict__ logits, const int *__restri
     const long long g = (long long)blockIdx.x * ALONG_THREADS + threadIdx.x;
     if (g < L) {
         const int sym = labels[g];
-        if (sym < 0 || sym >= C || sym == blank) atomicOr(&ctrl[LC_BAD_LABEL], 1);
-        if (g >= 1 && labels[g - 1] == sym) atomicAdd(&ctrl[LC_REPEATS], 1);
+        if (WILD && sym == CTCASR_ALIGN_WILDCARD) {
+            if (g >= 1 && labels[g - 1] == sym) atomicOr(&ctrl[LC_BAD_LABEL], 1);
+        } else {
+            if (sym < 0 || sym >= C || sym == blank) atomicOr(&ctrl[LC_BAD_LABEL], 1);
+            if (g >= 1 && labels[g - 1] == sym) atomicAdd(&ctrl[LC_REPEATS], 1);
+        }
     }
     if (g < T) {
         const float *row = logits + (size_t)g * C;
@@ -150,97 +166,45 @@ ctc_align_long_status_kernel(long long T, long long L, int *__restrict__ ctrl,
 }
 
 // ---- one anti-diagonal of tiles ------------------------------------------------------------
-__global__ void __launch_bounds__(ALONG_THREADS)
-ctc_align_long_tile_kernel(const int *__restrict__ labels, long long T, int C, int blank,
-                           long long L, int tile_frames, long long diag, long long i_lo,
-                           const int *__restrict__ ctrl, const float *__restrict__ table,
-                           double *__restrict__ rowb, double *__restrict__ halo,
-                           unsigned char *__restrict__ bp) {
-    __shared__ float s_lp[ALONG_STAGE_FRAMES * ALONG_MAX_C];
-    __shared__ double s_hin[ALONG_STAGE_FRAMES];
-    __shared__ double s_xch[2][ALONG_WAVES];
+// The body of a tile is ctc_align_long_tile.h, included twice: as K21's kernel, and as the device
+// function below, which K25's kernel calls with FILL = does a thread of this tile hold a wildcard.
+#define ALONG_TILE_ARGS                                                                        \
+    const int *__restrict__ labels, long long T, int C, int blank, long long L,                \
+    int tile_frames, long long diag, long long i_lo, const int *__restrict__ ctrl,             \
+    const float *__restrict__ table, double *__restrict__ rowb, double *__restrict__ halo,     \
+    unsigned char *__restrict__ bp
 
+__global__ void __launch_bounds__(ALONG_THREADS) ctc_align_long_tile_kernel(ALONG_TILE_ARGS) {
+    constexpr bool WILD = false, FILL = false;
+#include "ctc_align_long_tile.h"
+}
+
+template <bool FILL>
+__device__ __forceinline__ void along_partial_tile(ALONG_TILE_ARGS) {
+    constexpr bool WILD = true;
+#include "ctc_align_long_tile.h"
+}
+
+__global__ void __launch_bounds__(ALONG_THREADS) ctc_align_partial_tile_kernel(ALONG_TILE_ARGS) {
+    // Does a thread of this tile hold a wildcard?  A tile without one runs K21's loop: the vote
+    // is all that it pays.  (Every test before the vote is uniform over the block.)
     if (ctrl[LC_STATUS] != 0) return;
     const AlongGeom g(T, C, L, tile_frames);
     const long long i = i_lo + blockIdx.x, j = diag - i;
     if (!g.live(i, j)) return;
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const long long s0 = j * ALONG_TILE_STATES + (long long)tid * ALONG_PER_THREAD;
-    const long long t_first = i * g.tf;
-    const long long t_end = t_first + g.tf < T ? t_first + g.tf : T;
-
-    // states s0 .. s0+3: blank, label k0, blank, label k0 + 1 (where they exist)
-    const long long k0 = s0 >> 1;
-    const bool has_a = k0 < L, has_b = k0 + 1 < L;
-    const int lab_a = has_a ? labels[k0] : blank;
-    const int lab_b = has_b ? labels[k0 + 1] : blank;
-    const bool skip_a = has_a && k0 >= 1 && labels[k0 - 1] != lab_a;   // s0 - 1 -> s0 + 1
-    const bool skip_b = has_b && lab_b != lab_a;                       // s0 + 1 -> s0 + 3
-    const bool has_below = s0 >= 1;
-
-    const double ninf = -(double)INFINITY;
-    double v0 = ninf, v1 = ninf, v2 = ninf, v3 = ninf;
-    if (i > 0 && g.live(i - 1, j)) {
-        const double *src = rowb + (size_t)(i - 1) * g.s_pad + s0;
-        v0 = src[0]; v1 = src[1]; v2 = src[2]; v3 = src[3];
-    }
-    const bool left_live = g.live(i, j - 1);          // writer of the halo at frames >= t_first
-    const bool diag_live = g.live(i - 1, j - 1);      // ... and at frame t_first - 1
-
-    for (long long tc = t_first; tc < t_end; tc += ALONG_STAGE_FRAMES) {
-        const int nf = (int)(t_end - tc < ALONG_STAGE_FRAMES ? t_end - tc : ALONG_STAGE_FRAMES);
-        __syncthreads();          // the frames before are done with the stage
-        for (int e = tid; e < nf * C; e += ALONG_THREADS) s_lp[e] = table[(size_t)tc * C + e];
-        if (tid < nf) {
-            const long long tp = tc + tid - 1;        // the frame the halo value belongs to
-            double h = ninf;
-            if (j > 0 && tp >= 0 && (tp >= t_first ? left_live : diag_live))
-                h = halo[(size_t)(j - 1) * T + tp];
-            s_hin[tid] = h;
-        }
-        __syncthreads();
-        for (int f = 0; f < nf; ++f) {
-            const long long t = tc + f;
-            const float *lp = s_lp + f * C;
-            const double e_blank = (double)lp[blank];
-            const double e_a = (double)lp[lab_a], e_b = (double)lp[lab_b];
-            if (t == 0) {          // (uniform: the first frame of tile row 0)
-                v0 = s0 == 0 ? e_blank : ninf;
-                v1 = (s0 == 0 && has_a) ? e_a : ninf;
-                v2 = ninf;
-                v3 = ninf;
-            } else {
-                const int par = (int)(t & 1);
-                if (lane == 63) s_xch[par][wave] = v3;
-                __syncthreads();
-                double below = __shfl_up(v3, 1, 64);
-                if (lane == 0) below = wave == 0 ? s_hin[f] : s_xch[par][wave - 1];
-                // tie rule: strict > in the order s, s - 1, s - 2
-                double b0 = v0, b1 = v1, b2 = v2, b3 = v3;
-                int m0 = 0, m1 = 0, m2 = 0, m3 = 0;
-                if (has_below && below > b0) { b0 = below; m0 = 1; }
-                if (v0 > b1) { b1 = v0; m1 = 1; }
-                if (skip_a && below > b1) { b1 = below; m1 = 2; }
-                if (v1 > b2) { b2 = v1; m2 = 1; }
-                if (v2 > b3) { b3 = v2; m3 = 1; }
-                if (skip_b && v1 > b3) { b3 = v1; m3 = 2; }
-                v0 = b0 + e_blank;
-                v1 = has_a ? b1 + e_a : ninf;
-                v2 = has_a ? b2 + e_blank : ninf;     // state s0 + 2 exists iff label k0 does
-                v3 = has_b ? b3 + e_b : ninf;
-                if (s0 >= g.S) v0 = ninf;
-                bp[((size_t)j * T + t) * ALONG_THREADS + tid] =
-                    (unsigned char)(m0 | (m1 << 2) | (m2 << 4) | (m3 << 6));
-            }
-            if (tid == ALONG_THREADS - 1) halo[(size_t)j * T + t] = v3;
-        }
-    }
-    double *dst = rowb + (size_t)i * g.s_pad + s0;
-    dst[0] = v0; dst[1] = v1; dst[2] = v2; dst[3] = v3;
+    const long long k0 = (j * ALONG_TILE_STATES + (long long)threadIdx.x * ALONG_PER_THREAD) >> 1;
+    const bool mine = (k0 < L && labels[k0] == CTCASR_ALIGN_WILDCARD) ||
+                      (k0 + 1 < L && labels[k0 + 1] == CTCASR_ALIGN_WILDCARD);
+    if (__syncthreads_or(mine))
+        along_partial_tile<true>(labels, T, C, blank, L, tile_frames, diag, i_lo, ctrl, table,
+                                 rowb, halo, bp);
+    else
+        along_partial_tile<false>(labels, T, C, blank, L, tile_frames, diag, i_lo, ctrl, table,
+                                  rowb, halo, bp);
 }
 
 // ---- last launch: end state, score, backtrace ----------------------------------------------
+template <bool WILD>
 __global__ void __launch_bounds__(ALONG_THREADS)
 ctc_align_long_backtrace_kernel(const int *__restrict__ labels, long long T, int C, int blank,
                                 long long L, int tile_frames, const int *__restrict__ ctrl,
@@ -293,11 +257,32 @@ ctc_align_long_backtrace_kernel(const int *__restrict__ labels, long long T, int
             s_state = s;
         }
         __syncthreads();
-        if (tid < ALONG_CHUNK && t0 - tid >= 0) {
-            const long long t = t0 - tid;
-            const int s = s_path[tid];
-            path[t] = s;
-            if (frame_logp) frame_logp[t] = table[(size_t)t * C + ((s & 1) ? labels[s >> 1] : blank)];
+        if constexpr (!WILD) {
+            if (tid < ALONG_CHUNK && t0 - tid >= 0) {
+                const long long t = t0 - tid;
+                const int s = s_path[tid];
+                path[t] = s;
+                if (frame_logp) frame_logp[t] = table[(size_t)t * C + ((s & 1) ? labels[s >> 1] : blank)];
+            }
+        } else {
+            // 4 threads per frame (ALONG_THREADS = 4 ALONG_CHUNK): on a wildcard frame they take
+            // the columns q, q + 4, ... of the table's row in HBM and fold to fill[t]
+            const int f = tid >> 2, q = tid & 3;
+            const bool in = t0 - f >= 0;
+            const long long t = in ? t0 - f : 0;
+            const int s = in ? s_path[f] : 0;
+            const int sym = (s & 1) ? labels[s >> 1] : blank;
+            const bool wild = in && sym == CTCASR_ALIGN_WILDCARD;
+            const float *row = table + (size_t)t * C;
+            float mx = row[wild ? 0 : sym];
+            if (wild && frame_logp)
+                for (int c = q; c < C; c += 4) mx = fmaxf(mx, row[c]);
+            mx = fmaxf(mx, __shfl_xor(mx, 1, 64));
+            mx = fmaxf(mx, __shfl_xor(mx, 2, 64));
+            if (in && q == 0) {
+                path[t] = s;
+                if (frame_logp) frame_logp[t] = mx;
+            }
         }
         __syncthreads();
     }
@@ -318,11 +303,11 @@ extern "C" size_t ctcasr_ctc_align_long_workspace_bytes(int64_t T, int C, int64_
     return AlongGeom(T, C, L, tile_frames).total;
 }
 
-extern "C" int ctcasr_ctc_align_long(const float *logits, const int32_t *labels, int64_t T, int C,
-                                     int blank, int64_t L, int tile_frames, int32_t *path,
-                                     double *score, float *frame_logp, float *logp,
-                                     int32_t *status, void *workspace, size_t workspace_bytes,
-                                     ctcasr_stream_t stream) {
+template <bool WILD>
+static int along_run(const float *logits, const int32_t *labels, int64_t T, int C, int blank,
+                     int64_t L, int tile_frames, int32_t *path, double *score, float *frame_logp,
+                     float *logp, int32_t *status, void *workspace, size_t workspace_bytes,
+                     ctcasr_stream_t stream) {
     if (!score || !status) return CTCASR_ERR_BAD_ARGUMENT;
     if (!along_args_ok(T, C, L, tile_frames) || blank < 0 || blank >= C)
         return CTCASR_ERR_BAD_ARGUMENT;
@@ -344,7 +329,7 @@ extern "C" int ctcasr_ctc_align_long(const float *logits, const int32_t *labels,
     if (hipMemsetAsync(ctrl, 0, LC_WORDS * sizeof(int), s) != hipSuccess) return CTCASR_ERR_LAUNCH;
     const long long n = T > L ? T : L;
     if (n > 0) {
-        ctc_align_long_prep_kernel<<<(unsigned)((n + ALONG_THREADS - 1) / ALONG_THREADS),
+        ctc_align_long_prep_kernel<WILD><<<(unsigned)((n + ALONG_THREADS - 1) / ALONG_THREADS),
                                      ALONG_THREADS, 0, s>>>(logits, labels, T, C, blank, L, ctrl,
                                                             table, logp);
         if (ctcasr_launch_status() != CTCASR_OK) return CTCASR_ERR_LAUNCH;
@@ -364,12 +349,35 @@ extern "C" int ctcasr_ctc_align_long(const float *logits, const int32_t *labels,
         while (lo <= hi && !g.live(lo, d - lo)) ++lo;
         while (hi >= lo && !g.live(hi, d - hi)) --hi;
         if (lo > hi) continue;
-        ctc_align_long_tile_kernel<<<(unsigned)(hi - lo + 1), ALONG_THREADS, 0, s>>>(
-            labels, T, C, blank, L, tile_frames, d, lo, ctrl, table, rowb, halo, bp);
+        if constexpr (WILD)
+            ctc_align_partial_tile_kernel<<<(unsigned)(hi - lo + 1), ALONG_THREADS, 0, s>>>(
+                labels, T, C, blank, L, tile_frames, d, lo, ctrl, table, rowb, halo, bp);
+        else
+            ctc_align_long_tile_kernel<<<(unsigned)(hi - lo + 1), ALONG_THREADS, 0, s>>>(
+                labels, T, C, blank, L, tile_frames, d, lo, ctrl, table, rowb, halo, bp);
         if (ctcasr_launch_status() != CTCASR_OK) return CTCASR_ERR_LAUNCH;
     }
-    ctc_align_long_backtrace_kernel<<<1, ALONG_THREADS, 0, s>>>(
+    ctc_align_long_backtrace_kernel<WILD><<<1, ALONG_THREADS, 0, s>>>(
         labels, T, C, blank, L, tile_frames, ctrl, table, rowb, bp, path, score, frame_logp,
         status);
     return ctcasr_launch_status();
+}
+
+extern "C" int ctcasr_ctc_align_long(const float *logits, const int32_t *labels, int64_t T, int C,
+                                     int blank, int64_t L, int tile_frames, int32_t *path,
+                                     double *score, float *frame_logp, float *logp,
+                                     int32_t *status, void *workspace, size_t workspace_bytes,
+                                     ctcasr_stream_t stream) {
+    return along_run<false>(logits, labels, T, C, blank, L, tile_frames, path, score, frame_logp,
+                            logp, status, workspace, workspace_bytes, stream);
+}
+
+// K25: the same call with CTCASR_ALIGN_WILDCARD accepted among the labels.
+extern "C" int ctcasr_ctc_align_partial(const float *logits, const int32_t *labels, int64_t T,
+                                        int C, int blank, int64_t L, int tile_frames,
+                                        int32_t *path, double *score, float *frame_logp,
+                                        float *logp, int32_t *status, void *workspace,
+                                        size_t workspace_bytes, ctcasr_stream_t stream) {
+    return along_run<true>(logits, labels, T, C, blank, L, tile_frames, path, score, frame_logp,
+                           logp, status, workspace, workspace_bytes, stream);
 }

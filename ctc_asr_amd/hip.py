@@ -42,6 +42,7 @@ SEQ_BN_ROWS = 64                # ctcasr_seq_bn_*: consecutive rows per chunk of
 ALIGN_LONG_TILE_STATES = 1024   # ctcasr_ctc_align_long: lattice states per tile,
 ALIGN_LONG_TILE_FRAMES = 256    # ... frames per tile when the call passes 0,
 ALIGN_LONG_MAX = (1 << 22, 1 << 20, 64)   # ... and the most frames, labels and classes it serves
+ALIGN_WILDCARD = -1             # ctcasr_ctc_align_partial: the label that matches whatever is said
 SEARCH_MAX_LABEL_LEN = 576      # ctcasr_ctc_search: the longest phrase (2L - 1 <= 1151 states),
 SEARCH_MAX_HITS = 1024          # ... the most hits it stores per pair,
 SEARCH_WAVES = 4                # ... and the pairs one workgroup takes
@@ -89,6 +90,8 @@ SIGNATURES = {
     'ctcasr_ctc_align_long_workspace_bytes': (_c_sz, [_c_i64, _c_int, _c_i64, _c_int]),
     'ctcasr_ctc_align_long': (_c_int, [_c_p, _c_p, _c_i64, _c_int, _c_int, _c_i64, _c_int] +
                               [_c_p] * 6 + [_c_sz, _c_p]),
+    'ctcasr_ctc_align_partial': (_c_int, [_c_p, _c_p, _c_i64, _c_int, _c_int, _c_i64, _c_int] +
+                                 [_c_p] * 6 + [_c_sz, _c_p]),
     'ctcasr_ctc_search_workspace_bytes': (_c_sz, [_c_int] * 3),
     'ctcasr_ctc_search': (_c_int, [_c_p, _c_p] + [_c_int] * 4 + [_c_p, _c_p, _c_int, _c_int] +
                           [_c_p] * 3 + [_c_int, _c_int] + [_c_p] * 9 + [_c_sz, _c_p]),
@@ -760,6 +763,44 @@ def ctc_align_long_workspace_bytes(num_steps, classes, num_labels, tile_frames=0
                                                         int(num_labels), int(tile_frames))
 
 
+def _ctc_align_tiled(name, logits, labels, blank, tile_frames, frame_logp, logp, workspace,
+                     max_workspace_bytes):
+    """`ctc_align_long` and `ctc_align_partial`: one signature, one workspace, two entry points."""
+    if logits.dim() == 3 and logits.shape[1] == 1:
+        logits = logits.reshape(logits.shape[0], logits.shape[2])
+    if logits.dim() != 2:
+        raise CtcAsrError('{}: logits must be [T, C] or [T, 1, C] (got shape {}).'
+                          .format(name, tuple(logits.shape)))
+    num_steps, classes = logits.shape
+    num_labels = int(labels.numel())
+    blank = classes - 1 if blank is None else int(blank)
+    dev = logits.device
+    if num_steps > ALIGN_LONG_MAX[0] or num_labels > ALIGN_LONG_MAX[1] or \
+            classes > ALIGN_LONG_MAX[2]:
+        raise CtcAsrError('{}: T = {}, L = {}, C = {} is outside what the kernel '
+                          'serves (T <= {}, L <= {}, C <= {}).'
+                          .format(name, num_steps, num_labels, classes, *ALIGN_LONG_MAX))
+    need = ctc_align_long_workspace_bytes(num_steps, classes, num_labels, tile_frames)
+    if need > int(max_workspace_bytes):
+        raise ValueError('{}: T = {} frames x L = {} labels needs a workspace of {} '
+                         'bytes, above max_workspace_bytes = {}.'
+                         .format(name, num_steps, num_labels, need, int(max_workspace_bytes)))
+    if workspace is None:
+        workspace = _workspace(need, dev)
+    path = torch.empty(num_steps, dtype=torch.int32, device=dev)
+    score = torch.empty(1, dtype=torch.float64, device=dev)
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    frame_logp = torch.empty(num_steps, dtype=torch.float32, device=dev) if frame_logp else None
+    logp = torch.empty((num_steps, classes), dtype=torch.float32, device=dev) if logp else None
+    _check(getattr(load(), 'ctcasr_' + name)(
+        _dev(logits, name='logits'), _dev(labels, torch.int32, 'labels'), num_steps, classes,
+        blank, num_labels, int(tile_frames), _dev(path, torch.int32, 'path'),
+        _dev(score, torch.float64, 'score'), _dev(frame_logp, name='frame_logp'),
+        _dev(logp, name='logp'), _dev(status, torch.int32, 'status'),
+        _dev(workspace, torch.uint8, 'workspace'), workspace.numel(), _stream()), name)
+    return path, score, frame_logp, logp, status
+
+
 @_on_tensor_device
 def ctc_align_long(logits, labels, blank=None, tile_frames=0, frame_logp=True, logp=False,
                    workspace=None, max_workspace_bytes=64 << 30):
@@ -770,40 +811,22 @@ def ctc_align_long(logits, labels, blank=None, tile_frames=0, frame_logp=True, l
     the log-softmax table the lattice ran on.  A non-zero status is data, not an error.  The
     workspace grows with T x L (2 bits per cell): a need above ``max_workspace_bytes`` raises
     ValueError before anything is allocated."""
-    if logits.dim() == 3 and logits.shape[1] == 1:
-        logits = logits.reshape(logits.shape[0], logits.shape[2])
-    if logits.dim() != 2:
-        raise CtcAsrError('ctc_align_long: logits must be [T, C] or [T, 1, C] (got shape {}).'
-                          .format(tuple(logits.shape)))
-    num_steps, classes = logits.shape
-    num_labels = int(labels.numel())
-    blank = classes - 1 if blank is None else int(blank)
-    dev = logits.device
-    if num_steps > ALIGN_LONG_MAX[0] or num_labels > ALIGN_LONG_MAX[1] or \
-            classes > ALIGN_LONG_MAX[2]:
-        raise CtcAsrError('ctc_align_long: T = {}, L = {}, C = {} is outside what the kernel '
-                          'serves (T <= {}, L <= {}, C <= {}).'
-                          .format(num_steps, num_labels, classes, *ALIGN_LONG_MAX))
-    need = ctc_align_long_workspace_bytes(num_steps, classes, num_labels, tile_frames)
-    if need > int(max_workspace_bytes):
-        raise ValueError('ctc_align_long: T = {} frames x L = {} labels needs a workspace of {} '
-                         'bytes, above max_workspace_bytes = {}.'
-                         .format(num_steps, num_labels, need, int(max_workspace_bytes)))
-    if workspace is None:
-        workspace = _workspace(need, dev)
-    path = torch.empty(num_steps, dtype=torch.int32, device=dev)
-    score = torch.empty(1, dtype=torch.float64, device=dev)
-    status = torch.empty(1, dtype=torch.int32, device=dev)
-    frame_logp = torch.empty(num_steps, dtype=torch.float32, device=dev) if frame_logp else None
-    logp = torch.empty((num_steps, classes), dtype=torch.float32, device=dev) if logp else None
-    _check(load().ctcasr_ctc_align_long(
-        _dev(logits, name='logits'), _dev(labels, torch.int32, 'labels'), num_steps, classes,
-        blank, num_labels, int(tile_frames), _dev(path, torch.int32, 'path'),
-        _dev(score, torch.float64, 'score'), _dev(frame_logp, name='frame_logp'),
-        _dev(logp, name='logp'), _dev(status, torch.int32, 'status'),
-        _dev(workspace, torch.uint8, 'workspace'), workspace.numel(), _stream()),
-        'ctc_align_long')
-    return path, score, frame_logp, logp, status
+    return _ctc_align_tiled('ctc_align_long', logits, labels, blank, tile_frames, frame_logp,
+                            logp, workspace, max_workspace_bytes)
+
+
+@_on_tensor_device
+def ctc_align_partial(logits, labels, blank=None, tile_frames=0, frame_logp=True, logp=False,
+                      workspace=None, max_workspace_bytes=64 << 30):
+    """`ctc_align_long` for a text that covers only part of the recording
+    (``ctcasr_ctc_align_partial``): a label may be `ALIGN_WILDCARD`, one more class that matches
+    whatever is said for one frame or more, at the log-probability of the frame's best class.
+    Arguments, workspace (`ctc_align_long_workspace_bytes`), errors and the returned tuple are
+    `ctc_align_long`'s; on a wildcard frame ``path`` holds the wildcard's odd state and
+    ``frame_logp`` the row maximum of ``logp``.  Status 2 also for two wildcards side by side.
+    Without a wildcard every output equals `ctc_align_long`'s, bit for bit."""
+    return _ctc_align_tiled('ctc_align_partial', logits, labels, blank, tile_frames, frame_logp,
+                            logp, workspace, max_workspace_bytes)
 
 
 def ctc_search_workspace_bytes(num_steps, batch, classes):

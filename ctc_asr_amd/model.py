@@ -1351,6 +1351,15 @@ class CTCModel:
                                   device=self.device)
         return hip.ctc_align_long(logits, labels)
 
+    def align_partial_fn(self, logits, labels):
+        """`align_long_fn` for a text that covers only part of the sequence
+        (``hip.ctc_align_partial``): an id may be ``hip.ALIGN_WILDCARD``, which matches whatever
+        is said for one frame or more.  Returns what `align_long_fn` returns."""
+        if not torch.is_tensor(labels):
+            labels = torch.tensor([int(v) for v in labels], dtype=torch.int32,
+                                  device=self.device)
+        return hip.ctc_align_partial(logits, labels)
+
     def search_fn(self, logits, seq_len, phrases, min_score_per_label, max_hits=16, pairs=None):
         """CTC phrase spotting (``hip.ctc_search``): where in the utterances of ``logits``
         [T, B, C] are the ``phrases`` (a list of id lists) said?  ``pairs`` is a list of (utt,

@@ -703,6 +703,36 @@ FLAGS.define('string', 'cut_min_confidence', '',
              'Utterances whose mean log-probability over their label frames is below this are '
              'reported as low_confidence and not written; empty: off.', parse_cut_min_confidence)
 
+
+def check_transcript_wildcard(token):
+    """--transcript_wildcard: '' (off), or one token that no word of a transcript can be: no
+    whitespace in it, and nothing of it survives `align_long.normalize_transcript`."""
+    if token == '':
+        return
+    if token.split() != [token]:
+        raise ValueError('--transcript_wildcard="{}" holds whitespace: it is one token of the '
+                         'transcript.'.format(token))
+    from ctc_asr_amd.align_long import normalize_transcript    # (imports this module)
+    try:
+        word = normalize_transcript(token)
+    except ValueError as error:
+        if 'digit' in str(error):
+            raise ValueError('--transcript_wildcard="{}" holds a digit.'.format(token))
+        return
+    raise ValueError('--transcript_wildcard="{}" reads as the word "{}": choose a token without '
+                     'letters, such as "[...]".'.format(token, word))
+
+
+# A text that covers only PART of the recording (`hip.ctc_align_partial`): both off by default,
+# and then `align_long` does what it did without them.
+FLAGS.define('string', 'transcript_wildcard', '',
+             'align_long.py: a whitespace-delimited token of the transcript that stands for '
+             '"something is said here that the text does not hold"; empty: off.',
+             check_transcript_wildcard)
+FLAGS.define('bool', 'align_free_ends', False,
+             'align_long.py: the same before the first word and after the last one of the '
+             'transcript (a spoken preamble, a closing line).')
+
 # Phrase spotting (no counterpart in the reference): `python -m ctc_asr_amd.search` looks for the
 # phrases of --phrases in --input, scoring them against the logits (`hip.ctc_search`), not against
 # the decoded text.  Nothing else reads these flags.

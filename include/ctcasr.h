@@ -415,6 +415,42 @@ int ctcasr_ctc_align_long(const float *logits, const int32_t *labels, int64_t T,
                           float *frame_logp, float *logp, int32_t *status, void *workspace,
                           size_t workspace_bytes, ctcasr_stream_t stream);
 
+/* ---- K25: CTC forced alignment with wildcard spans ----------------------------------------------
+ * K21 for a text that covers only part of the recording.  The signature, the outputs, the status
+ * words, the workspace (ctcasr_ctc_align_long_workspace_bytes) and the limits are K21's; the one
+ * difference is that a label may be CTCASR_ALIGN_WILDCARD: "something is said here that the text
+ * does not hold", any number of frames >= 1, at the price the greedy path pays for those frames.
+ * A wildcard in front of the first label and one behind the last free the ends.  (An added entry
+ * point, as K19 - K24: CTCASR_ABI_VERSION stays.)
+ *
+ * PINNED: the wildcard is one more class.
+ *   - its log-probability at frame t is fill[t] = the fmaxf over table_t[0 .. C-1], fp32, of the
+ *     table K21 builds (what the greedy path emits at t);
+ *   - in the lattice it is an ordinary label state: at an odd s, a blank on either side, at least
+ *     one frame; it differs from every label, so the skip s - 2 into it and out of it is allowed;
+ *   - everything else is K21's, operation for operation: delta = max(...) + (double)emission in
+ *     fp64, strict > in the order s, s - 1, s - 2, S - 1 over S - 2 at the end, 2-bit
+ *     back-pointers, the same tiles and the same rule for skipping them.
+ * Reference semantics: append to the table a column C that holds fill and give the wildcard the
+ * id C; the result is K21's on that table of C + 1 classes (tests/align_partial_reference.py).
+ * The limit C <= 64 counts real classes: the column exists in no buffer, logp stays [T, C].
+ *   path       as K21; a wildcard sits at an odd state like any label
+ *   frame_logp fill[t] on a frame the path spends in a wildcard
+ *   score      the fp64 sum along the path, wildcard frames included
+ *   status     2 also for a label that is neither the wildcard nor a valid non-blank class, and
+ *              for two wildcards side by side; 1 T < L + adjacent repeats, where a wildcard
+ *              counts as a label and never as a repeat; 3 as K21.  The order 2, 1, 3 and the
+ *              outputs of a sequence without a path are K21's.
+ * Without a wildcard among the labels every output equals ctcasr_ctc_align_long's, bit for bit,
+ * for every tile_frames.  ctcasr_ctc_align_long itself keeps refusing -1 with status 2.
+ * Left out on purpose: a wildcard that may take no frame, optional words, a price per wildcard
+ * frame. */
+#define CTCASR_ALIGN_WILDCARD (-1)
+int ctcasr_ctc_align_partial(const float *logits, const int32_t *labels, int64_t T, int C,
+                             int blank, int64_t L, int tile_frames, int32_t *path, double *score,
+                             float *frame_logp, float *logp, int32_t *status, void *workspace,
+                             size_t workspace_bytes, ctcasr_stream_t stream);
+
 /* ---- K22: CTC phrase spotting -------------------------------------------------------------------
  * Is this phrase said in here, and where?  (No counterpart in the reference.)  P phrases, each
  * stored once, scored against the logits directly: pair h runs phrase pair_phrase[h] over
