@@ -24,6 +24,8 @@
 // K24: the scorer is a policy, `LM` its number - 0 none, 1 the dense automaton, 2 a word n-gram
 // over a lexicon trie (`BeamWordLm`): the same search, the same places where the scorer enters; only
 // where an edge's score and state come from differs.
+// K26: 3 is the word n-gram with look-ahead - the trie node's table entry `la` is charged on
+// entering the node and settled at the space; the states, the contexts and the memo are K24's.
 #include "common.h"
 
 #define BEAM_THREADS 256
@@ -72,7 +74,7 @@ struct BeamLdsLm : BeamLds {
     int lm_state[BEAM_SLOTS];
     float lm_e[BEAM_SLOTS];
 };
-template <int LM> struct BeamLdsOf { typedef BeamLdsLm type; };
+template <int LM> struct BeamLdsOf { typedef BeamLdsLm type; };   // LM 1, 2, 3
 template <> struct BeamLdsOf<0> { typedef BeamLds type; };
 
 // The scorer of the fused search: a deterministic weighted automaton over label ids, TensorFlow's
@@ -110,12 +112,25 @@ struct BeamWordLm {
     long long *stats;                // NULL or [B, 2]: branches expanded, space edges looked up
     int *pool_ctx, *pool_sp_ctx, *pool_sp_score;
 };
+// K26: the same tables plus the look-ahead table of the trie.  A leaf's `la` is a function of its
+// trie node, which is `lm_state` of its slot: nothing per slot or per tree node is added.  No index
+// is derived from `la`.
+struct BeamWordLmLa : BeamWordLm {
+    const double *la;                // [nodes]
+};
 template <int LM> struct BeamLmOf { typedef BeamLm type; };
 template <> struct BeamLmOf<2> { typedef BeamWordLm type; };
+template <> struct BeamLmOf<3> { typedef BeamWordLmLa type; };
 
 // the scorer as one utterance sees it: the word model's pools start at the utterance's first node
 __device__ __forceinline__ const BeamLm &lm_of_row(const BeamLm &lm, size_t) { return lm; }
 __device__ __forceinline__ BeamWordLm lm_of_row(BeamWordLm lm, size_t first) {
+    lm.pool_ctx += first;
+    lm.pool_sp_ctx += first;
+    lm.pool_sp_score += first;
+    return lm;
+}
+__device__ __forceinline__ BeamWordLmLa lm_of_row(BeamWordLmLa lm, size_t first) {
     lm.pool_ctx += first;
     lm.pool_sp_ctx += first;
     lm.pool_sp_score += first;
@@ -185,6 +200,22 @@ __device__ float wordlm_end(const BeamWordLm &m, int n, int h, int lane) {
     if (!(d > -INFINITY)) return -INFINITY;
     int unused;
     return (float)(d + wordlm_wd(m, ctx, 1, lane, unused));
+}
+
+// K26: what the word that n closes costs in full - K24's, but the sink's word carries oov too (the
+// edge into the sink charged la[1] - la[n] instead of it) -, and the end score that settles la[n].
+__device__ double wordlm_close_la(const BeamWordLmLa &m, int n, int h, int lane, int &ctx,
+                                  int &walks) {
+    const double d = wordlm_close(m, n, h, lane, ctx, walks);
+    return n == 1 ? d + m.oov : d;
+}
+__device__ float wordlm_end_la(const BeamWordLmLa &m, int n, int h, int lane) {
+    int ctx, walks = 0;
+    if (n == 0) return (float)wordlm_wd(m, h, 1, lane, ctx);
+    const double d = wordlm_close_la(m, n, h, lane, ctx, walks);
+    if (!(d > -INFINITY)) return -INFINITY;
+    int unused;
+    return (float)((d - m.la[n]) + wordlm_wd(m, ctx, 1, lane, unused));
 }
 
 // a ranks below b in the heap order (lower total; equal totals: the younger node)
@@ -267,6 +298,8 @@ __device__ void bitonic_sort(unsigned long long *keys, int n_pow2, int tid) {
 // space's lane the memo of the branch's tree node; the context and the memo come from the
 // workspace one branch ahead too.  The memo is filled by the whole wave on the node's first
 // expansion (`wordlm_close`: a chain of dependent loads, run once per tree node, not per frame).
+// LM == 3: as LM == 2, but the non-space lanes' scores are (la[target] - la[node]) + bonus, finished
+// in the prefetch, and the memo holds the space edge less la[node] (`wordlm_close_la`).
 // NBEST changes nothing here: it gives the n-best kernels copies of their own, so that the
 // inliner sees the top-1 kernels' callees exactly as it did before there were four kernels.
 template <int PER, int LM, bool NBEST>
@@ -326,8 +359,9 @@ __device__ void beam_expand(typename BeamLdsOf<LM>::type &L, int lane, int W, in
     // the model's rows of a branch's state, likewise (the blank's column is never read)
     float lms_next = -INFINITY;
     int lmn_next = 0;
-    // LM == 2: the branch's trie node, context and space-edge memo (context < 0: not computed)
+    // LM >= 2: the branch's trie node, context and space-edge memo (context < 0: not computed)
     int wn_next = 0, wh_next = 0, wsc_next = 0, wss_next = 0;
+    double wla_next = 0.0;      // LM == 3: la[the branch's trie node]
     int n_expanded = 0, n_lookups = 0;
     auto lm_fetch = [&](int slot) {
         if constexpr (LM == 1) {
@@ -347,6 +381,30 @@ __device__ void beam_expand(typename BeamLdsOf<LM>::type &L, int lane, int W, in
             if (lane < C && lane != blank && lane != lm.space && wn_next != 1)
                 lmn_next = min(max(lm.trie_next[(size_t)wn_next * C + lane], -1), lm.nodes - 1);
         }
+        if constexpr (LM == 3) {
+            // K26: the non-space lanes' edges are finished here, one branch ahead - state and
+            // score -, so that the gather of la[target] is not in front of the branch's first
+            // insertion.  la[wn] is one address for the wave (a scalar load).
+            const int node = L.node[slot];
+            wn_next = __builtin_amdgcn_readfirstlane(min(max(L.lm_state[slot], 0), lm.nodes - 1));
+            wh_next = gload(&lm.pool_ctx[node]);
+            wsc_next = gload(&lm.pool_sp_ctx[node]);
+            wss_next = gload(&lm.pool_sp_score[node]);
+            wla_next = lm.la[wn_next];
+            lmn_next = 1;
+            lms_next = -INFINITY;
+            if (lane < C && lane != blank && lane != lm.space) {
+                if (wn_next == 1) {
+                    lms_next = (float)lm.bonus;
+                } else {
+                    const int m = min(max(lm.trie_next[(size_t)wn_next * C + lane], -1),
+                                      lm.nodes - 1);
+                    lmn_next = m >= 0 ? m : 1;
+                    if (m >= 0 || lm.oov > -INFINITY)
+                        lms_next = (float)((lm.la[lmn_next] - wla_next) + lm.bonus);
+                }
+            }
+        }
     };
     if constexpr (LM != 0) {
         if (nheap0 > 0) lm_fetch(L.branches[0]);
@@ -361,6 +419,7 @@ __device__ void beam_expand(typename BeamLdsOf<LM>::type &L, int lane, int W, in
         int lmn = lmn_next;
         const int wn = wn_next, wh = wh_next;
         int wsc = wsc_next, wss = wss_next;
+        const double wla = wla_next;
         if constexpr (LM != 0) {
             if (j + 1 < nheap0) lm_fetch(L.branches[j + 1]);
         }
@@ -396,6 +455,21 @@ __device__ void beam_expand(typename BeamLdsOf<LM>::type &L, int lane, int W, in
                     lms = lm.oov > -INFINITY ? (float)(lm.oov + lm.bonus) : -INFINITY;
                     lmn = 1;
                 }
+            }
+        }
+        if constexpr (LM == 3) {
+            ++n_expanded;
+            if (wsc < 0) {      // as above; the memo holds the space edge of this rule
+                const double d = wordlm_close_la(lm, wn, wh, lane, wsc, n_lookups);
+                wss = __float_as_int((float)((d - wla) + lm.bonus));
+                if (lane == 0) {
+                    gstore(&lm.pool_sp_score[L.node[s]], wss);
+                    gstore(&lm.pool_sp_ctx[L.node[s]], wsc);
+                }
+            }
+            if (lane == lm.space) {
+                lms = __int_as_float(wss);
+                lmn = 0;
             }
         }
         const int slabel = L.label[s];
@@ -452,7 +526,7 @@ __device__ void beam_expand(typename BeamLdsOf<LM>::type &L, int lane, int W, in
                     gstore(&pool_label[kid], c);
                 }
                 if (lane < C) gstore(&pool_children[(size_t)kid * C + lane], -1);
-                if constexpr (LM == 2) {
+                if constexpr (LM >= 2) {
                     // the child's context, and a memo that says "not computed": a workspace that
                     // another launch left behind never serves a stale entry
                     if (lane == 0) {
@@ -493,7 +567,7 @@ __device__ void beam_expand(typename BeamLdsOf<LM>::type &L, int lane, int W, in
         }
     }
     if (lane == 0) { L.misc[0] = nheap; L.misc[1] = nodes; }
-    if constexpr (LM == 2) {
+    if constexpr (LM >= 2) {
         if (lane == 0) { L.misc[4] += n_expanded; L.misc[5] += n_lookups; }
     }
 }
@@ -535,7 +609,7 @@ beam_decode_kernel(const float *__restrict__ logits, const int *__restrict__ seq
         L.node[0] = 0; L.label[0] = -1; L.parent[0] = -1; L.alive[0] = 1;
         L.n_total[0] = 0.f; L.n_blank[0] = 0.f; L.n_label[0] = -INFINITY;
         if constexpr (LM != 0) { L.lm_state[0] = 0; L.lm_e[0] = 0.f; }
-        if constexpr (LM == 2) {
+        if constexpr (LM >= 2) {
             gstore(&lm.pool_ctx[0], 0); gstore(&lm.pool_sp_ctx[0], -1);
             L.misc[4] = 0; L.misc[5] = 0;
         }
@@ -641,12 +715,17 @@ beam_decode_kernel(const float *__restrict__ logits, const int *__restrict__ seq
     }
 
     // ---- best leaf and its label path --------------------------------------------------------------
-    if constexpr (LM == 2) {
+    if constexpr (LM >= 2) {
         // the end scores of the (at most W) final leaves, one wave per leaf, all waves at work
         const int nheap = L.misc[0];
         for (int i = tid >> 6; i < nheap; i += BEAM_THREADS / 64) {
             const int s = L.heap[i];
-            const float e = wordlm_end(lm, L.lm_state[s], gload(&lm.pool_ctx[L.node[s]]), lane);
+            float e;
+            if constexpr (LM == 3)
+                e = wordlm_end_la(lm, min(max(L.lm_state[s], 0), lm.nodes - 1),
+                                  gload(&lm.pool_ctx[L.node[s]]), lane);
+            else
+                e = wordlm_end(lm, L.lm_state[s], gload(&lm.pool_ctx[L.node[s]]), lane);
             if (lane == 0) L.n_total[s] += e;
         }
         if (lm.stats && tid == 0) {
@@ -758,7 +837,7 @@ int beam_launch(const float *logits, const int32_t *seq_len, int T, int B, int C
                 int beam_width, int norm_mode, const BeamLm *lm, int top_paths, int32_t *out,
                 int32_t *out_len, float *logp, int32_t *n_paths, void *workspace,
                 size_t workspace_bytes, ctcasr_stream_t stream,
-                const BeamWordLm *word = nullptr) {
+                const BeamWordLm *word = nullptr, const double *lookahead = nullptr) {
     const bool nbest = top_paths != 0 || n_paths;
     if (nbest && (!logp || !n_paths || top_paths < 1 || top_paths > beam_width))
         return CTCASR_ERR_BAD_ARGUMENT;
@@ -792,7 +871,12 @@ int beam_launch(const float *logits, const int32_t *seq_len, int T, int B, int C
             pool_parent, pool_label, pool_slot, pool_children, (int)n, MODEL, top_paths,        \
             n_paths);                                                                           \
     } while (0)
-    if (word) BEAM_LAUNCH(2, true, wlm);
+    if (word && lookahead) {
+        BeamWordLmLa wla;
+        static_cast<BeamWordLm &>(wla) = wlm;
+        wla.la = lookahead;
+        BEAM_LAUNCH(3, true, wla);
+    } else if (word) BEAM_LAUNCH(2, true, wlm);
     else if (lm && nbest) BEAM_LAUNCH(1, true, *lm);
     else if (lm) BEAM_LAUNCH(1, false, *lm);
     else if (nbest) BEAM_LAUNCH(0, true, BeamLm{});
@@ -877,6 +961,13 @@ bool wordlm_tables(const ctcasr_wordlm_t *lm, BeamWordLm *m) {
     return true;
 }
 
+// what the search needs of the tables beyond what a lookup needs
+bool wordlm_search_arguments(const BeamWordLm &m, int C, int blank) {
+    return m.trie_next && m.trie_word && m.nodes >= 2 && m.space >= 0 && m.space < C &&
+           m.space != blank && m.bonus == m.bonus && m.bonus - m.bonus == 0.0 && m.oov == m.oov &&
+           m.oov != INFINITY;
+}
+
 // one wave per pair, the device function of the search
 __global__ void __launch_bounds__(BEAM_THREADS)
 wordlm_lookup_kernel(BeamWordLm m, const int *__restrict__ ctx, const int *__restrict__ word, int n,
@@ -909,12 +1000,24 @@ extern "C" int ctcasr_ctc_beam_decode_wordlm(const float *logits, const int32_t 
                                              ctcasr_stream_t stream) {
     BeamWordLm m;
     if (top_paths < 1 || !n_paths || !wordlm_tables(lm, &m)) return CTCASR_ERR_BAD_ARGUMENT;
-    if (!m.trie_next || !m.trie_word || m.nodes < 2 || m.space < 0 || m.space >= C ||
-        m.space == blank || !(m.bonus == m.bonus) || m.bonus - m.bonus != 0.0 ||
-        !(m.oov == m.oov) || m.oov == INFINITY)
-        return CTCASR_ERR_BAD_ARGUMENT;
+    if (!wordlm_search_arguments(m, C, blank)) return CTCASR_ERR_BAD_ARGUMENT;
     return beam_launch(logits, seq_len, T, B, C, blank, beam_width, norm_mode, nullptr, top_paths,
                        out, out_len, logp, n_paths, workspace, workspace_bytes, stream, &m);
+}
+
+// K26: the same search with look-ahead scores inside a word; the table only steers pruning
+extern "C" int ctcasr_ctc_beam_decode_wordlm_lookahead(
+    const float *logits, const int32_t *seq_len, int T, int B, int C, int blank, int beam_width,
+    int norm_mode, int top_paths, const ctcasr_wordlm_t *lm, const double *trie_lookahead,
+    int32_t *out, int32_t *out_len, float *logp, int32_t *n_paths, void *workspace,
+    size_t workspace_bytes, ctcasr_stream_t stream) {
+    BeamWordLm m;
+    if (top_paths < 1 || !n_paths || !trie_lookahead || !wordlm_tables(lm, &m))
+        return CTCASR_ERR_BAD_ARGUMENT;
+    if (!wordlm_search_arguments(m, C, blank)) return CTCASR_ERR_BAD_ARGUMENT;
+    return beam_launch(logits, seq_len, T, B, C, blank, beam_width, norm_mode, nullptr, top_paths,
+                       out, out_len, logp, n_paths, workspace, workspace_bytes, stream, &m,
+                       trie_lookahead);
 }
 
 extern "C" int ctcasr_wordlm_lookup(const ctcasr_wordlm_t *lm, const int32_t *ctx,

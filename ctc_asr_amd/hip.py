@@ -9,6 +9,7 @@ import ctypes
 import functools
 import os
 
+import numpy as np
 import torch
 
 _PKG_DIR = os.path.dirname(os.path.abspath(__file__))
@@ -74,6 +75,8 @@ SIGNATURES = {
     'ctcasr_ctc_beam_wordlm_workspace_bytes': (_c_sz, [_c_int] * 4),
     'ctcasr_ctc_beam_decode_wordlm': (_c_int, [_c_p, _c_p] + [_c_int] * 7 + [_c_p] * 6 +
                                       [_c_sz, _c_p]),
+    'ctcasr_ctc_beam_decode_wordlm_lookahead': (_c_int, [_c_p, _c_p] + [_c_int] * 7 + [_c_p] * 7 +
+                                                [_c_sz, _c_p]),
     'ctcasr_wordlm_lookup': (_c_int, [_c_p] * 3 + [_c_int] + [_c_p] * 3),
     'ctcasr_ctc_beam_nbest_workspace_bytes': (_c_sz, [_c_int] * 4),
     'ctcasr_ctc_beam_decode_nbest': (_c_int, [_c_p, _c_p] + [_c_int] * 7 + [_c_p] * 3 + [_c_int] +
@@ -560,7 +563,10 @@ def ctc_beam_decode_wordlm(logits, seq_len, beam_width, scorer, top_paths=1, bla
     `lm.WordLmScorer`, already scaled (`WordLmScorer.scaled`).  Returns (out i32[B, N, T], out_len
     i32[B, N], logp f32[B, N], n_paths i32[B]) in the order of `ctc_beam_decode_nbest`;
     ``top_paths`` 1 is the top-1 decode.  ``stats``: None or int64 [B, 2] on the device, which
-    receives the branches expanded and the word lookups performed per utterance."""
+    receives the branches expanded and the word lookups performed per utterance.  A scorer that
+    carries a look-ahead table (``scorer.lookahead``, from ``scaled(..., lookahead=True)``) is
+    searched with look-ahead scores inside a word (K26); a table of the wrong length or with a
+    non-finite entry is refused before anything is launched."""
     num_steps, batch, classes = _decode_shape('ctc_beam_decode_wordlm', logits, seq_len)
     if scorer.num_classes != classes:
         raise CtcAsrError('ctc_beam_decode_wordlm: the scorer has {} classes, the logits {}.'
@@ -570,6 +576,16 @@ def ctc_beam_decode_wordlm(logits, seq_len, beam_width, scorer, top_paths=1, bla
     dev = logits.device
     if stats is not None:
         _expect_numel('ctc_beam_decode_wordlm', 'stats', stats, 2 * batch)
+    lookahead = getattr(scorer, 'lookahead', None)
+    if lookahead is not None:
+        lookahead = np.asarray(lookahead)
+        if lookahead.shape != (scorer.num_nodes,):
+            raise CtcAsrError('ctc_beam_decode_wordlm: the look-ahead table has shape {}, the '
+                              'trie {} nodes.'.format(lookahead.shape, scorer.num_nodes))
+        if not np.isfinite(lookahead).all():
+            raise CtcAsrError('ctc_beam_decode_wordlm: the look-ahead table holds a non-finite '
+                              'entry.')
+        lookahead = scorer.lookahead_to(dev)
     tables, keep = _wordlm_struct(scorer, dev, stats)
     rows = max(top_paths, 0)
     out = torch.empty((batch, rows, num_steps), dtype=torch.int32, device=dev)
@@ -578,14 +594,19 @@ def ctc_beam_decode_wordlm(logits, seq_len, beam_width, scorer, top_paths=1, bla
     n_paths = torch.empty(batch, dtype=torch.int32, device=dev)
     workspace = _workspace(load().ctcasr_ctc_beam_wordlm_workspace_bytes(
         num_steps, batch, classes, int(beam_width)), dev)
-    _check(load().ctcasr_ctc_beam_decode_wordlm(
-        _dev(logits, name='logits'), _dev(seq_len, torch.int32, 'seq_len'), num_steps, batch,
-        classes, blank, int(beam_width), {'max': 0, 'log_softmax': 1}[normalization], top_paths,
-        ctypes.addressof(tables), _dev(out, torch.int32, 'out'),
-        _dev(out_len, torch.int32, 'out_len'), _dev(logp, name='logp'),
-        _dev(n_paths, torch.int32, 'n_paths'), _dev(workspace, torch.uint8, 'workspace'),
-        workspace.numel(), _stream()), 'ctc_beam_decode_wordlm')
-    del keep
+    head = (_dev(logits, name='logits'), _dev(seq_len, torch.int32, 'seq_len'), num_steps, batch,
+            classes, blank, int(beam_width), {'max': 0, 'log_softmax': 1}[normalization],
+            top_paths, ctypes.addressof(tables))
+    tail = (_dev(out, torch.int32, 'out'), _dev(out_len, torch.int32, 'out_len'),
+            _dev(logp, name='logp'), _dev(n_paths, torch.int32, 'n_paths'),
+            _dev(workspace, torch.uint8, 'workspace'), workspace.numel(), _stream())
+    if lookahead is None:
+        _check(load().ctcasr_ctc_beam_decode_wordlm(*(head + tail)), 'ctc_beam_decode_wordlm')
+    else:
+        _check(load().ctcasr_ctc_beam_decode_wordlm_lookahead(
+            *(head + (_dev(lookahead, torch.float64, 'trie_lookahead'),) + tail)),
+            'ctc_beam_decode_wordlm_lookahead')
+    del keep, lookahead
     if bool((n_paths < 0).any()):
         raise CtcAsrError('ctc_beam_decode_wordlm: prefix-tree pool exhausted')
     return out, out_len, logp, n_paths

@@ -199,7 +199,13 @@ class WordLmScorer:
 
     Word id 0 is ``<unk>``, 1 is ``</s>``.  ``bonus`` and ``oov_score`` (-inf: closed vocabulary)
     are what `scaled` sets.  Everything is validated before anything is uploaded: a violation is a
-    ``ValueError`` that names the array."""
+    ``ValueError`` that names the array.
+
+    ``lookahead`` is None, or the float64 [N] look-ahead table of the scaled arrays
+    (`lookahead_table`; ``scaled(..., lookahead=True)`` sets it): the scorer then scores by K26 -
+    entering a trie node charges the best score a word below it can still get, the space settles
+    the difference - in `step`, `end_score`, `sequence_scores` and on the device.  Complete
+    hypotheses are worth what they are worth without it; only pruning changes."""
 
     def __init__(self, trie_next, trie_word, ctx_begin, succ_word, succ_lp, succ_ctx, ctx_backoff,
                  ctx_parent, order, space, vocab=None, bonus=0.0, oov_score=-np.inf):
@@ -296,7 +302,9 @@ class WordLmScorer:
         if self.vocab is not None and len(self.vocab) != words - 2:
             raise ValueError('WordLmScorer: vocab holds {} words, the tables {}.'
                              .format(len(self.vocab), words - 2))
+        self.lookahead = None
         self._device = {}
+        self._device_lookahead = {}
 
     num_nodes = property(lambda self: self.trie_next.shape[0])
     num_classes = property(lambda self: self.trie_next.shape[1])
@@ -305,10 +313,11 @@ class WordLmScorer:
     num_words = property(lambda self: int(self.ctx_begin[1]))     # <unk> and </s> included
     oov = property(lambda self: np.isfinite(self.oov_score))
 
-    def scaled(self, weight=1.0, bonus=0.0, oov_score=-np.inf):
+    def scaled(self, weight=1.0, bonus=0.0, oov_score=-np.inf, lookahead=False):
         """The scorer the kernel takes: ``succ_lp`` and ``ctx_backoff`` times ``weight`` in
         float64 (-inf stays -inf at every weight, 0 included); ``bonus`` and ``oov_score`` are
-        kept as float64 - the device adds them in float64 and rounds each score once."""
+        kept as float64 - the device adds them in float64 and rounds each score once.
+        ``lookahead``: the scorer carries the `lookahead_table` of its scaled arrays (K26)."""
         weight = float(weight)
         if not np.isfinite(weight):
             raise ValueError('WordLmScorer.scaled: weight must be finite.')
@@ -317,9 +326,67 @@ class WordLmScorer:
             safe = np.where(np.isneginf(values), 0.0, values)
             return np.where(np.isneginf(values), -np.inf, weight * safe)
 
-        return WordLmScorer(self.trie_next, self.trie_word, self.ctx_begin, self.succ_word,
-                            scale(self.succ_lp), self.succ_ctx, scale(self.ctx_backoff),
-                            self.ctx_parent, self.order, self.space, self.vocab, bonus, oov_score)
+        scorer = WordLmScorer(self.trie_next, self.trie_word, self.ctx_begin, self.succ_word,
+                              scale(self.succ_lp), self.succ_ctx, scale(self.ctx_backoff),
+                              self.ctx_parent, self.order, self.space, self.vocab, bonus,
+                              oov_score)
+        if lookahead:
+            scorer.lookahead = scorer.lookahead_table()
+        return scorer
+
+    def _trie_levels(self):
+        """The nodes of the trie level by level from the root, as (parents, children) arrays per
+        level - after checking that ``trie_next`` is a tree rooted at node 0: every node >= 2 the
+        target of exactly one edge, nodes 0 and 1 of none, every node but the sink reached from
+        the root.  Anything else is a ``ValueError`` that names ``trie_next``."""
+        nodes = self.num_nodes
+        targets = self.trie_next[self.trie_next >= 0]
+        reached = np.bincount(targets, minlength=nodes)
+        if reached[0] or reached[1]:
+            raise ValueError('WordLmScorer: trie_next is no tree: an edge leads into node {}.'
+                             .format(0 if reached[0] else 1))
+        if (reached[2:] != 1).any():
+            node = 2 + int(np.flatnonzero(reached[2:] != 1)[0])
+            raise ValueError('WordLmScorer: trie_next is no tree: node {} is the target of {} '
+                             'edges.'.format(node, int(reached[node])))
+        levels, frontier, seen = [], np.zeros(1, dtype=np.int64), 1
+        while frontier.size:
+            rows = self.trie_next[frontier]
+            at = rows >= 0
+            parents = np.broadcast_to(frontier[:, None], rows.shape)[at]
+            children = rows[at].astype(np.int64)
+            if children.size:
+                levels.append((parents, children))
+            seen += children.size
+            frontier = children
+        if seen != nodes - 1:
+            raise ValueError('WordLmScorer: trie_next is no tree: {} nodes are not reached from '
+                             'the root.'.format(nodes - 1 - seen))
+        return levels
+
+    def lookahead_table(self):
+        """float64 [N], K26's table of these (scaled) arrays: for a node n >= 2 the best unigram
+        score ``succ_lp[w]`` (context 0 lists every word) of a word at or below n, -inf entries
+        not counting; with OOV on never below ``oov_score + succ_lp[0]``, which is the sink's
+        entry; 0.0 where nothing is finite, and 0.0 at the root.  ``trie_next`` must be a tree
+        (``ValueError``).  Level by level, no recursion."""
+        levels = self._trie_levels()
+        unigram = self.succ_lp[:self.num_words]
+        table = np.full(self.num_nodes, -np.inf)
+        closing = self.trie_word >= 0
+        table[closing] = unigram[self.trie_word[closing]]
+        table[:2] = -np.inf
+        for parents, children in reversed(levels):
+            np.maximum.at(table, parents, table[children])
+        unk = self.oov_score + float(unigram[UNK])
+        if self.oov and np.isfinite(unk):
+            table[2:] = np.maximum(table[2:], unk)
+            table[1] = unk
+        else:
+            table[1] = -np.inf
+        table[~np.isfinite(table)] = 0.0
+        table[0] = 0.0
+        return table
 
     def word_score(self, context, word):
         """(Wd(h, w) in float64, next context): the pinned back-off walk - search h's range for
@@ -336,7 +403,8 @@ class WordLmScorer:
         return -np.inf, 0
 
     def _close(self, node, context):
-        """(score of the word that ``node`` closes in ``context``, no bonus; next context)."""
+        """(score of the word that ``node`` closes in ``context``, no bonus; next context).  With
+        a look-ahead table the word's full cost: the sink's word carries ``oov_score`` too."""
         if node == 0:
             return -np.inf, 0
         word = -1 if node == 1 else int(self.trie_word[node])
@@ -345,24 +413,33 @@ class WordLmScorer:
         if not self.oov:
             return -np.inf, 0
         score, after = self.word_score(context, UNK)
-        return (score if node == 1 else score + self.oov_score), after
+        if node == 1 and self.lookahead is None:
+            return score, after
+        return score + self.oov_score, after
 
     def step(self, node, context, label):
         """((next node, next context), float32 score) of the edge ``label`` out of the state
         (node, context); a forbidden edge gives (None, -inf)."""
         forbidden = (None, np.float32(-np.inf))
+        la = self.lookahead
         if label != self.space:
             if node == 1:
                 return (1, context), np.float32(self.bonus)
             target = int(self.trie_next[node, label])
             if target >= 0:
+                if la is not None:
+                    return (target, context), np.float32((la[target] - la[node]) + self.bonus)
                 return (target, context), np.float32(self.bonus)
             if self.oov:
+                if la is not None:
+                    return (1, context), np.float32((la[1] - la[node]) + self.bonus)
                 return (1, context), np.float32(self.oov_score + self.bonus)
             return forbidden
         score, after = self._close(node, context)
         if np.isneginf(score):       # nothing closes here (or the tables forbid the word)
             return forbidden
+        if la is not None:
+            return (0, after), np.float32((score - la[node]) + self.bonus)
         return (0, after), np.float32(score + self.bonus)
 
     def end_score(self, node, context):
@@ -372,6 +449,8 @@ class WordLmScorer:
         score, after = self._close(node, context)
         if np.isneginf(score):
             return np.float32(-np.inf)
+        if self.lookahead is not None:
+            return np.float32((score - self.lookahead[node]) + self.word_score(after, EOS)[0])
         return np.float32(score + self.word_score(after, EOS)[0])
 
     def sequence_scores(self, rows):
@@ -409,10 +488,26 @@ class WordLmScorer:
                                          for name in WORD_ARRAYS)
         return self._device[device]
 
+    def lookahead_to(self, device):
+        """The look-ahead table on ``device`` (float64 [N]); uploaded once per device and
+        cached, like the arrays of `to`."""
+        import torch
+        if self.lookahead is None:
+            raise ValueError('WordLmScorer.lookahead_to: the scorer carries no look-ahead table.')
+        device = torch.device(device)
+        if device.type == 'cuda' and device.index is None:
+            device = torch.device('cuda', torch.cuda.current_device())
+        cached = self._device_lookahead.get(device)
+        if cached is None or cached[0] is not self.lookahead:
+            table = np.ascontiguousarray(self.lookahead, dtype=np.float64)
+            cached = (self.lookahead, torch.from_numpy(table).to(device))
+            self._device_lookahead[device] = cached
+        return cached[1]
+
     def save(self, path):
         """``.npz`` of the arrays plus ``kind``, ``order``, ``num_classes``, ``space`` and the
         vocabulary as flat label rows with offsets; no pickle.  Scaling is not stored: save the
-        model `build_word_ngram` returned."""
+        model `build_word_ngram` returned.  Nor is a look-ahead table: it is derived."""
         vocab = self.vocab or []
         arrays = {name: getattr(self, name) for name in WORD_ARRAYS}
         arrays.update(kind=np.array(WORD_KIND), order=np.int64(self.order),
@@ -546,7 +641,8 @@ def from_flags(num_classes):
     scorer = load(FLAGS.lm_path, num_classes)
     if isinstance(scorer, WordLmScorer):
         check_word_space('--lm_path', scorer)
-        return scorer.scaled(FLAGS.lm_weight, FLAGS.lm_bonus, FLAGS.lm_oov_score)
+        return scorer.scaled(FLAGS.lm_weight, FLAGS.lm_bonus, FLAGS.lm_oov_score,
+                             lookahead=FLAGS.lm_lookahead)
     return scorer.scaled(FLAGS.lm_weight, FLAGS.lm_bonus)
 
 
@@ -581,7 +677,8 @@ def check_file(flag, path, num_classes):
     """The parse-time check of ``--lm_path`` / ``--rescore_lm_path``: the file exists, is a model
     of either kind for ``num_classes`` classes and, if a word model, ends its words at the
     alphabet's space.  Reads the file's scalars only: the tables are validated when the model is
-    loaded for use.  Every refusal is a ``ValueError`` that names the flag."""
+    loaded for use.  Every refusal is a ``ValueError`` that names the flag.  Returns the file's
+    ``kind``."""
     import zipfile
     try:
         with np.load(path, allow_pickle=False) as data:
@@ -600,6 +697,7 @@ def check_file(flag, path, num_classes):
         if space is None:
             raise ValueError('{}: {}: the word model lacks the array space.'.format(flag, path))
         _check_space(flag, space)
+    return kind
 
 
 def build_char_ngram(label_rows, order, num_classes, blank=None):

@@ -521,6 +521,10 @@ FLAGS.define('string', 'lm_corpus_text', '', 'lm.py, word models: a plain text f
 FLAGS.define('float', 'lm_oov_score', float('-inf'), 'Word models: added once to a word outside '
              'the vocabulary, which then scores as <unk>; -inf (the default): closed vocabulary.',
              _oov_score('lm_oov_score'))
+FLAGS.define('bool', 'lm_lookahead', False, 'Word models: look-ahead scores inside a word - '
+             'entering a trie node charges the best unigram score of a word below it, the space '
+             'settles the difference.  Complete hypotheses keep their scores; a narrower beam '
+             'keeps the right word alive.  Needs --lm_path with a word model.')
 
 # N-best lists and second-pass rescoring (no counterpart in the reference): evaluate.py and
 # predict.py read the --nbest best hypotheses off the final beam, score each exactly
@@ -567,10 +571,15 @@ FLAGS.define_validator(_validate_nbest)
 def _validate_lm_path(flags):
     """--lm_path names a model to decode with, unless a corpus flag says that `ctc_asr_amd.lm` is
     about to write it."""
+    from ctc_asr_amd import lm
+    if flags.lm_lookahead and not flags.lm_path:
+        raise ValueError('--lm_lookahead needs --lm_path with a word model.')
     if not flags.lm_path or flags.lm_corpus_csv or flags.lm_corpus_text:
         return
-    from ctc_asr_amd import lm
-    lm.check_file('--lm_path', flags.lm_path, flags.num_classes)
+    kind = lm.check_file('--lm_path', flags.lm_path, flags.num_classes)
+    if flags.lm_lookahead and kind != lm.WORD_KIND:
+        raise ValueError('--lm_lookahead needs a word model: --lm_path {} holds a character '
+                         'model.'.format(flags.lm_path))
 
 
 FLAGS.define_validator(_validate_lm_path)

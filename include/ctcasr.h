@@ -321,8 +321,8 @@ int ctcasr_ctc_mwer(const float *logits, const int32_t *seq_len, int T, int B, i
  * ctcasr_wordlm_lookup: score[i] = fp32(Wd(ctx[i], word[i])) and next_ctx[i] for n pairs, by the
  * device function the search uses (trie_*, space, bonus, oov_score and stats are not read; ctx[i]
  * is clamped into [0, num_ctx)).  n == 0 returns CTCASR_OK and launches nothing.
- * Left out on purpose: look-ahead scores inside a word, hashed or quantised storage, orders
- * above 5, lattice output. */
+ * Left out on purpose: hashed or quantised storage, orders above 5, lattice output.  (Look-ahead
+ * scores inside a word: K26, below the declarations.) */
 typedef struct ctcasr_wordlm {
     const int32_t *trie_next;
     const int32_t *trie_word;
@@ -345,6 +345,57 @@ int ctcasr_ctc_beam_decode_wordlm(const float *logits, const int32_t *seq_len, i
                                   size_t workspace_bytes, ctcasr_stream_t stream);
 int ctcasr_wordlm_lookup(const ctcasr_wordlm_t *lm, const int32_t *ctx, const int32_t *word, int n,
                          float *score, int32_t *next_ctx, ctcasr_stream_t stream);
+
+/* ---- K26: look-ahead scores inside a word ------------------------------------------------------
+ * K24 pays a word's score when the hypothesis closes the word, so between two spaces the beam is
+ * pruned on acoustics alone.  With look-ahead ("smearing") entering a trie node charges the best
+ * score a word below that node can still get, and the space settles the difference.  (An added
+ * entry point, as K19 - K24: CTCASR_ABI_VERSION stays; ctcasr_wordlm_t keeps its layout.)
+ *
+ * One table joins K24's: trie_lookahead, double [num_nodes], `la` below.  Everything K24 pins
+ * stands - Wd, the contexts, the memo, the outputs; only the scores of the edges and of the end
+ * change.  PINNED (tests/word_lm_lookahead_reference.py restates it).  Each score is one fp64
+ * expression, in exactly the order written, rounded once to fp32.  The edge for label c out of
+ * (n, h):
+ *   c not the space:  n == 1                       -> (1, h)     bonus
+ *                     m = trie_next[n, c] >= 0     -> (m, h)     (la[m] - la[n]) + bonus
+ *                     no trie edge, OOV on         -> (1, h)     (la[1] - la[n]) + bonus
+ *                     no trie edge, OOV off        -> none       -inf
+ *   c the space, d what the word costs in full:
+ *                     n == 0                       -> none       -inf
+ *                     w = trie_word[n] >= 0        d = Wd(h, w)
+ *                     n == 1 (OOV on)              d = Wd(h, 0) + oov_score
+ *                     other n, OOV on              d = Wd(h, 0) + oov_score
+ *                     other n, OOV off             -> none       -inf
+ *                     otherwise                    -> (0, ctx')  (d - la[n]) + bonus
+ * The end of a hypothesis in (n, h): n == 0: Wd(h, 1); otherwise (d - la[n]) + Wd(ctx', 1), or -inf
+ * where nothing closes.  Note the sink: K24 charges oov_score on the edge into node 1 and Wd(h, 0)
+ * at its space; here the edge into the sink charges la[1] - la[n] and the space settles against
+ * the full Wd(h, 0) + oov_score.
+ * The sums telescope: along any label row the scores from a root state to the next root state, or
+ * to the end, add up to K24's (to rounding), for every table of finite values.  The table steers
+ * pruning and never what a complete hypothesis is worth, so any finite table is accepted; the
+ * caller answers for its entries being finite.  No index is derived from the table, and every
+ * index read from a table stays clamped.  (The project's table, lm.WordLmScorer.lookahead_table:
+ * la[n] = the best unigram score succ_lp[w], context 0, of a word at or below n - with OOV on
+ * never below oov_score + succ_lp[0], which is la[1] -, 0 where nothing is finite, and la[0] = 0:
+ * nothing is paid ahead at the root, so the state after a space is the start state.)
+ *
+ * ctcasr_ctc_beam_decode_wordlm_lookahead: the arguments, outputs, refusals and stats of
+ * ctcasr_ctc_beam_decode_wordlm; a NULL trie_lookahead: CTCASR_ERR_BAD_ARGUMENT.  The workspace is
+ * K24's, ctcasr_ctc_beam_wordlm_workspace_bytes; its contents on entry do not matter, and one that
+ * a launch of either entry point left behind serves the other (the memo of a tree node is
+ * initialised where the node is created).
+ * Left out on purpose: look-ahead from higher-order contexts (this is the unigram bound when the
+ * project's table is used), look-ahead for the dense automaton of ctcasr_ctc_beam_decode_lm. */
+int ctcasr_ctc_beam_decode_wordlm_lookahead(const float *logits, const int32_t *seq_len, int T,
+                                            int B, int C, int blank, int beam_width,
+                                            int norm_mode, int top_paths,
+                                            const ctcasr_wordlm_t *lm,
+                                            const double *trie_lookahead, int32_t *out,
+                                            int32_t *out_len, float *logp, int32_t *n_paths,
+                                            void *workspace, size_t workspace_bytes,
+                                            ctcasr_stream_t stream);
 
 /* ---- K11: CTC forced alignment ----------------------------------------------------------------
  * The Viterbi (max-sum) form of K9's alpha recursion: the single best alignment of each

@@ -6,8 +6,12 @@ A synthetic language, nothing downloaded: 20 000 seeded pseudo-words, sentences 
 word n-grams of orders 2 and 3.  The logits spell sentences of that language (peaked, with noise)
 at the evaluation group's shape: T' = 500, 176 utterances, widths 64 and 1024.  Also printed: the
 word lookups actually performed per utterance against the branches expanded (the kernel's
-`stats`).  The models are cached as .npz under the directory given (building them is host work):
-python tools/word_lm_microbench.py [cache_dir [T B]]"""
+`stats`).  Then the search with look-ahead scores inside a word (K26) beside the plain word search
+at equal widths, 4 to 1024: the time per launch and the mean exact fused total of the returned
+hypothesis - `hip.ctc_score` of it plus the model's `sequence_scores` of it, the quantity the search
+maximises, comparable across both forms because the look-ahead sums telescope.  The models are
+cached as .npz under the directory given (building them is host work):
+python tools/word_lm_microbench.py [cache_dir [T B [build-only | lookahead-only]]]"""
 import os
 import sys
 import time
@@ -80,6 +84,44 @@ def timed(fn, reps):
     return start.elapsed_time(stop) / reps
 
 
+def fused_total(logits, seq_len, out, out_len, scorer):
+    """Mean over the utterances of ctc_score(hypothesis) + sequence_scores(hypothesis), float64;
+    and how many hypotheses the exact scorer placed (status 0) with a finite model score."""
+    lengths = out_len[:, 0].cpu().numpy()
+    rows = [out[b, 0, :lengths[b]].cpu().tolist() for b in range(out.shape[0])]
+    labels = torch.as_tensor([c for row in rows for c in row] or [0], dtype=torch.int32,
+                             device='cuda')
+    offsets = torch.as_tensor(np.concatenate([[0], np.cumsum(lengths)]), dtype=torch.int32,
+                              device='cuda')
+    utt = torch.arange(len(rows), dtype=torch.int32, device='cuda')
+    score, status = hip.ctc_score(logits, seq_len, labels, offsets, utt)
+    total = score.double().cpu().numpy() + scorer.sequence_scores(rows)
+    good = (status.cpu().numpy() == 0) & np.isfinite(total)
+    return (float(total[good].mean()) if good.any() else float('nan')), int(good.sum())
+
+
+def lookahead_table(logits, seq_len, name, model):
+    """Per width, the plain word search and the look-ahead search: ms per launch, mean fused
+    total, hypotheses counted."""
+    plain = model.scaled(1.0, 0.0, -8.0)
+    start = time.time()
+    ahead = model.scaled(1.0, 0.0, -8.0, lookahead=True)
+    print('{}: look-ahead table of {} nodes in {:.2f} s'.format(name, model.num_nodes,
+                                                                time.time() - start))
+    print('  {:>5s} {:>11s} {:>13s} {:>6s} {:>11s} {:>13s} {:>6s}'.format(
+        'width', 'plain ms', 'plain total', 'n', 'ahead ms', 'ahead total', 'n'))
+    for width in (4, 16, 64, 256, 1024):
+        reps = 3 if width <= 64 else 1
+        line = '  {:5d}'.format(width)
+        for scorer in (plain, ahead):
+            ms = timed(lambda: hip.ctc_beam_decode_wordlm(logits, seq_len, width, scorer), reps)
+            out, out_len, _, _ = hip.ctc_beam_decode_wordlm(logits, seq_len, width, scorer)
+            # the total under the plain scorer: the same number for both forms, to rounding
+            total, count = fused_total(logits, seq_len, out, out_len, plain)
+            line += ' {:11.1f} {:13.4f} {:6d}'.format(ms, total, count)
+        print(line, flush=True)
+
+
 def main():
     cache = sys.argv[1] if len(sys.argv) >= 2 else ''
     T, B = (int(v) for v in sys.argv[2:4]) if len(sys.argv) >= 4 else (500, 176)
@@ -108,6 +150,9 @@ def main():
     logits = torch.as_tensor(spelled_logits(rng, rows, T, B)).cuda()
     seq_len = torch.full((B,), T, dtype=torch.int32, device='cuda')
     stats = torch.zeros((B, 2), dtype=torch.int64, device='cuda')
+    if len(sys.argv) >= 5 and sys.argv[4] == 'lookahead-only':
+        lookahead_table(logits, seq_len, *models[0])
+        return
     print('T={} B={}: ms per launch'.format(T, B))
     print('  {:>5s} {:>9s} {:>9s}'.format('width', 'plain', 'char 5') +
           ''.join(' {:>13s} {:>20s}'.format(name, 'lookups / branches') for name, _ in scaled))
@@ -132,6 +177,7 @@ def main():
         ms = timed(lambda: hip.wordlm_lookup(scorer, ctx, word), 3)
         print('wordlm_lookup, {}: {} pairs in {:.2f} ms ({:.1f} ns per pair)'.format(
             name, pairs, ms, ms * 1e6 / pairs))
+    lookahead_table(logits, seq_len, *models[0])
 
 
 if __name__ == '__main__':
