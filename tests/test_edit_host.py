@@ -61,6 +61,69 @@ def test_reference_takes_the_fewest_substitutions_among_the_shortest_alignments(
     assert ref.error_counts([], [5, 6]) == (2, 0, 2, 0)
 
 
+def _symbols(rng, alphabet, size):
+    if alphabet == 'wide':       # ids of 2^31 scale, both signs
+        pool = rng.integers(-2 ** 31, 2 ** 31, size=24)
+        return pool[rng.integers(0, len(pool), size=size)].tolist()
+    return rng.integers(0, alphabet, size=size).tolist()
+
+
+def test_fast_reference_equals_the_tuple_reference():
+    rng = np.random.default_rng(61)
+    lengths = [(0, 0), (0, 60), (60, 0), (1, 1), (60, 60)] + \
+        [tuple(rng.integers(0, 61, size=2).tolist()) for _ in range(75)]
+    for alphabet in (2, 3, 28, 'wide'):
+        for hyp_len, ref_len in lengths:
+            hyp, ref_seq = _symbols(rng, alphabet, hyp_len), _symbols(rng, alphabet, ref_len)
+            counts = ref.error_counts_fast(hyp, ref_seq)
+            assert counts == ref.error_counts(hyp, ref_seq), (alphabet, hyp, ref_seq)
+            assert all(type(v) is int for v in counts)
+    assert ref.error_counts_fast([1, 0], [0, 1]) == (2, 0, 1, 1)
+    # symbols of any comparable kind, as `error_counts` takes them
+    assert ref.error_counts_fast('a dog sat'.split(), 'the dog'.split()) == \
+        ref.error_counts('a dog sat'.split(), 'the dog'.split())
+
+
+def test_fast_reference_equals_brute_force_on_tiny_pairs():
+    for hyp_len, ref_len in itertools.product(range(5), repeat=2):
+        for hyp in itertools.product((0, 1), repeat=hyp_len):
+            for ref_seq in itertools.product((0, 1), repeat=ref_len):
+                assert ref.error_counts_fast(hyp, ref_seq) == ref.brute_force(hyp, ref_seq), \
+                    (hyp, ref_seq)
+    rng = np.random.default_rng(67)
+    for _ in range(60):
+        hyp = rng.integers(0, 3, size=int(rng.integers(0, 6))).tolist()
+        ref_seq = rng.integers(0, 3, size=int(rng.integers(0, 6))).tolist()
+        assert ref.error_counts_fast(hyp, ref_seq) == ref.brute_force(hyp, ref_seq), (hyp, ref_seq)
+
+
+@pytest.mark.parametrize('ref_len,subs,dels,ins', [
+    (1, 0, 0, 0), (1, 1, 0, 0), (1, 0, 1, 0), (1, 0, 0, 1), (7, 1, 1, 1),   # densest: 3 apart
+    (300, 100, 0, 0), (300, 0, 100, 0), (300, 0, 0, 100), (300, 34, 33, 33),
+    (2000, 0, 0, 0), (2000, 200, 0, 0), (2000, 0, 200, 0), (2000, 0, 0, 200),
+    (2000, 60, 60, 60), (2000, 1, 300, 2), (1999, 222, 222, 222)])
+def test_known_edits_are_what_the_fast_reference_finds(ref_len, subs, dels, ins):
+    rng = np.random.default_rng(ref_len + 3 * subs + 5 * dels + 7 * ins)
+    hyp, ref_seq, counts = ref.known_edits(rng, ref_len, subs, dels, ins)
+    assert counts == (subs + dels + ins, subs, dels, ins)
+    assert len(ref_seq) == ref_len == len(set(ref_seq)) and len(hyp) == ref_len - dels + ins
+    assert min(ref_seq) < 0 < max(ref_seq) or ref_len < 8
+    assert all(-2 ** 31 <= v < 2 ** 31 for v in hyp + ref_seq)
+    assert len(set(hyp) - set(ref_seq)) == subs + ins
+    # every edit is at least two untouched symbols away from the next
+    kept = set(ref_seq) & set(hyp)
+    touched = [i for i, v in enumerate(hyp) if v not in kept]
+    assert all(b - a >= 3 for a, b in zip(touched, touched[1:]))
+    assert ref.error_counts_fast(hyp, ref_seq) == counts
+    if ref_len <= 300:
+        assert ref.error_counts(hyp, ref_seq) == counts
+
+
+def test_known_edits_refuses_more_edits_than_fit():
+    with pytest.raises(AssertionError, match='no room'):
+        ref.known_edits(np.random.default_rng(0), 6, 1, 1, 1)
+
+
 def test_word_ids_split_as_wer_does():
     originals = ['the cat  sat', b'caf\xc3\xa9 au lait', '', ' a\tb\nc ']
     results = [b'the cat sat on', 'cafe au  lait', 'x', 'a b']

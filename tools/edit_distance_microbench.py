@@ -3,8 +3,9 @@
 `metrics.error_counts` path (packing, upload, launch, download) and the host functions it
 replaces, on one evaluation group - 176 utterances of 10 s in 11 batches of 16, label pairs plus
 word pairs, decodes with about 10 % label edits - and on a few length mixes.  The width-64 beam
-search launch over the same group is timed beside them.  Prints one JSON line per case; nothing
-is gated on the numbers."""
+search launch over the same group is timed beside them.  ``--plans`` times one long pair per
+LDS layout of the kernel instead.  Prints one JSON line per case; nothing is gated on the
+numbers."""
 import json
 import os
 import sys
@@ -172,7 +173,35 @@ def length_mixes():
         print(json.dumps(line))
 
 
+def plans():
+    """``--plans``: one long pair per layout of ``ed_plan`` (the pairs of
+    tests/test_gpu_edit_distance_plans.py by size), kernel time and the time per step of the
+    pair's wave - a pair is one chain of strips x (ref_len + width - 1) dependent steps."""
+    rng = np.random.default_rng(2)
+    cases = (
+        ('4790 x 4800, 4 waves, carry in LDS', [4790], [4800]),
+        ('4801 x 4801, 4 waves, carry in the workspace', [4801], [4801]),
+        ('9601 x 9601, 2 waves, workspace', [9601], [9601]),
+        ('19201 x 19201, 1 wave, workspace', [19201], [19201]),
+        ('two rows of 32767 x 32767, 1 wave, workspace', [32767] * 2, [32767] * 2),
+        ('32767 x 70, 512 strips, carry in LDS', [32767], [70]),
+        ('70 x 32767, 1 wave, workspace', [70], [32767]),
+    )
+    for name, hyp_lens, ref_lens in cases:
+        hyps = [rng.integers(1, 28, size=n).tolist() for n in hyp_lens]
+        refs = [rng.integers(1, 28, size=n).tolist() for n in ref_lens]
+        launch, _ = kernel_only(hyps, refs)
+        kernel_ms = events_ms(launch, iters=3, warmup=1)
+        steps = sum(ref_lens[0] + min(64, hyp_lens[0] - base) - 1
+                    for base in range(0, hyp_lens[0], 64))
+        print(json.dumps({'case': name, 'pairs': len(hyps), 'steps_per_pair': steps,
+                          'kernel_ms': round(kernel_ms, 3),
+                          'ns_per_step': round(kernel_ms * 1e6 / steps, 1)}), flush=True)
+
+
 def main():
+    if '--plans' in sys.argv[1:]:
+        return plans()
     assert len(ALPHABET) == 27
     cfg = ModelConfig(used_model='ds2', conv_filters=(4, 4), rnn_cell='lstm', cudnn=True,
                       num_units_dense=32, num_layers_rnn=1, num_units_rnn=64,
