@@ -831,110 +831,6 @@ size_t wordlm_workspace_bytes(int T, int B, int C, int beam_width) {
     return (size_t)B * nodes_per_utt(T, beam_width, C) * (6 + (size_t)C) * sizeof(int) + 256;
 }
 
-// arguments, limits, workspace layout and launch of all entry points (lm: NULL without a model;
-// top_paths 0: the top-1 entry points, whose `logp` may be NULL and which have no `n_paths`)
-int beam_launch(const float *logits, const int32_t *seq_len, int T, int B, int C, int blank,
-                int beam_width, int norm_mode, const BeamLm *lm, int top_paths, int32_t *out,
-                int32_t *out_len, float *logp, int32_t *n_paths, void *workspace,
-                size_t workspace_bytes, ctcasr_stream_t stream,
-                const BeamWordLm *word = nullptr, const double *lookahead = nullptr) {
-    const bool nbest = top_paths != 0 || n_paths;
-    if (nbest && (!logp || !n_paths || top_paths < 1 || top_paths > beam_width))
-        return CTCASR_ERR_BAD_ARGUMENT;
-    if (!logits || !seq_len || !out || !out_len || T <= 0 || B <= 0 || C <= 1 || blank < 0 ||
-        blank >= C || beam_width <= 0 || norm_mode < 0 || norm_mode > 1)
-        return CTCASR_ERR_BAD_ARGUMENT;
-    if (lm && (!lm->next || !lm->score || lm->states < 1)) return CTCASR_ERR_BAD_ARGUMENT;
-    if (beam_width > BEAM_MAX_WIDTH || C > BEAM_MAX_CLASSES) return CTCASR_ERR_UNSUPPORTED;
-    if (!workspace || workspace_bytes < (word ? wordlm_workspace_bytes(T, B, C, beam_width)
-                                              : ctcasr_ctc_beam_workspace_bytes(T, B, C, beam_width)))
-        return CTCASR_ERR_WORKSPACE;
-    const size_t n = nodes_per_utt(T, beam_width, C);
-    int *pool_parent = reinterpret_cast<int *>(workspace);
-    int *pool_label = pool_parent + (size_t)B * n;
-    int *pool_slot = pool_label + (size_t)B * n;
-    int *pool_children = pool_slot + (size_t)B * n;
-    const size_t lds = lm || word ? sizeof(BeamLdsLm) : sizeof(BeamLds);
-    // the word model's three pools trail the plain search's four
-    BeamWordLm wlm = word ? *word : BeamWordLm{};
-    wlm.pool_ctx = pool_children + (size_t)B * n * C;
-    wlm.pool_sp_ctx = wlm.pool_ctx + (size_t)B * n;
-    wlm.pool_sp_score = wlm.pool_sp_ctx + (size_t)B * n;
-#define BEAM_LAUNCH(LM, NBEST, MODEL)                                                                \
-    do {                                                                                        \
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(&beam_decode_kernel<LM, NBEST>), \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=        \
-            hipSuccess)                                                                         \
-            return CTCASR_ERR_LAUNCH;                                                           \
-        beam_decode_kernel<LM, NBEST><<<B, BEAM_THREADS, lds, (hipStream_t)stream>>>(           \
-            logits, seq_len, T, B, C, blank, beam_width, norm_mode, out, out_len, logp,         \
-            pool_parent, pool_label, pool_slot, pool_children, (int)n, MODEL, top_paths,        \
-            n_paths);                                                                           \
-    } while (0)
-    if (word && lookahead) {
-        BeamWordLmLa wla;
-        static_cast<BeamWordLm &>(wla) = wlm;
-        wla.la = lookahead;
-        BEAM_LAUNCH(3, true, wla);
-    } else if (word) BEAM_LAUNCH(2, true, wlm);
-    else if (lm && nbest) BEAM_LAUNCH(1, true, *lm);
-    else if (lm) BEAM_LAUNCH(1, false, *lm);
-    else if (nbest) BEAM_LAUNCH(0, true, BeamLm{});
-    else BEAM_LAUNCH(0, false, BeamLm{});
-#undef BEAM_LAUNCH
-    return ctcasr_launch_status();
-}
-
-}  // namespace
-
-extern "C" int ctcasr_ctc_beam_decode(const float *logits, const int32_t *seq_len, int T, int B,
-                                      int C, int blank, int beam_width, int norm_mode,
-                                      int32_t *out, int32_t *out_len, float *logp, void *workspace,
-                                      size_t workspace_bytes, ctcasr_stream_t stream) {
-    return beam_launch(logits, seq_len, T, B, C, blank, beam_width, norm_mode, nullptr, 0, out,
-                       out_len, logp, nullptr, workspace, workspace_bytes, stream);
-}
-
-// A leaf's state and edge score are constants of its tree node, and the branch's rows give them
-// again whenever the node re-enters the beam: the prefix tree itself carries nothing of the model,
-// and the fused search needs the plain search's pool.
-extern "C" size_t ctcasr_ctc_beam_lm_workspace_bytes(int T, int B, int C, int beam_width) {
-    return ctcasr_ctc_beam_workspace_bytes(T, B, C, beam_width);
-}
-
-extern "C" int ctcasr_ctc_beam_decode_lm(const float *logits, const int32_t *seq_len, int T, int B,
-                                         int C, int blank, int beam_width, int norm_mode,
-                                         const int32_t *lm_next, const float *lm_score,
-                                         const float *lm_final, int lm_states, int32_t *out,
-                                         int32_t *out_len, float *logp, void *workspace,
-                                         size_t workspace_bytes, ctcasr_stream_t stream) {
-    const BeamLm lm = {lm_next, lm_score, lm_final, lm_states};
-    return beam_launch(logits, seq_len, T, B, C, blank, beam_width, norm_mode, &lm, 0, out,
-                       out_len, logp, nullptr, workspace, workspace_bytes, stream);
-}
-
-// The n-best list is read off the final beam: the search and its prefix tree are the plain ones.
-extern "C" size_t ctcasr_ctc_beam_nbest_workspace_bytes(int T, int B, int C, int beam_width) {
-    return ctcasr_ctc_beam_workspace_bytes(T, B, C, beam_width);
-}
-
-extern "C" int ctcasr_ctc_beam_decode_nbest(const float *logits, const int32_t *seq_len, int T,
-                                            int B, int C, int blank, int beam_width, int norm_mode,
-                                            int top_paths, const int32_t *lm_next,
-                                            const float *lm_score, const float *lm_final,
-                                            int lm_states, int32_t *out, int32_t *out_len,
-                                            float *logp, int32_t *n_paths, void *workspace,
-                                            size_t workspace_bytes, ctcasr_stream_t stream) {
-    if (top_paths < 1 || !n_paths) return CTCASR_ERR_BAD_ARGUMENT;
-    const BeamLm lm = {lm_next, lm_score, lm_final, lm_states};
-    return beam_launch(logits, seq_len, T, B, C, blank, beam_width, norm_mode,
-                       lm_next ? &lm : nullptr, top_paths, out, out_len, logp, n_paths, workspace,
-                       workspace_bytes, stream);
-}
-
-// ---- K24: word n-gram over a lexicon trie, fused into the search ----------------------------------
-namespace {
-
 // the caller's tables as the kernels take them; false: an argument error
 bool wordlm_tables(const ctcasr_wordlm_t *lm, BeamWordLm *m) {
     if (!lm || !lm->succ_word || !lm->succ_lp || !lm->succ_ctx || !lm->ctx_begin ||
@@ -968,6 +864,120 @@ bool wordlm_search_arguments(const BeamWordLm &m, int C, int blank) {
            m.oov != INFINITY;
 }
 
+// The model of one search as its entry point was given it: which kind it is, and that kind's
+// tables, unchecked.
+struct BeamModel {
+    enum Kind { NONE, DENSE, WORD, WORD_LOOKAHEAD } kind;
+    BeamLm dense;                   // DENSE
+    const ctcasr_wordlm_t *word;    // WORD, WORD_LOOKAHEAD
+    const double *lookahead;        // WORD_LOOKAHEAD: [nodes]
+};
+
+// arguments, limits, workspace layout and launch of all entry points (nbest false: the top-1
+// entry points, whose `logp` may be NULL and which have neither `top_paths` nor `n_paths`)
+int beam_launch(const float *logits, const int32_t *seq_len, int T, int B, int C, int blank,
+                int beam_width, int norm_mode, const BeamModel &model, bool nbest, int top_paths,
+                int32_t *out, int32_t *out_len, float *logp, int32_t *n_paths, void *workspace,
+                size_t workspace_bytes, ctcasr_stream_t stream) {
+    const bool dense = model.kind == BeamModel::DENSE;
+    const bool word = model.kind == BeamModel::WORD || model.kind == BeamModel::WORD_LOOKAHEAD;
+    if (nbest && (!logp || !n_paths || top_paths < 1 || top_paths > beam_width))
+        return CTCASR_ERR_BAD_ARGUMENT;
+    BeamWordLmLa wlm = {};
+    if (word && (!wordlm_tables(model.word, &wlm) || !wordlm_search_arguments(wlm, C, blank)))
+        return CTCASR_ERR_BAD_ARGUMENT;
+    if (model.kind == BeamModel::WORD_LOOKAHEAD && !model.lookahead)
+        return CTCASR_ERR_BAD_ARGUMENT;
+    if (!logits || !seq_len || !out || !out_len || T <= 0 || B <= 0 || C <= 1 || blank < 0 ||
+        blank >= C || beam_width <= 0 || norm_mode < 0 || norm_mode > 1)
+        return CTCASR_ERR_BAD_ARGUMENT;
+    if (dense && (!model.dense.next || !model.dense.score || model.dense.states < 1))
+        return CTCASR_ERR_BAD_ARGUMENT;
+    if (beam_width > BEAM_MAX_WIDTH || C > BEAM_MAX_CLASSES) return CTCASR_ERR_UNSUPPORTED;
+    if (!workspace || workspace_bytes < (word ? wordlm_workspace_bytes(T, B, C, beam_width)
+                                              : ctcasr_ctc_beam_workspace_bytes(T, B, C, beam_width)))
+        return CTCASR_ERR_WORKSPACE;
+    const size_t n = nodes_per_utt(T, beam_width, C);
+    int *pool_parent = reinterpret_cast<int *>(workspace);
+    int *pool_label = pool_parent + (size_t)B * n;
+    int *pool_slot = pool_label + (size_t)B * n;
+    int *pool_children = pool_slot + (size_t)B * n;
+    const size_t lds = dense || word ? sizeof(BeamLdsLm) : sizeof(BeamLds);
+    // the word model's three pools trail the plain search's four
+    wlm.la = model.lookahead;
+    wlm.pool_ctx = pool_children + (size_t)B * n * C;
+    wlm.pool_sp_ctx = wlm.pool_ctx + (size_t)B * n;
+    wlm.pool_sp_score = wlm.pool_sp_ctx + (size_t)B * n;
+#define BEAM_LAUNCH(LM, NBEST, MODEL)                                                                \
+    do {                                                                                        \
+        if (hipFuncSetAttribute(reinterpret_cast<const void *>(&beam_decode_kernel<LM, NBEST>), \
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=        \
+            hipSuccess)                                                                         \
+            return CTCASR_ERR_LAUNCH;                                                           \
+        beam_decode_kernel<LM, NBEST><<<B, BEAM_THREADS, lds, (hipStream_t)stream>>>(           \
+            logits, seq_len, T, B, C, blank, beam_width, norm_mode, out, out_len, logp,         \
+            pool_parent, pool_label, pool_slot, pool_children, (int)n, MODEL, top_paths,        \
+            n_paths);                                                                           \
+    } while (0)
+    if (model.kind == BeamModel::WORD_LOOKAHEAD) BEAM_LAUNCH(3, true, wlm);
+    else if (word) BEAM_LAUNCH(2, true, static_cast<const BeamWordLm &>(wlm));
+    else if (dense && nbest) BEAM_LAUNCH(1, true, model.dense);
+    else if (dense) BEAM_LAUNCH(1, false, model.dense);
+    else if (nbest) BEAM_LAUNCH(0, true, BeamLm{});
+    else BEAM_LAUNCH(0, false, BeamLm{});
+#undef BEAM_LAUNCH
+    return ctcasr_launch_status();
+}
+
+}  // namespace
+
+extern "C" int ctcasr_ctc_beam_decode(const float *logits, const int32_t *seq_len, int T, int B,
+                                      int C, int blank, int beam_width, int norm_mode,
+                                      int32_t *out, int32_t *out_len, float *logp, void *workspace,
+                                      size_t workspace_bytes, ctcasr_stream_t stream) {
+    return beam_launch(logits, seq_len, T, B, C, blank, beam_width, norm_mode, BeamModel{}, false,
+                       0, out, out_len, logp, nullptr, workspace, workspace_bytes, stream);
+}
+
+// A leaf's state and edge score are constants of its tree node, and the branch's rows give them
+// again whenever the node re-enters the beam: the prefix tree itself carries nothing of the model,
+// and the fused search needs the plain search's pool.
+extern "C" size_t ctcasr_ctc_beam_lm_workspace_bytes(int T, int B, int C, int beam_width) {
+    return ctcasr_ctc_beam_workspace_bytes(T, B, C, beam_width);
+}
+
+extern "C" int ctcasr_ctc_beam_decode_lm(const float *logits, const int32_t *seq_len, int T, int B,
+                                         int C, int blank, int beam_width, int norm_mode,
+                                         const int32_t *lm_next, const float *lm_score,
+                                         const float *lm_final, int lm_states, int32_t *out,
+                                         int32_t *out_len, float *logp, void *workspace,
+                                         size_t workspace_bytes, ctcasr_stream_t stream) {
+    const BeamModel model = {BeamModel::DENSE, {lm_next, lm_score, lm_final, lm_states}};
+    return beam_launch(logits, seq_len, T, B, C, blank, beam_width, norm_mode, model, false, 0,
+                       out, out_len, logp, nullptr, workspace, workspace_bytes, stream);
+}
+
+// The n-best list is read off the final beam: the search and its prefix tree are the plain ones.
+extern "C" size_t ctcasr_ctc_beam_nbest_workspace_bytes(int T, int B, int C, int beam_width) {
+    return ctcasr_ctc_beam_workspace_bytes(T, B, C, beam_width);
+}
+
+extern "C" int ctcasr_ctc_beam_decode_nbest(const float *logits, const int32_t *seq_len, int T,
+                                            int B, int C, int blank, int beam_width, int norm_mode,
+                                            int top_paths, const int32_t *lm_next,
+                                            const float *lm_score, const float *lm_final,
+                                            int lm_states, int32_t *out, int32_t *out_len,
+                                            float *logp, int32_t *n_paths, void *workspace,
+                                            size_t workspace_bytes, ctcasr_stream_t stream) {
+    const BeamModel model = {lm_next ? BeamModel::DENSE : BeamModel::NONE,
+                             {lm_next, lm_score, lm_final, lm_states}};
+    return beam_launch(logits, seq_len, T, B, C, blank, beam_width, norm_mode, model, true,
+                       top_paths, out, out_len, logp, n_paths, workspace, workspace_bytes, stream);
+}
+
+// ---- K24: word n-gram over a lexicon trie, fused into the search ----------------------------------
+namespace {
+
 // one wave per pair, the device function of the search
 __global__ void __launch_bounds__(BEAM_THREADS)
 wordlm_lookup_kernel(BeamWordLm m, const int *__restrict__ ctx, const int *__restrict__ word, int n,
@@ -998,11 +1008,9 @@ extern "C" int ctcasr_ctc_beam_decode_wordlm(const float *logits, const int32_t 
                                              int32_t *out_len, float *logp, int32_t *n_paths,
                                              void *workspace, size_t workspace_bytes,
                                              ctcasr_stream_t stream) {
-    BeamWordLm m;
-    if (top_paths < 1 || !n_paths || !wordlm_tables(lm, &m)) return CTCASR_ERR_BAD_ARGUMENT;
-    if (!wordlm_search_arguments(m, C, blank)) return CTCASR_ERR_BAD_ARGUMENT;
-    return beam_launch(logits, seq_len, T, B, C, blank, beam_width, norm_mode, nullptr, top_paths,
-                       out, out_len, logp, n_paths, workspace, workspace_bytes, stream, &m);
+    const BeamModel model = {BeamModel::WORD, {}, lm};
+    return beam_launch(logits, seq_len, T, B, C, blank, beam_width, norm_mode, model, true,
+                       top_paths, out, out_len, logp, n_paths, workspace, workspace_bytes, stream);
 }
 
 // K26: the same search with look-ahead scores inside a word; the table only steers pruning
@@ -1011,13 +1019,9 @@ extern "C" int ctcasr_ctc_beam_decode_wordlm_lookahead(
     int norm_mode, int top_paths, const ctcasr_wordlm_t *lm, const double *trie_lookahead,
     int32_t *out, int32_t *out_len, float *logp, int32_t *n_paths, void *workspace,
     size_t workspace_bytes, ctcasr_stream_t stream) {
-    BeamWordLm m;
-    if (top_paths < 1 || !n_paths || !trie_lookahead || !wordlm_tables(lm, &m))
-        return CTCASR_ERR_BAD_ARGUMENT;
-    if (!wordlm_search_arguments(m, C, blank)) return CTCASR_ERR_BAD_ARGUMENT;
-    return beam_launch(logits, seq_len, T, B, C, blank, beam_width, norm_mode, nullptr, top_paths,
-                       out, out_len, logp, n_paths, workspace, workspace_bytes, stream, &m,
-                       trie_lookahead);
+    const BeamModel model = {BeamModel::WORD_LOOKAHEAD, {}, lm, trie_lookahead};
+    return beam_launch(logits, seq_len, T, B, C, blank, beam_width, norm_mode, model, true,
+                       top_paths, out, out_len, logp, n_paths, workspace, workspace_bytes, stream);
 }
 
 extern "C" int ctcasr_wordlm_lookup(const ctcasr_wordlm_t *lm, const int32_t *ctx,

@@ -426,105 +426,6 @@ def ctc_greedy_decode(logits, seq_len, blank=None, out=None, out_len=None):
     return out, out_len
 
 
-def ctc_beam_workspace_bytes(num_steps, batch, classes, beam_width):
-    return load().ctcasr_ctc_beam_workspace_bytes(num_steps, batch, classes, int(beam_width))
-
-
-@_on_tensor_device
-def ctc_beam_decode(logits, seq_len, beam_width, blank=None, normalization='max'):
-    num_steps, batch, classes = _decode_shape('ctc_beam_decode', logits, seq_len)
-    blank = classes - 1 if blank is None else blank
-    dev = logits.device
-    out = torch.empty((batch, num_steps), dtype=torch.int32, device=dev)
-    out_len = torch.empty(batch, dtype=torch.int32, device=dev)
-    logp = torch.empty(batch, dtype=torch.float32, device=dev)
-    workspace = _workspace(load().ctcasr_ctc_beam_workspace_bytes(num_steps, batch, classes,
-                                                                  int(beam_width)), dev)
-    _check(load().ctcasr_ctc_beam_decode(
-        _dev(logits, name='logits'), _dev(seq_len, torch.int32, 'seq_len'), num_steps, batch,
-        classes, blank, int(beam_width), {'max': 0, 'log_softmax': 1}[normalization],
-        _dev(out, torch.int32, 'out'), _dev(out_len, torch.int32, 'out_len'),
-        _dev(logp, name='logp'), _dev(workspace, torch.uint8, 'workspace'), workspace.numel(),
-        _stream()), 'ctc_beam_decode')
-    if bool((out_len < 0).any()):
-        raise CtcAsrError('ctc_beam_decode: prefix-tree pool exhausted')
-    return out, out_len, logp
-
-
-def ctc_beam_lm_workspace_bytes(num_steps, batch, classes, beam_width):
-    return load().ctcasr_ctc_beam_lm_workspace_bytes(num_steps, batch, classes, int(beam_width))
-
-
-@_on_tensor_device
-def ctc_beam_decode_lm(logits, seq_len, beam_width, scorer, blank=None, normalization='max'):
-    """`ctc_beam_decode` with a language model fused into the search: ``scorer`` is an
-    `lm.LmScorer`, already scaled (`LmScorer.scaled`).  ``logp`` includes the model's scores."""
-    num_steps, batch, classes = _decode_shape('ctc_beam_decode_lm', logits, seq_len)
-    if scorer.num_classes != classes:
-        raise CtcAsrError('ctc_beam_decode_lm: the scorer has {} classes, the logits {}.'
-                          .format(scorer.num_classes, classes))
-    blank = classes - 1 if blank is None else blank
-    dev = logits.device
-    lm_next, lm_score, lm_final = scorer.to(dev)
-    out = torch.empty((batch, num_steps), dtype=torch.int32, device=dev)
-    out_len = torch.empty(batch, dtype=torch.int32, device=dev)
-    logp = torch.empty(batch, dtype=torch.float32, device=dev)
-    workspace = _workspace(load().ctcasr_ctc_beam_lm_workspace_bytes(num_steps, batch, classes,
-                                                                     int(beam_width)), dev)
-    _check(load().ctcasr_ctc_beam_decode_lm(
-        _dev(logits, name='logits'), _dev(seq_len, torch.int32, 'seq_len'), num_steps, batch,
-        classes, blank, int(beam_width), {'max': 0, 'log_softmax': 1}[normalization],
-        _dev(lm_next, torch.int32, 'lm_next'), _dev(lm_score, name='lm_score'),
-        _dev(lm_final, name='lm_final'), scorer.num_states,
-        _dev(out, torch.int32, 'out'), _dev(out_len, torch.int32, 'out_len'),
-        _dev(logp, name='logp'), _dev(workspace, torch.uint8, 'workspace'), workspace.numel(),
-        _stream()), 'ctc_beam_decode_lm')
-    if bool((out_len < 0).any()):
-        raise CtcAsrError('ctc_beam_decode_lm: prefix-tree pool exhausted')
-    return out, out_len, logp
-
-
-def ctc_beam_nbest_workspace_bytes(num_steps, batch, classes, beam_width):
-    return load().ctcasr_ctc_beam_nbest_workspace_bytes(num_steps, batch, classes,
-                                                        int(beam_width))
-
-
-@_on_tensor_device
-def ctc_beam_decode_nbest(logits, seq_len, beam_width, top_paths, scorer=None, blank=None,
-                          normalization='max'):
-    """The ``top_paths`` best leaves of the final beam of `ctc_beam_decode` (``scorer`` None) or
-    `ctc_beam_decode_lm`.  Returns (out i32[B, N, T], out_len i32[B, N], logp f32[B, N], n_paths
-    i32[B]); rank 0 is what the top-1 search returns, ranks >= n_paths[b] are empty (out_len 0,
-    logp -inf)."""
-    num_steps, batch, classes = _decode_shape('ctc_beam_decode_nbest', logits, seq_len)
-    if scorer is not None and scorer.num_classes != classes:
-        raise CtcAsrError('ctc_beam_decode_nbest: the scorer has {} classes, the logits {}.'
-                          .format(scorer.num_classes, classes))
-    blank = classes - 1 if blank is None else blank
-    top_paths = int(top_paths)
-    dev = logits.device
-    lm_next, lm_score, lm_final = scorer.to(dev) if scorer is not None else (None, None, None)
-    rows = max(top_paths, 0)
-    out = torch.empty((batch, rows, num_steps), dtype=torch.int32, device=dev)
-    out_len = torch.empty((batch, rows), dtype=torch.int32, device=dev)
-    logp = torch.empty((batch, rows), dtype=torch.float32, device=dev)
-    n_paths = torch.empty(batch, dtype=torch.int32, device=dev)
-    workspace = _workspace(load().ctcasr_ctc_beam_nbest_workspace_bytes(
-        num_steps, batch, classes, int(beam_width)), dev)
-    _check(load().ctcasr_ctc_beam_decode_nbest(
-        _dev(logits, name='logits'), _dev(seq_len, torch.int32, 'seq_len'), num_steps, batch,
-        classes, blank, int(beam_width), {'max': 0, 'log_softmax': 1}[normalization], top_paths,
-        _dev(lm_next, torch.int32, 'lm_next'), _dev(lm_score, name='lm_score'),
-        _dev(lm_final, name='lm_final'), scorer.num_states if scorer is not None else 0,
-        _dev(out, torch.int32, 'out'), _dev(out_len, torch.int32, 'out_len'),
-        _dev(logp, name='logp'), _dev(n_paths, torch.int32, 'n_paths'),
-        _dev(workspace, torch.uint8, 'workspace'), workspace.numel(), _stream()),
-        'ctc_beam_decode_nbest')
-    if bool((n_paths < 0).any()):
-        raise CtcAsrError('ctc_beam_decode_nbest: prefix-tree pool exhausted')
-    return out, out_len, logp, n_paths
-
-
 class WordLm(ctypes.Structure):
     """``ctcasr_wordlm_t`` of include/ctcasr.h."""
     _fields_ = [(name, _c_p) for name in ('trie_next', 'trie_word', 'ctx_begin', 'succ_word',
@@ -551,65 +452,154 @@ def _wordlm_struct(scorer, device, stats=None):
                   **fields), tensors
 
 
-def ctc_beam_wordlm_workspace_bytes(num_steps, batch, classes, beam_width):
-    return load().ctcasr_ctc_beam_wordlm_workspace_bytes(num_steps, batch, classes,
-                                                         int(beam_width))
+def _is_word(scorer):
+    """Whether ``scorer`` is a word model (`lm.WordLmScorer`) and not a dense one
+    (`lm.LmScorer`): the scorer classes say what they are, and only this function asks."""
+    return scorer is not None and scorer.kind == 'word'
+
+
+def _beam_workspace_bytes(word, num_steps, batch, classes, beam_width):
+    # (a dense model and an n-best list need the plain search's pool: csrc/beam.hip)
+    sizer = load().ctcasr_ctc_beam_wordlm_workspace_bytes if word else \
+        load().ctcasr_ctc_beam_workspace_bytes
+    return sizer(num_steps, batch, classes, int(beam_width))
+
+
+def ctc_beam_search_workspace_bytes(num_steps, batch, classes, beam_width, scorer=None):
+    """The workspace of `ctc_beam_search` with the same ``scorer``, for any ``top_paths``."""
+    return _beam_workspace_bytes(_is_word(scorer), num_steps, batch, classes, beam_width)
+
+
+def _lookahead_on(what, scorer, device):
+    """A word scorer's look-ahead table on ``device``, or None if it carries none; a table of
+    the wrong length or with a non-finite entry is refused."""
+    lookahead = getattr(scorer, 'lookahead', None)
+    if lookahead is None:
+        return None
+    lookahead = np.asarray(lookahead)
+    if lookahead.shape != (scorer.num_nodes,):
+        raise CtcAsrError('{}: the look-ahead table has shape {}, the trie {} nodes.'
+                          .format(what, lookahead.shape, scorer.num_nodes))
+    if not np.isfinite(lookahead).all():
+        raise CtcAsrError('{}: the look-ahead table holds a non-finite entry.'.format(what))
+    return scorer.lookahead_to(device)
 
 
 @_on_tensor_device
+def _beam_search(what, logits, seq_len, beam_width, scorer, top_paths, blank, normalization,
+                 stats):
+    """`ctc_beam_search` under the name ``what``, which the errors carry."""
+    num_steps, batch, classes = _decode_shape(what, logits, seq_len)
+    if scorer is not None and scorer.num_classes != classes:
+        raise CtcAsrError('{}: the scorer has {} classes, the logits {}.'
+                          .format(what, scorer.num_classes, classes))
+    blank = classes - 1 if blank is None else blank
+    dev = logits.device
+    word = _is_word(scorer)
+    nbest = word or top_paths is not None       # (the word model has n-best kernels only)
+    ranks = 1 if top_paths is None else int(top_paths)
+    if stats is not None:
+        if not word:
+            raise CtcAsrError('{}: stats are counted with a word scorer only.'.format(what))
+        _expect_numel(what, 'stats', stats, 2 * batch)
+    # `keep`: the tables on the device, referenced until the call has returned
+    entry, model, keep = 'ctcasr_ctc_beam_decode', (), None
+    if word:
+        lookahead = _lookahead_on(what, scorer, dev)
+        tables, keep = _wordlm_struct(scorer, dev, stats)
+        entry, model = entry + '_wordlm', (ctypes.addressof(tables),)
+        if lookahead is not None:
+            entry, keep = entry + '_lookahead', (keep, lookahead)
+            model += (_dev(lookahead, torch.float64, 'trie_lookahead'),)
+    elif scorer is not None or nbest:
+        entry += '_nbest' if nbest else '_lm'
+        keep = scorer.to(dev) if scorer is not None else (None, None, None)
+    shape = (batch, max(ranks, 0)) if nbest else (batch,)
+    out = torch.empty(shape + (num_steps,), dtype=torch.int32, device=dev)
+    out_len = torch.empty(shape, dtype=torch.int32, device=dev)
+    logp = torch.empty(shape, dtype=torch.float32, device=dev)
+    n_paths = torch.empty(batch, dtype=torch.int32, device=dev) if nbest else None
+    workspace = _workspace(_beam_workspace_bytes(word, num_steps, batch, classes, beam_width), dev)
+    args = (_dev(logits, name='logits'), _dev(seq_len, torch.int32, 'seq_len'), num_steps, batch,
+            classes, blank, int(beam_width), {'max': 0, 'log_softmax': 1}[normalization])
+    if nbest:
+        args += (ranks,)
+    if not word and keep is not None:
+        model = (_dev(keep[0], torch.int32, 'lm_next'), _dev(keep[1], name='lm_score'),
+                 _dev(keep[2], name='lm_final'), scorer.num_states if scorer is not None else 0)
+    args += model + (_dev(out, torch.int32, 'out'), _dev(out_len, torch.int32, 'out_len'),
+                     _dev(logp, name='logp'))
+    if nbest:
+        args += (_dev(n_paths, torch.int32, 'n_paths'),)
+    args += (_dev(workspace, torch.uint8, 'workspace'), workspace.numel(), _stream())
+    _check(getattr(load(), entry)(*args),
+           what + '_lookahead' if entry.endswith('_lookahead') else what)
+    del keep
+    if bool(((n_paths if nbest else out_len) < 0).any()):
+        raise CtcAsrError('{}: prefix-tree pool exhausted'.format(what))
+    if not nbest:
+        return out, out_len, logp
+    if top_paths is None:                       # the word model's top-1: rank 0 of one
+        return out[:, 0], out_len[:, 0], logp[:, 0]
+    return out, out_len, logp, n_paths
+
+
+def ctc_beam_search(logits, seq_len, beam_width, scorer=None, top_paths=None, blank=None,
+                    normalization='max', stats=None):
+    """The CTC beam search of ``logits`` f32 [T, B, C] at ``beam_width``, in every form.
+
+    ``scorer``: None, or a scaled scorer of `lm` fused into the search - an `lm.LmScorer` (a
+    dense automaton) or an `lm.WordLmScorer` (a word n-gram over a lexicon trie, K24; one that
+    carries a look-ahead table, from ``scaled(..., lookahead=True)``, is searched with look-ahead
+    scores inside a word, K26).  ``logp`` includes the model's scores.
+
+    ``top_paths`` None: the best hypothesis, (out i32[B, T], out_len i32[B], logp f32[B]).  An
+    integer: the ``top_paths`` best leaves of the final beam, (out i32[B, N, T], out_len
+    i32[B, N], logp f32[B, N], n_paths i32[B]); rank 0 is what the top-1 form returns, ranks >=
+    n_paths[b] are empty (out_len 0, logp -inf).
+
+    ``stats`` (word scorer only): None or int64 [B, 2] on the device, which receives the
+    branches expanded and the word lookups performed per utterance.
+
+    Wrong shapes, a scorer of another class count, a ``stats`` of the wrong size and a look-ahead
+    table of the wrong length or with a non-finite entry are refused before anything is launched;
+    a ``top_paths`` outside [1, beam_width] is refused by the library."""
+    return _beam_search('ctc_beam_search', logits, seq_len, beam_width, scorer, top_paths, blank,
+                        normalization, stats)
+
+
+# The older names, one per model and output form: shims over `ctc_beam_search` and its sizer.
+def ctc_beam_workspace_bytes(num_steps, batch, classes, beam_width):
+    return _beam_workspace_bytes(False, num_steps, batch, classes, beam_width)
+
+
+ctc_beam_lm_workspace_bytes = ctc_beam_nbest_workspace_bytes = ctc_beam_workspace_bytes
+
+
+def ctc_beam_wordlm_workspace_bytes(num_steps, batch, classes, beam_width):
+    return _beam_workspace_bytes(True, num_steps, batch, classes, beam_width)
+
+
+def ctc_beam_decode(logits, seq_len, beam_width, blank=None, normalization='max'):
+    return _beam_search('ctc_beam_decode', logits, seq_len, beam_width, None, None, blank,
+                        normalization, None)
+
+
+def ctc_beam_decode_lm(logits, seq_len, beam_width, scorer, blank=None, normalization='max'):
+    return _beam_search('ctc_beam_decode_lm', logits, seq_len, beam_width, scorer, None, blank,
+                        normalization, None)
+
+
+def ctc_beam_decode_nbest(logits, seq_len, beam_width, top_paths, scorer=None, blank=None,
+                          normalization='max'):
+    return _beam_search('ctc_beam_decode_nbest', logits, seq_len, beam_width, scorer,
+                        int(top_paths), blank, normalization, None)
+
+
 def ctc_beam_decode_wordlm(logits, seq_len, beam_width, scorer, top_paths=1, blank=None,
                            normalization='max', stats=None):
-    """`ctc_beam_decode_nbest` with a word n-gram fused into the search: ``scorer`` is an
-    `lm.WordLmScorer`, already scaled (`WordLmScorer.scaled`).  Returns (out i32[B, N, T], out_len
-    i32[B, N], logp f32[B, N], n_paths i32[B]) in the order of `ctc_beam_decode_nbest`;
-    ``top_paths`` 1 is the top-1 decode.  ``stats``: None or int64 [B, 2] on the device, which
-    receives the branches expanded and the word lookups performed per utterance.  A scorer that
-    carries a look-ahead table (``scorer.lookahead``, from ``scaled(..., lookahead=True)``) is
-    searched with look-ahead scores inside a word (K26); a table of the wrong length or with a
-    non-finite entry is refused before anything is launched."""
-    num_steps, batch, classes = _decode_shape('ctc_beam_decode_wordlm', logits, seq_len)
-    if scorer.num_classes != classes:
-        raise CtcAsrError('ctc_beam_decode_wordlm: the scorer has {} classes, the logits {}.'
-                          .format(scorer.num_classes, classes))
-    blank = classes - 1 if blank is None else blank
-    top_paths = int(top_paths)
-    dev = logits.device
-    if stats is not None:
-        _expect_numel('ctc_beam_decode_wordlm', 'stats', stats, 2 * batch)
-    lookahead = getattr(scorer, 'lookahead', None)
-    if lookahead is not None:
-        lookahead = np.asarray(lookahead)
-        if lookahead.shape != (scorer.num_nodes,):
-            raise CtcAsrError('ctc_beam_decode_wordlm: the look-ahead table has shape {}, the '
-                              'trie {} nodes.'.format(lookahead.shape, scorer.num_nodes))
-        if not np.isfinite(lookahead).all():
-            raise CtcAsrError('ctc_beam_decode_wordlm: the look-ahead table holds a non-finite '
-                              'entry.')
-        lookahead = scorer.lookahead_to(dev)
-    tables, keep = _wordlm_struct(scorer, dev, stats)
-    rows = max(top_paths, 0)
-    out = torch.empty((batch, rows, num_steps), dtype=torch.int32, device=dev)
-    out_len = torch.empty((batch, rows), dtype=torch.int32, device=dev)
-    logp = torch.empty((batch, rows), dtype=torch.float32, device=dev)
-    n_paths = torch.empty(batch, dtype=torch.int32, device=dev)
-    workspace = _workspace(load().ctcasr_ctc_beam_wordlm_workspace_bytes(
-        num_steps, batch, classes, int(beam_width)), dev)
-    head = (_dev(logits, name='logits'), _dev(seq_len, torch.int32, 'seq_len'), num_steps, batch,
-            classes, blank, int(beam_width), {'max': 0, 'log_softmax': 1}[normalization],
-            top_paths, ctypes.addressof(tables))
-    tail = (_dev(out, torch.int32, 'out'), _dev(out_len, torch.int32, 'out_len'),
-            _dev(logp, name='logp'), _dev(n_paths, torch.int32, 'n_paths'),
-            _dev(workspace, torch.uint8, 'workspace'), workspace.numel(), _stream())
-    if lookahead is None:
-        _check(load().ctcasr_ctc_beam_decode_wordlm(*(head + tail)), 'ctc_beam_decode_wordlm')
-    else:
-        _check(load().ctcasr_ctc_beam_decode_wordlm_lookahead(
-            *(head + (_dev(lookahead, torch.float64, 'trie_lookahead'),) + tail)),
-            'ctc_beam_decode_wordlm_lookahead')
-    del keep, lookahead
-    if bool((n_paths < 0).any()):
-        raise CtcAsrError('ctc_beam_decode_wordlm: prefix-tree pool exhausted')
-    return out, out_len, logp, n_paths
+    return _beam_search('ctc_beam_decode_wordlm', logits, seq_len, beam_width, scorer,
+                        int(top_paths), blank, normalization, stats)
 
 
 @_on_tensor_device

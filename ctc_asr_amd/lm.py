@@ -39,6 +39,8 @@ class LmScorer:
     n-gram).  Raises ``ValueError`` for wrong shapes, a ``next`` entry outside [0, S), NaN or
     +inf - before anything is uploaded."""
 
+    kind = 'dense'      # what `hip.ctc_beam_search` launches for this scorer
+
     def __init__(self, next, score, final=None, order=None):
         next_, score = np.asarray(next), np.asarray(score)
         if next_.ndim != 2 or next_.shape[0] < 1 or next_.shape[1] < 2:
@@ -206,6 +208,8 @@ class WordLmScorer:
     entering a trie node charges the best score a word below it can still get, the space settles
     the difference - in `step`, `end_score`, `sequence_scores` and on the device.  Complete
     hypotheses are worth what they are worth without it; only pruning changes."""
+
+    kind = 'word'       # what `hip.ctc_beam_search` launches for this scorer
 
     def __init__(self, trie_next, trie_word, ctx_begin, succ_word, succ_lp, succ_ctx, ctx_backoff,
                  ctx_parent, order, space, vocab=None, bonus=0.0, oov_score=-np.inf):

@@ -21,7 +21,7 @@ import os
 import numpy as np
 import torch
 
-from ctc_asr_amd import hip, lm, metrics, split_gemm
+from ctc_asr_amd import hip, metrics, split_gemm
 from ctc_asr_amd.labels import num_classes
 from ctc_asr_amd.params import check_mwer_settings, ema_alpha_at
 
@@ -1282,8 +1282,8 @@ class CTCModel:
         num_steps, batch = int(logits.shape[0]), int(logits.shape[1])
         per_utt, grad, status = hip.ctc_loss_fwd_bwd(logits, flat, offsets, seq_length, max_len,
                                                      grad_scale=float(ctc_weight) / batch)
-        out, out_len, _, n_paths = hip.ctc_beam_decode_nbest(logits, seq_length, beam_width,
-                                                            nbest)
+        out, out_len, _, n_paths = hip.ctc_beam_search(logits, seq_length, beam_width,
+                                                       top_paths=nbest)
         dev = out.device
         # (a row of non-finite logits has no defined answer: keep what it claims inside the row)
         lengths = out_len.reshape(-1).clamp(0, num_steps)
@@ -2140,21 +2140,9 @@ class CTCModel:
         beam_width = self.cfg.beam_width if beam_width is None else beam_width
         if greedy:
             out, out_len = hip.ctc_greedy_decode(logits, seq_len)
-        elif scorer is not None:
-            out, out_len = self._fused_top1(logits, seq_len, beam_width, scorer)
         else:
-            out, out_len, _ = hip.ctc_beam_decode(logits, seq_len, beam_width)
+            out, out_len, _ = hip.ctc_beam_search(logits, seq_len, beam_width, scorer)
         return self._decoded_to_text(out.cpu().numpy(), out_len.cpu().numpy(), originals)
-
-    @staticmethod
-    def _fused_top1(logits, seq_len, beam_width, scorer):
-        """(out [B, T], out_len [B]) of the search with ``scorer`` fused in: a word model
-        (`lm.WordLmScorer`) through its own entry point, any other through the dense one."""
-        if isinstance(scorer, lm.WordLmScorer):
-            out, out_len, _, _ = hip.ctc_beam_decode_wordlm(logits, seq_len, beam_width, scorer)
-            return out[:, 0], out_len[:, 0]
-        out, out_len, _ = hip.ctc_beam_decode_lm(logits, seq_len, beam_width, scorer)
-        return out, out_len
 
     @staticmethod
     def _decoded_to_text(out, out_len, originals):
@@ -2178,10 +2166,8 @@ class CTCModel:
         256 CUs and a group of batches decodes in about the time of one.  Bounded by the prefix
         tree pool (256 MB per utterance at width 1024, T' = 500) and ``max_utterances``."""
         beam_width = self.cfg.beam_width if beam_width is None else beam_width
-        sizer = hip.ctc_beam_workspace_bytes if scorer is None else \
-            hip.ctc_beam_wordlm_workspace_bytes if isinstance(scorer, lm.WordLmScorer) else \
-            hip.ctc_beam_lm_workspace_bytes
-        per_utt = max(1, sizer(num_steps, 1, self.cfg.num_classes, beam_width))
+        per_utt = max(1, hip.ctc_beam_search_workspace_bytes(num_steps, 1, self.cfg.num_classes,
+                                                             beam_width, scorer))
         utterances = max(batch, min(max_utterances, budget_bytes // per_utt))
         return max(1, int(utterances // batch))
 
@@ -2194,28 +2180,28 @@ class CTCModel:
         beam_width = self.cfg.beam_width if beam_width is None else beam_width
         if not batches:
             return []
+        joint, lengths, rows = self._join_batches(batches)
+        out, out_len, _ = hip.ctc_beam_search(joint, lengths, beam_width, scorer)
+        out, out_len = out.cpu().numpy(), out_len.cpu().numpy()
+        return [self._decoded_to_text(out[part], out_len[part], originals)
+                for part, (_, _, originals) in zip(rows, batches)]
+
+    def _join_batches(self, batches):
+        """(joint logits [max T'_i, sum B_i, C], lengths [sum B_i], one slice of the joint batch
+        per entry) of a non-empty list of (logits, seq_len, originals): the batches side by
+        side, zeros beyond a batch's own frames."""
         steps = max(int(logits.shape[0]) for logits, _, _ in batches)
         total = sum(int(logits.shape[1]) for logits, _, _ in batches)
         classes = int(batches[0][0].shape[2])
         joint = torch.zeros((steps, total, classes), dtype=torch.float32, device=self.device)
         lengths = torch.empty(total, dtype=torch.int32, device=self.device)
-        start = 0
+        rows, start = [], 0
         for logits, seq_len, _ in batches:
-            stop = start + int(logits.shape[1])
-            joint[:logits.shape[0], start:stop] = logits
-            lengths[start:stop] = seq_len
-            start = stop
-        if scorer is not None:
-            out, out_len = self._fused_top1(joint, lengths, beam_width, scorer)
-        else:
-            out, out_len, _ = hip.ctc_beam_decode(joint, lengths, beam_width)
-        out, out_len = out.cpu().numpy(), out_len.cpu().numpy()
-        results, start = [], 0
-        for logits, _, originals in batches:
-            stop = start + int(logits.shape[1])
-            results.append(self._decoded_to_text(out[start:stop], out_len[start:stop], originals))
-            start = stop
-        return results
+            rows.append(slice(start, start + int(logits.shape[1])))
+            joint[:logits.shape[0], rows[-1]] = logits
+            lengths[rows[-1]] = seq_len
+            start = rows[-1].stop
+        return joint, lengths, rows
 
     # ------------------------------------------------------------------ n-best / rescoring
     @staticmethod
@@ -2255,12 +2241,8 @@ class CTCModel:
         from ctc_asr_amd.labels import decode
         beam_width = self.cfg.beam_width if beam_width is None else beam_width
         top_paths = int(top_paths)
-        if isinstance(scorer, lm.WordLmScorer):
-            out, out_len, logp, n_paths = hip.ctc_beam_decode_wordlm(logits, seq_len, beam_width,
-                                                                     scorer, top_paths)
-        else:
-            out, out_len, logp, n_paths = hip.ctc_beam_decode_nbest(logits, seq_len, beam_width,
-                                                                    top_paths, scorer=scorer)
+        out, out_len, logp, n_paths = hip.ctc_beam_search(logits, seq_len, beam_width, scorer,
+                                                          top_paths)
         num_steps, batch = int(logits.shape[0]), int(logits.shape[1])
         # every rank is a hypothesis of the scoring launch; the empty ranks beyond n_paths point
         # at no utterance (status 2: their waves leave at once)
@@ -2345,24 +2327,10 @@ class CTCModel:
         result per batch, identical to calling it batch by batch."""
         if not batches:
             return []
-        steps = max(int(logits.shape[0]) for logits, _, _ in batches)
-        total = sum(int(logits.shape[1]) for logits, _, _ in batches)
-        classes = int(batches[0][0].shape[2])
-        joint = torch.zeros((steps, total, classes), dtype=torch.float32, device=self.device)
-        lengths = torch.empty(total, dtype=torch.int32, device=self.device)
-        start = 0
-        for logits, seq_len, _ in batches:
-            stop = start + int(logits.shape[1])
-            joint[:logits.shape[0], start:stop] = logits
-            lengths[start:stop] = seq_len
-            start = stop
+        joint, lengths, rows = self._join_batches(batches)
         flat = self._nbest_launch(joint, lengths, top_paths, beam_width, scorer, rescorer)
-        results, start = [], 0
-        for logits, _, originals in batches:
-            stop = start + int(logits.shape[1])
-            results.append(self._with_originals(flat[start:stop], originals))
-            start = stop
-        return results
+        return [self._with_originals(flat[part], originals)
+                for part, (_, _, originals) in zip(rows, batches)]
 
     @staticmethod
     def error_rates_fn(labels, originals, decoded, decoded_texts):

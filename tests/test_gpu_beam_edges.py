@@ -25,6 +25,7 @@ import torch
 
 from oracle import cref
 from oracle import ctc as octc
+from tests.beam_helpers import _logits, _same_bits, _t
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda'
@@ -36,10 +37,6 @@ NODE_ID_CAP = 1 << 21                               # nodes_per_utt's ceiling (t
 # what whoever runs the module reads to report it (the asserts do not depend on it):
 # {group: largest |logp - reference|}, and the wall time of the pool-exhaustion launch
 MEASURED = {}
-
-
-def _t(a, dtype=torch.float32):
-    return torch.as_tensor(np.ascontiguousarray(a), dtype=dtype).to(DEV)
 
 
 def _run(hip, logits, seq_len, width, blank=None, norm='max'):
@@ -76,17 +73,6 @@ def _check(hip, logits, seq_len, width, blank, norm, group='parity'):
     assert np.allclose(logp, ref_logp, rtol=1e-5, atol=1e-2 if num_steps >= 500 else 1e-3), \
         (logp, ref_logp)
     return out, out_len, logp, ref_paths
-
-
-def _logits(rng, num_steps, batch, classes, blank, scale=2.0, blank_bias=1.0):
-    logits = rng.normal(size=(num_steps, batch, classes)) * scale
-    logits[:, :, blank] += blank_bias
-    return logits.astype(np.float32)
-
-
-def _same_bits(a, b):
-    return all(np.array_equal(np.ascontiguousarray(x).view(np.int32),
-                              np.ascontiguousarray(y).view(np.int32)) for x, y in zip(a, b))
 
 
 def _row_alone(hip, logits, seq_len, width, blank, norm, got, rows):

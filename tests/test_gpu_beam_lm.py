@@ -22,22 +22,13 @@ from ctc_asr_amd import lm
 from ctc_asr_amd.params import FLAGS
 from oracle import ctc as octc
 from tests import lm_beam_reference as ref
+from tests.beam_helpers import _logits, _random_scorer, _same_bits, _t, _tables, raw_beam
 from tests.test_lm_host import TRUTH_CASES, check_truth
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda'
 NORMS = ['max', 'log_softmax']
 MAX_WIDTH = 1024
-
-
-def _t(a, dtype=torch.float32):
-    return torch.as_tensor(np.ascontiguousarray(a), dtype=dtype).to(DEV)
-
-
-def _logits(rng, num_steps, batch, classes, blank, scale=2.0, blank_bias=1.0):
-    logits = rng.normal(size=(num_steps, batch, classes)) * scale
-    logits[:, :, blank] += blank_bias
-    return logits.astype(np.float32)
 
 
 def _run(hip, logits, seq_len, width, scorer, blank=None, norm='max'):
@@ -52,27 +43,10 @@ def _run_plain(hip, logits, seq_len, width, blank=None, norm='max'):
     return out.cpu().numpy(), out_len.cpu().numpy(), logp.cpu().numpy()
 
 
-def _same_bits(a, b):
-    return all(np.array_equal(np.ascontiguousarray(x).view(np.int32),
-                              np.ascontiguousarray(y).view(np.int32)) for x, y in zip(a, b))
-
-
 def _zero_scorer(classes, final=False):
     return lm.LmScorer(np.zeros((1, classes), dtype=np.int32),
                        np.zeros((1, classes), dtype=np.float32),
                        np.zeros(1, dtype=np.float32) if final else None)
-
-
-def _random_scorer(rng, states, classes, final=True, forbidden=0.0):
-    score = rng.normal(size=(states, classes)).astype(np.float32)
-    if forbidden:
-        score[rng.random(size=score.shape) < forbidden] = -np.inf
-    return lm.LmScorer(rng.integers(0, states, size=(states, classes)), score,
-                       rng.normal(size=states).astype(np.float32) if final else None)
-
-
-def _tables(scorer):
-    return scorer.next, scorer.score, scorer.final
 
 
 def _check(hip, logits, seq_len, width, scorer, blank, norm):
@@ -298,22 +272,6 @@ def test_a_row_in_a_batch_of_64_is_the_row_alone(hip):
             assert (out[b, out_len[b]:] == 0).all(), b
 
 
-def _raw(hip, logits, seq_len, width, scorer, workspace, blank=28):
-    """The C entry point on a workspace of the caller's."""
-    num_steps, batch, classes = logits.shape
-    nxt, score, final = scorer.to(torch.device(DEV, torch.cuda.current_device()))
-    out = torch.full((batch, num_steps), -7, dtype=torch.int32, device=DEV)
-    out_len = torch.full((batch,), -7, dtype=torch.int32, device=DEV)
-    logp = torch.full((batch,), float('nan'), dtype=torch.float32, device=DEV)
-    status = hip.load().ctcasr_ctc_beam_decode_lm(
-        logits.data_ptr(), seq_len.data_ptr(), num_steps, batch, classes, blank, width, 0,
-        nxt.data_ptr(), score.data_ptr(), None if final is None else final.data_ptr(),
-        scorer.num_states, out.data_ptr(), out_len.data_ptr(), logp.data_ptr(),
-        workspace.data_ptr(), workspace.numel(), torch.cuda.current_stream().cuda_stream)
-    torch.cuda.synchronize()
-    return status, (out.cpu().numpy(), out_len.cpu().numpy(), logp.cpu().numpy())
-
-
 def test_two_scorers_on_one_workspace_give_each_its_own_result(hip):
     """The prefix tree of one launch is stale data for the next: everything a launch reads of
     it, it has written first.  Scorer A, then B with other states and other forbidden edges on
@@ -328,7 +286,7 @@ def test_two_scorers_on_one_workspace_give_each_its_own_result(hip):
     lg, sl = _t(logits), _t(seq_len, torch.int32)
     results = []
     for scorer in (a, b, a):
-        status, got = _raw(hip, lg, sl, 32, scorer, workspace)
+        status, got = raw_beam(hip, lg, sl, 32, scorer, workspace)
         assert status == 0
         results.append(got)
         paths, logp = ref.beam_search_decode(logits, seq_len, 32, *_tables(scorer), blank=28)
@@ -338,7 +296,7 @@ def test_two_scorers_on_one_workspace_give_each_its_own_result(hip):
     assert _same_bits(results[0], results[2])
     assert not np.array_equal(results[0][2], results[1][2])
     # too small a workspace and bad scorer arguments are refused, nothing launched
-    status, _ = _raw(hip, lg, sl, 32, a, workspace[:need - 1])
+    status, _ = raw_beam(hip, lg, sl, 32, a, workspace[:need - 1])
     assert status == -3
     lib = hip.load()
     nxt, score, _ = a.to(torch.device(DEV, torch.cuda.current_device()))

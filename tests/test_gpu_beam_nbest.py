@@ -18,6 +18,7 @@ import torch
 from ctc_asr_amd import lm
 from oracle import ctc as octc
 from tests import nbest_reference as ref
+from tests.beam_helpers import _logits, _random_scorer, _same_bits, _t, _tables, raw_beam
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda'
@@ -25,39 +26,9 @@ NORMS = ['max', 'log_softmax']
 MAX_WIDTH = 1024
 
 
-def _t(a, dtype=torch.float32):
-    return torch.as_tensor(np.ascontiguousarray(a), dtype=dtype).to(DEV)
-
-
-def _logits(rng, num_steps, batch, classes, blank, scale=2.0, blank_bias=1.0):
-    logits = rng.normal(size=(num_steps, batch, classes)) * scale
-    logits[:, :, blank] += blank_bias
-    return logits.astype(np.float32)
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.int32)
-
-
-def _same_bits(a, b):
-    return all(np.array_equal(_bits(x), _bits(y)) for x, y in zip(a, b))
-
-
 def _close(a, b):
     """The existing logp bar: rtol 1e-5, atol 1e-3."""
     return bool(np.isclose(np.float64(a), np.float64(b), rtol=1e-5, atol=1e-3))
-
-
-def _random_scorer(rng, states, classes, final=True, forbidden=0.0):
-    score = rng.normal(size=(states, classes)).astype(np.float32)
-    if forbidden:
-        score[rng.random(size=score.shape) < forbidden] = -np.inf
-    return lm.LmScorer(rng.integers(0, states, size=(states, classes)), score,
-                       rng.normal(size=states).astype(np.float32) if final else None)
-
-
-def _tables(scorer):
-    return (None, None, None) if scorer is None else (scorer.next, scorer.score, scorer.final)
 
 
 def _nbest(hip, logits, seq_len, width, top_paths, scorer=None, blank=None, norm='max'):
@@ -119,38 +90,6 @@ def test_rank_0_is_the_top_1_search_bit_for_bit(hip, num_steps, fused, norm):
             assert n_paths[1] == 1 and out_len[1, 0] == 0      # seq_len 0: the root alone
 
 
-def _raw(hip, logits, seq_len, width, top_paths, scorer, workspace, blank=28, norm=0,
-         nbytes=None):
-    """The C entry points on a workspace of the caller's, outputs pre-filled with garbage;
-    ``top_paths`` None: the top-1 entry point."""
-    num_steps, batch, classes = logits.shape
-    nxt, score, final = (None, None, None) if scorer is None else \
-        scorer.to(torch.device(DEV, torch.cuda.current_device()))
-    ptr = lambda t: None if t is None else t.data_ptr()                          # noqa: E731
-    rows = (batch,) if top_paths is None else (batch, max(top_paths, 1))
-    out = torch.full(rows + (num_steps,), -7, dtype=torch.int32, device=DEV)
-    out_len = torch.full(rows, -7, dtype=torch.int32, device=DEV)
-    logp = torch.full(rows, float('nan'), dtype=torch.float32, device=DEV)
-    n_paths = torch.full((batch,), -7, dtype=torch.int32, device=DEV)
-    nbytes = workspace.numel() if nbytes is None else nbytes
-    lib, stream = hip.load(), torch.cuda.current_stream().cuda_stream
-    head = (logits.data_ptr(), seq_len.data_ptr(), num_steps, batch, classes, blank, width, norm)
-    model = (ptr(nxt), ptr(score), ptr(final), 0 if scorer is None else scorer.num_states)
-    tail = (workspace.data_ptr(), nbytes, stream)
-    if top_paths is not None:
-        status = lib.ctcasr_ctc_beam_decode_nbest(
-            *head, top_paths, *model, out.data_ptr(), out_len.data_ptr(), logp.data_ptr(),
-            n_paths.data_ptr(), *tail)
-    elif scorer is None:
-        status = lib.ctcasr_ctc_beam_decode(*head, out.data_ptr(), out_len.data_ptr(),
-                                            logp.data_ptr(), *tail)
-    else:
-        status = lib.ctcasr_ctc_beam_decode_lm(*head, *model, out.data_ptr(), out_len.data_ptr(),
-                                               logp.data_ptr(), *tail)
-    torch.cuda.synchronize()
-    return status, tuple(x.cpu().numpy() for x in (out, out_len, logp, n_paths))
-
-
 @pytest.mark.parametrize('fused', [False, True], ids=['plain', 'fused'])
 def test_top_1_entry_points_are_undisturbed_by_an_nbest_launch(hip, fused):
     """Top-1, n-best, top-1 on the same bytes: the two top-1 results are identical bits and
@@ -163,11 +102,11 @@ def test_top_1_entry_points_are_undisturbed_by_an_nbest_launch(hip, fused):
     assert need == hip.ctc_beam_workspace_bytes(30, 4, 29, 32)
     workspace = torch.full((need,), 0xff, dtype=torch.uint8, device=DEV)
     lg, sl = _t(logits), _t(seq_len, torch.int32)
-    status, before = _raw(hip, lg, sl, 32, None, scorer, workspace)
+    status, before = raw_beam(hip, lg, sl, 32, scorer, workspace)
     assert status == 0
-    status, (out, out_len, logp, n_paths) = _raw(hip, lg, sl, 32, 8, scorer, workspace)
+    status, (out, out_len, logp, n_paths) = raw_beam(hip, lg, sl, 32, scorer, workspace, 8)
     assert status == 0
-    status, after = _raw(hip, lg, sl, 32, None, scorer, workspace)
+    status, after = raw_beam(hip, lg, sl, 32, scorer, workspace)
     assert status == 0
     assert _same_bits(before[:3], after[:3])
     assert _same_bits((out[:, 0], out_len[:, 0], logp[:, 0]), before[:3])
@@ -279,8 +218,8 @@ def test_fewer_leaves_than_top_paths(hip, classes):
     lg, sl = _t(logits), _t(np.array([1, 0, 1]), torch.int32)
     workspace = torch.empty(hip.ctc_beam_nbest_workspace_bytes(1, 3, classes, 8),
                             dtype=torch.uint8, device=DEV)
-    status, (out, out_len, logp, n_paths) = _raw(hip, lg, sl, 8, 8, None, workspace,
-                                                 blank=classes - 1)
+    status, (out, out_len, logp, n_paths) = raw_beam(hip, lg, sl, 8, None, workspace, 8,
+                                                     blank=classes - 1)
     assert status == 0
     assert n_paths.tolist() == [min(8, classes), 1, min(8, classes)]
     _check_structure(out, out_len, logp, n_paths, 8, classes, classes - 1)
@@ -295,11 +234,11 @@ def test_bad_top_paths_is_a_bad_argument(hip):
     workspace = torch.empty(hip.ctc_beam_nbest_workspace_bytes(6, 2, 29, 8), dtype=torch.uint8,
                             device=DEV)
     for top_paths in (0, 9, -1):
-        status, _ = _raw(hip, logits, seq_len, 8, top_paths, None, workspace)
+        status, _ = raw_beam(hip, logits, seq_len, 8, None, workspace, top_paths)
         assert status == -1, top_paths
         with pytest.raises(hip.CtcAsrError):
             hip.ctc_beam_decode_nbest(logits, seq_len, 8, top_paths)
-    status, _ = _raw(hip, logits, seq_len, 8, 8, None, workspace)
+    status, _ = raw_beam(hip, logits, seq_len, 8, None, workspace, 8)
     assert status == 0
     with pytest.raises(hip.CtcAsrError, match='1 lengths for a batch of 2'):
         hip.ctc_beam_decode_nbest(logits, seq_len[:1], 8, 2)
@@ -318,10 +257,11 @@ def test_pool_exhaustion_is_reported_as_n_paths_minus_1(hip):
     seq_len = _t(np.array([num_steps]), torch.int32)
     need = hip.ctc_beam_nbest_workspace_bytes(num_steps, 1, classes, MAX_WIDTH)
     workspace = torch.empty(need, dtype=torch.uint8, device=DEV)
-    status, _ = _raw(hip, logits, seq_len, MAX_WIDTH, 4, None, workspace, blank, nbytes=need - 1)
+    status, _ = raw_beam(hip, logits, seq_len, MAX_WIDTH, None, workspace, 4, blank,
+                         nbytes=need - 1)
     assert status == -3
-    status, (out, out_len, logp, n_paths) = _raw(hip, logits, seq_len, MAX_WIDTH, 4, None,
-                                                 workspace, blank)
+    status, (out, out_len, logp, n_paths) = raw_beam(hip, logits, seq_len, MAX_WIDTH, None,
+                                                     workspace, 4, blank)
     assert status == 0
     assert n_paths.tolist() == [-1] and (out_len == -1).all()
     small = _logits(rng, 30, 3, 29, 28)

@@ -22,6 +22,7 @@ from ctc_asr_amd import lm
 from ctc_asr_amd.params import FLAGS
 from tests import lm_beam_reference as lref
 from tests import word_lm_reference as ref
+from tests.beam_helpers import _t, raw_beam
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda'
@@ -30,10 +31,6 @@ NORMS = ['max', 'log_softmax']
 ALPHABETS = {(29, 28): (1, [2, 3, 4, 5, 6]), (6, 5): (4, [0, 1, 2, 3, 3])}
 # a one-letter word, words that are prefixes of others ('a' < 'ab' < 'abc')
 LEXICON = ['a', 'ab', 'abc', 'ba', 'cab', 'd', 'bad', 'ca', 'dd', 'acbd', 'bb', 'c']
-
-
-def _t(a, dtype=torch.float32):
-    return torch.as_tensor(np.ascontiguousarray(a), dtype=dtype).to(DEV)
 
 
 def _spell(text, classes, blank):
@@ -286,22 +283,7 @@ def test_parity_with_the_dense_automaton(hip, classes, blank, order, oov):
 # ------------------------------------------------------------------------------------------------
 # 3. Memo and workspace
 # ------------------------------------------------------------------------------------------------
-def _raw(hip, logits, seq_len, width, scorer, workspace, top_paths=2, blank=28):
-    """The C entry point on a workspace of the caller's."""
-    num_steps, batch, classes = logits.shape
-    tables, keep = hip._wordlm_struct(scorer, logits.device)
-    out = torch.full((batch, top_paths, num_steps), -7, dtype=torch.int32, device=DEV)
-    out_len = torch.full((batch, top_paths), -7, dtype=torch.int32, device=DEV)
-    logp = torch.full((batch, top_paths), float('nan'), dtype=torch.float32, device=DEV)
-    n_paths = torch.full((batch,), -7, dtype=torch.int32, device=DEV)
-    status = hip.load().ctcasr_ctc_beam_decode_wordlm(
-        logits.data_ptr(), seq_len.data_ptr(), num_steps, batch, classes, blank, width, 0,
-        top_paths, ctypes.addressof(tables), out.data_ptr(), out_len.data_ptr(), logp.data_ptr(),
-        n_paths.data_ptr(), workspace.data_ptr(), workspace.numel(),
-        torch.cuda.current_stream().cuda_stream)
-    torch.cuda.synchronize()
-    del keep
-    return status, tuple(t.cpu().numpy() for t in (out, out_len, logp, n_paths))
+_raw = functools.partial(raw_beam, top_paths=2)     # the C entry point of the scorer's rule
 
 
 def test_a_row_in_a_batch_of_64_is_the_row_alone(hip):
@@ -510,12 +492,13 @@ def test_drivers_decode_with_the_word_model_of_lm_path(trained, capsys, monkeypa
                     '--lm_path', words]) == 0
     FLAGS.update(lm_corpus_csv='', lm_unit='char')
     calls = []
-    real = hip.ctc_beam_decode_wordlm
+    real = hip.ctc_beam_search
 
-    def counted(*args, **kwargs):
-        calls.append(len(args))
-        return real(*args, **kwargs)
-    monkeypatch.setattr(hip, 'ctc_beam_decode_wordlm', counted)
+    def counted(logits, seq_len, beam_width, scorer=None, *args, **kwargs):
+        if isinstance(scorer, lm.WordLmScorer):         # the searches with the word model
+            calls.append(1)
+        return real(logits, seq_len, beam_width, scorer, *args, **kwargs)
+    monkeypatch.setattr(hip, 'ctc_beam_search', counted)
     capsys.readouterr()
     flags = ['--lm_path', words, '--lm_oov_score=-6']
     assert evaluate.main(['--dev'] + flags) == 0

@@ -8,7 +8,6 @@ dicts, materialised as the dense automaton over the reachable (trie node, contex
 executes the same float32 operations on the same float32 scores.  Shapes, logits and bars are
 those of tests/test_gpu_word_lm.py."""
 
-import ctypes
 import functools
 import os
 import re
@@ -23,7 +22,7 @@ from tests import lm_beam_reference as lref
 from tests import word_lm_lookahead_reference as laref
 from tests import word_lm_reference as ref
 from tests.test_gpu_word_lm import (ALPHABETS, LEXICON, NORMS, TEXTS, _dense_nbest, _facts, _logits,
-                                    _models, _same_bits, _t, _word, trained)  # noqa: F401
+                                    _models, _raw, _same_bits, _t, _word, trained)  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda'
@@ -106,30 +105,6 @@ def test_weight_zero_returns_the_bits_of_the_plain_launch(hip, oov):
 # ------------------------------------------------------------------------------------------------
 # 2. Memo and workspace
 # ------------------------------------------------------------------------------------------------
-def _raw(hip, logits, seq_len, width, scorer, workspace, top_paths=2, blank=28, table='own',
-         stats=None):
-    """The C entry points on a workspace of the caller's: the look-ahead one where the scorer
-    carries a table (``table``: 'own', or None for a NULL pointer), else the plain one."""
-    num_steps, batch, classes = logits.shape
-    tables, keep = hip._wordlm_struct(scorer, logits.device, stats)
-    out = torch.full((batch, top_paths, num_steps), -7, dtype=torch.int32, device=DEV)
-    out_len = torch.full((batch, top_paths), -7, dtype=torch.int32, device=DEV)
-    logp = torch.full((batch, top_paths), float('nan'), dtype=torch.float32, device=DEV)
-    n_paths = torch.full((batch,), -7, dtype=torch.int32, device=DEV)
-    head = (logits.data_ptr(), seq_len.data_ptr(), num_steps, batch, classes, blank, width, 0,
-            top_paths, ctypes.addressof(tables))
-    tail = (out.data_ptr(), out_len.data_ptr(), logp.data_ptr(), n_paths.data_ptr(),
-            workspace.data_ptr(), workspace.numel(), torch.cuda.current_stream().cuda_stream)
-    if scorer.lookahead is None:
-        status = hip.load().ctcasr_ctc_beam_decode_wordlm(*(head + tail))
-    else:
-        pointer = None if table is None else scorer.lookahead_to(logits.device).data_ptr()
-        status = hip.load().ctcasr_ctc_beam_decode_wordlm_lookahead(*(head + (pointer,) + tail))
-    torch.cuda.synchronize()
-    del keep
-    return status, tuple(t.cpu().numpy() for t in (out, out_len, logp, n_paths))
-
-
 def test_both_rules_share_one_workspace(hip):
     """Plain, look-ahead, plain, look-ahead on the same bytes (filled with 0xff first), the
     look-ahead launches at two lengths: each as on a fresh workspace - the memo of one rule never
@@ -265,12 +240,12 @@ def test_drivers_decode_with_look_ahead(trained, capsys, monkeypatch):
                     '--lm_path', words]) == 0
     FLAGS.update(lm_corpus_csv='', lm_unit='char')
     tables = []
-    real = hip.ctc_beam_decode_wordlm
+    real = hip.ctc_beam_search
 
     def counted(logits, seq_len, beam_width, scorer, *args, **kwargs):
         tables.append(scorer.lookahead is not None)
         return real(logits, seq_len, beam_width, scorer, *args, **kwargs)
-    monkeypatch.setattr(hip, 'ctc_beam_decode_wordlm', counted)
+    monkeypatch.setattr(hip, 'ctc_beam_search', counted)
     rows = input_functions.read_manifest(FLAGS.test_csv)
     wav = os.path.join(FLAGS.corpus_dir, rows[2]['path'])
     flags = ['--lm_path', words, '--lm_oov_score=-6', '--lm_weight', '1.5']
@@ -295,7 +270,7 @@ def test_drivers_decode_with_look_ahead(trained, capsys, monkeypatch):
     logits, seq_len = model.inference_fn(feats, lengths, training=False)
     for ahead in (False, True):
         scorer = lm.load(words, 29).scaled(1.5, 0.0, -6.0, lookahead=ahead)
-        out, out_len, _, _ = real(logits, seq_len, FLAGS.beam_width, scorer)
+        out, out_len, _, _ = hip.ctc_beam_decode_wordlm(logits, seq_len, FLAGS.beam_width, scorer)
         labels = out[0, 0, :int(out_len[0, 0])].cpu().tolist()
         found = re.search(r"'decoded': array\(\[([^\]]*)\]", printed[ahead])
         assert found and [int(v) for v in re.findall(r'\d+', found.group(1))] == labels, \
